@@ -15,7 +15,9 @@ A "step" is one reference training iteration (train_and_evaluate.py:43-48): nega
 model.loss() = full-graph 3-layer propagate + BPR + L2, loss.backward(), Adam step.  `value` is
 directed-edge messages per second through that step, counting the forward AND backward SpMM
 (2 * L * E_dir per step), with all inputs resident in HBM.  users_scored_per_s times
-gene_ranklist() (scoring + mask + top-50 for every user).
+gene_ranklist() (scoring + mask + top-50 for every user).  The timed region is exactly --steps steps after --warmup
+untimed ones; `ms_per_step` in the result line is its wall time per step.  --dump-outputs DIR writes what the last timed
+step computed, with inputs that are the same from run to run for the same arguments.
 
 At N > 1 the graph shards by user rows (weak scaling: every rank owns a sports-sized user shard
 over the same item set), items replicated, item-row partial sums all-reduced over RCCL per layer.
@@ -69,9 +71,17 @@ def parse():
     p.add_argument("--spmm-only", action="store_true",
                    help="N=1: stop after the timed steps and the SpMM roofline (no ranking): the command of the --pmc passes "
                         "at config 5, where a counter-collecting run of the 5 PFLOP ranking takes tens of minutes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="N=1 LightGCN: after the timed steps write what the last of them computed (loss, updated embedding "
+                        "tables, propagated table) to DIR/<name>.npy as float32, at most 64 MB (benchlib/dump.py)")
     p.add_argument("--probe-graph", action="store_true", help=argparse.SUPPRESS)   # child mode of probe_sharded_graph()
     p.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)   # child mode of the launcher's CPU test
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.model != "LightGCN"):
+        p.error("--dump-outputs: only the single-GPU LightGCN bench (--gpus 1 --model LightGCN)")
+    return args
 
 
 def main():
@@ -87,6 +97,8 @@ def main():
         return launch_selftest(world, rank)
     # CHAOREC_FORCE_SHARDED=1: run the N>1 code path (sharded model, RCCL calls, graph capture of them) on one rank
     force_sharded = world == 1 and os.environ.get("CHAOREC_FORCE_SHARDED", "0") == "1"
+    if args.dump_outputs and force_sharded:
+        raise SystemExit("--dump-outputs: only the single-GPU LightGCN bench (not CHAOREC_FORCE_SHARDED=1)")
     if args.model != "LightGCN":
         return main_model(args, world, rank, local_rank, force_sharded)
     if world == 1 and not force_sharded:

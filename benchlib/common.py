@@ -16,9 +16,6 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 
 
-MIN_TIMED_S = 0.05                   # the timed region is repeated in blocks of --steps until this much was timed
-
-
 STEADY_EVALS = 6                     # carried-threshold evaluations (one per epoch) before the timed one
 
 

@@ -7,7 +7,7 @@ import time
 import numpy as np
 import torch
 
-from .common import MIN_TIMED_S, flush_c_stdout, init_ranks  # noqa: F401
+from .common import flush_c_stdout, init_ranks  # noqa: F401
 
 
 def measure_model(args, name, world, rank, dev, sharded, backend, steps=None, warmup=None, dataset=None):
@@ -123,22 +123,12 @@ def measure_model(args, name, world, rank, dev, sharded, backend, steps=None, wa
 
     for _ in range(warmup):
         step()
-    blocks = []
-    while True:
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
-        barrier()
-        blocks.append(time.perf_counter() - t0)
-        stop = sum(blocks) >= MIN_TIMED_S or len(blocks) >= 64
-        if sharded:                             # (the ranks leave the loop together: every block ends in a barrier)
-            flag = torch.tensor([1.0 if stop else 0.0], device=dev)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            stop = float(flag.item()) > 0.0
-        if stop:
-            break
-    dt = float(np.median(blocks))
+    barrier()                                   # the timed region: exactly `steps` steps
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    barrier()
+    dt = time.perf_counter() - t0
     t = torch.tensor([dt, float(nnz_step[0]), float(U_g)], device=dev, dtype=torch.float64)
     if sharded:
         tm = t.clone()
@@ -159,8 +149,6 @@ def measure_model(args, name, world, rank, dev, sharded, backend, steps=None, wa
         "value": nnz_all / (dt / steps), "unit": "directed-edge messages/s (every SpMM launch of the train step, fwd+bwd)",
         "users_scored_per_s_incl_d2h": n_scored / (rank_ms * 1e-3),
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
-        "timed_blocks": {"blocks_of_steps": len(blocks), "ms_per_step_min": min(blocks) / steps * 1e3,
-                         "ms_per_step_max": max(blocks) / steps * 1e3},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
         "data": "real interactions, synthetic modality features, random-init weights",
         "config": {"workload": f"{name} train step on the real {dataset} graph" +

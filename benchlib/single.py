@@ -7,7 +7,7 @@ import time
 import numpy as np
 import torch
 
-from .common import BF16_MFMA_PEAK_TFLOPS, F32_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, MIN_TIMED_S, ROOT, STEADY_EVALS, TRAINED_STEPS, load_graph, spmm_kernel_name, spmm_model_bytes, spmm_source_hash  # noqa: F401
+from .common import BF16_MFMA_PEAK_TFLOPS, F32_MFMA_PEAK_TFLOPS, HBM_PEAK_GBS, ROOT, STEADY_EVALS, TRAINED_STEPS, load_graph, spmm_kernel_name, spmm_model_bytes, spmm_source_hash  # noqa: F401
 from .cpu import cpu_baseline  # noqa: F401
 from .models import measure_model  # noqa: F401
 from .record import emit
@@ -157,7 +157,7 @@ def light_step_accounting(ops, stepper, csr, U, I, D, L, edges_dev, hist, expand
                     "step's order as ONE graph"}
 
 
-def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps_rank=5, synthetic=False):
+def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps_rank=5, synthetic=False, dump_dir=None):
     """One GPU, unsharded LightGCN: the timed training steps, the SpMM roofline, gene_ranklist.  -> dict."""
     from chaorec_amd import ops, ranking
     from chaorec_amd.Model import LightGCN
@@ -200,10 +200,12 @@ def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps
             stepper.run(n, full_last=full_last)
     else:
         acc0 = torch.zeros((), device=dev)
+        last_loss = [None]                      # (captured: the graph's static loss tensor, rewritten by every replay)
 
         def drawn_loss():
             loss = model.loss_drawn(edges_dev, B, 42, 0, step_dev=batch_counter, advance=True)
             acc0.add_(loss.detach())
+            last_loss[0] = loss.detach()
             return loss
 
         graphed = None
@@ -229,23 +231,27 @@ def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps
     if not fused:
         acc0.zero_()
     n_loss[0] = 0
-    # The timed region is a block of EXACTLY `steps` steps between two synchronisations.  A block of the driver's 20
-    # sports steps is 2.5 ms (two graph replays): too short to quote alone, so the block is repeated until >= 50 ms
-    # have been timed and the MEDIAN block is the one reported; every block's ms/step is in `ms_per_step_blocks`.
+    # The timed region is EXACTLY `steps` steps between two synchronisations (--steps; no repetition: the state the steps
+    # leave behind is then the same from run to run, and --dump-outputs writes it).
     # A step built with the LIGHT forward (large graphs: optim.FusedLightGCNStep.light) computes the propagated table in the
     # rows its loss reads; the timed steps are consecutive steps INSIDE an epoch, as the training loop runs them -- the one
     # step per epoch that precedes the evaluation and leaves the whole table behind is timed separately below.
-    blocks = []
-    while True:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        run_steps(steps, full_last=False)
-        torch.cuda.synchronize()
-        blocks.append(time.perf_counter() - t0)
-        if sum(blocks) >= MIN_TIMED_S or len(blocks) >= 64:
-            break
-    dt = float(np.median(blocks))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run_steps(steps, full_last=False)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
     ms_per_step = dt / steps * 1e3
+    if dump_dir:
+        # what a caller of the last timed step receives: its loss, the updated embedding tables and (unless the step was
+        # light) the propagated table model.result -- taken before anything below reuses the step's buffers
+        from . import dump
+        outs = {"loss": (stepper.static_loss if fused else last_loss[0]).reshape(1),
+                "user_embedding": model.user_embedding.weight, "item_embedding": model.item_embedding.weight}
+        if model.result is not None:
+            outs["result"] = model.result
+        dumped = dump.write(dump_dir, outs)
+        print(f"[bench] --dump-outputs {dump_dir}: {dumped}", file=sys.stderr, flush=True)
     forward_note = None
     if fused and stepper.light:
         n_full = 3
@@ -529,7 +535,7 @@ def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps
                 out["host_ms"] = (time.perf_counter() - t1) / 3 * 1e3
         return out
 
-    steps_done = warmup + steps * len(blocks)
+    steps_done = warmup + steps
     # (BASELINE configs[4] whole is 5 PFLOP per ranking call -- seconds: one timed call, and no 4 GB rank list on the host)
     heavy = 2.0 * U * I * D > 1e15
     if heavy:
@@ -568,7 +574,7 @@ def measure_single_gpu(args, dataset, D, steps, warmup, dev, trained_steps, reps
                 cold_ms=rk["cold_ms"], cold_st=rk["cold_st"], steady="steady_ms" in rk,
                 score_st=st, score_tf=tf, sweep_alone=rk.get("sweep_alone") or early.get("sweep_alone"),
                 host_rank_ms=host_ms, edges=edges, reg=reg, table_mb=table_mb,
-                build_s=build_s, blocks_ms_per_step=[b / steps * 1e3 for b in blocks], forward=forward_note)
+                build_s=build_s, forward=forward_note)
 
 
 def scoring_roofline(r):
@@ -590,7 +596,7 @@ def main_single(args, dev):
     _lib.load()
     D = args.dim
     r = measure_single_gpu(args, args.dataset, D, args.steps, args.warmup, dev,
-                           0 if args.no_trained_state else TRAINED_STEPS, synthetic=args.synthetic)
+                           0 if args.no_trained_state else TRAINED_STEPS, synthetic=args.synthetic, dump_dir=args.dump_outputs)
     U, I = r["U"], r["I"]
     if r.get("spmm_only"):
         print(json.dumps({"metric": f"GCN edges/sec, dim={D} (--spmm-only: no ranking)", "value": r["value"],
@@ -609,10 +615,6 @@ def main_single(args, dev):
         "users_scored_per_s_incl_d2h": U / (r["host_rank_ms"] * 1e-3) if r["host_rank_ms"] else None,
         "users_scored_per_s_right_after_timed_steps": U / (r["early_ms"] * 1e-3),
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
-        "timed_blocks": {"blocks_of_steps": len(r["blocks_ms_per_step"]), "ms_per_step_min": min(r["blocks_ms_per_step"]),
-                         "ms_per_step_median": r["ms_per_step"], "ms_per_step_max": max(r["blocks_ms_per_step"]),
-                         "note": f"the --steps block repeated until >= {MIN_TIMED_S * 1e3:.0f} ms were timed; value and "
-                                 "ms_per_step are the median block"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": r["data"],
         "config": {"workload": f"LightGCN train step on the {'real' if r['data'] == 'real' else 'synthetic'} "
                                f"{args.dataset} graph (U={U}, I={I}, E_dir={r['e_dir']}), dim={D}, n_layers={r['L']}, "
@@ -677,7 +679,7 @@ def main_single(args, dev):
         for name in ("MMGCN", "FREEDOM"):
             try:
                 m = measure_model(args, name, 1, 0, dev, False, None, steps=200, warmup=20)
-                out["models"][name] = {k: m[k] for k in ("ms_per_step", "timed_blocks", "value", "unit", "steps", "warmup", "data",
+                out["models"][name] = {k: m[k] for k in ("ms_per_step", "value", "unit", "steps", "warmup", "data",
                                                          "users_scored_per_s_incl_d2h", "config", "roofline") if k in m}
             except Exception as exc:      # noqa: BLE001 -- a sub-record must not take the headline with it
                 out["models"][name] = {"error": repr(exc)[:300]}
