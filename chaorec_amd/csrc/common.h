@@ -56,9 +56,9 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 // Shared by adam_step_kernel and the SpMM kernel's Adam epilogue: same expression, same rounding.
 struct AdamConsts {
   float lr, b1, b2, eps, wd;
-  float omb1, omb2;     // 1 - beta, taken in DOUBLE on the host and then rounded, as torch does with its python floats:
-                        // (float)(1.0 - 0.999) = 0.001f, whereas 1.0f - 0.999f = 0.00099998713f (1.3e-5 off in every
-                        // exp_avg_sq increment)
+  float omb1, omb2;     // 1 - beta of the FLOAT beta this launch receives, taken in double and rounded once: for 0.999f
+                        // that is 0.00099998713f.  (torch, with the python float 0.999, uses (float)(1.0 - 0.999) = 0.001f:
+                        // the two differ by 1.3e-5 in every exp_avg_sq increment, and 1 - beta2^t below by as much.)
 };
 __host__ __device__ inline AdamConsts make_adam_consts(float lr, float b1, float b2, float eps, float wd) {
   return AdamConsts{lr, b1, b2, eps, wd, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2)};
@@ -71,7 +71,7 @@ __device__ __forceinline__ void adam_update(float &pi, float gi, float &mi, floa
   const float denom = sqrtf(vi) / bc2_sqrt + c.eps;
   pi = pi - (c.lr / bc1) * (mi / denom);
 }
-// bias corrections in double, as torch does with python floats
+// bias corrections in double from the float betas
 __device__ __forceinline__ void adam_bias_corrections(int step, float b1, float b2, float &bc1, float &bc2_sqrt) {
   bc1 = (float)(1.0 - pow((double)b1, (double)step));
   bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));

@@ -126,8 +126,12 @@ def test_layer_mean_in_last_epilogue_is_bit_identical(dev, D, L):
     assert torch.equal(ops.layer_mean_propagate(x0, csr, L), want)
 
 
-def test_multi_step_replay_equals_single_steps(dev):
+@pytest.mark.parametrize("ordered", ["1", "2"])
+def test_multi_step_replay_equals_single_steps(dev, ordered, monkeypatch):
+    """ordered "2": the same launches in the same order, so the same bits; "1": the gradient rows' float atomics may
+    add in another order"""
     from chaorec_amd.optim import FusedLightGCNStep
+    monkeypatch.setenv("CHAOREC_BPR_ORDERED", ordered)
     d = load_interactions("baby")
     U, I, edges = d["U"], d["I"], d["train"]
     (a, oa), (b, ob) = _pair(dev, U, I, edges, 64, 3)
@@ -142,4 +146,8 @@ def test_multi_step_replay_equals_single_steps(dev):
     assert float(la) == pytest.approx(float(lb), rel=1e-5)
     wa = torch.cat((a.user_embedding.weight, a.item_embedding.weight)).detach()
     wb = torch.cat((b.user_embedding.weight, b.item_embedding.weight)).detach()
+    if ordered == "2":
+        assert torch.equal(wa, wb) and torch.equal(a.result, b.result)
+        for k in ("exp_avg", "exp_avg_sq"):
+            assert torch.equal(oa.state[a.user_embedding.weight][k], ob.state[b.user_embedding.weight][k])
     assert float((wa - wb).abs().max()) <= 2e-5 and float((wa - wb).abs().mean()) <= 1e-8
