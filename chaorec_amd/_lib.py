@@ -12,7 +12,7 @@ import subprocess
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libchaorec_hip.so")
 SOURCES = ["spmm.hip", "bpr.hip", "score_topk.hip", "gemm.hip", "gemm_bf16x3.hip", "metrics.hip", "graph_dropout.hip",
-           "rowops.hip", "feature_adam.hip", "exchange.hip"]
+           "rowops.hip", "feature_adam.hip", "exchange.hip", "dgcf.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-mllvm", "-amdgpu-mfma-vgpr-form"]   # MFMA results in VGPRs: no v_accvgpr_read per compared score
 
@@ -186,6 +186,15 @@ SIGNATURES = {
                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                               ctypes.c_int32, c_ptr, c_ptr]),
     "chaorec_unique_rows": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "chaorec_dgcf_check_shape": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
+    "chaorec_dgcf_softmax_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr]),
+    "chaorec_dgcf_propagate_f32": (ctypes.c_int, [c_ptr] * 9 + [ctypes.c_int64] * 3 + [ctypes.c_int32, ctypes.c_int32, c_ptr,
+                                                                                       c_ptr, c_ptr]),
+    "chaorec_dgcf_dcor_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "chaorec_dgcf_dcor_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr,
+                                                 ctypes.c_size_t, c_ptr]),
+    "chaorec_dgcf_dcor_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr,
+                                                 c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
 }
 
 

@@ -32,6 +32,8 @@ def build_parser():
     parser.add_argument('--prompt_num', type=float, default=0.1, help='prompt modal numbers.')
     parser.add_argument('--neg_weight', type=float, default=0.1, help='weak modal weight.')
     parser.add_argument('--n_ui_layers', type=int, default=3, help='n_ui layers.')
+    parser.add_argument('--corDecay', type=float, default=0.001, help='DGCF distance-correlation weight.')
+    parser.add_argument('--n_factors', type=int, default=4, help='DGCF: the number of intents (hidden factors) k.')
     parser.add_argument('--n_iterations', type=int, default=3, help='the number of iteration.')
     parser.add_argument('--G_rate', type=float, default=0.0001, help='MMSSL')
     parser.add_argument('--cl_weight', type=float, default=2.0, help='the number of cl_loss_weight.')

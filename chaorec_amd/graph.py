@@ -411,3 +411,30 @@ def binary_sym_norm_csr(users, items, num_user, num_item):
     d = torch.from_numpy(np.power(deg.numpy() + 1e-7, -0.5))
     val = ((d[u] * 1.0) * d[U + i]).to(torch.float32)
     return coo_to_csr_coalesced(torch.cat([u, U + i]), torch.cat([U + i, u]), torch.cat([val, val]), N, N, symmetric=True)
+
+
+class DGCFStructure(CSR):
+    """DGCFConv's graph (Model/DGCF.py:27-39): the LightGCN-normalised CSR of both directions of every train_data row
+    (deg^-1/2[row] deg^-1/2[col], degrees counted on the 2E list) plus `eid` int32 [2E] = the undirected edge, i.e. the
+    train_data row, of every entry.  The reference's intent weights are `cat((s_k, s_k))` over that list, so the entry of
+    (u -> i) and the entry of (i -> u) of the same row read the same weight: a repeated interaction is two edges with two
+    weights, and its j-th copy in one direction is paired with its j-th copy in the other (the pairing ngcf_structure's
+    transpose_entry makes).  The user-row entry of edge e is its (i -> u) entry: every edge has exactly one."""
+
+    def __init__(self, csr, eid, num_user, n_edges):
+        super().__init__(csr.rowptr, csr.col, csr.val, csr.n_rows, csr.n_cols, symmetric=True)
+        self.eid, self.num_user, self.n_edges = eid, int(num_user), int(n_edges)
+
+    def to(self, device):
+        return DGCFStructure(CSR.to(self, device), self.eid.to(device), self.num_user, self.n_edges)
+
+
+def dgcf_structure(edge_index, num_user, n_nodes):
+    """edge_index: [E, 2] (user, global item id) in train_data order -> DGCFStructure (on the CPU)."""
+    csr = lightgcn_csr(edge_index, n_nodes)
+    e = torch.as_tensor(np.asarray(edge_index)).to(torch.int64)
+    E = e.shape[0]
+    dst = torch.cat([e[:, 1], e[:, 0]])          # destinations of the bidirectional list, as lightgcn_csr orders it
+    order = torch.argsort(dst, stable=True)      # the same stable sort coo_to_csr makes: entry k is list position order[k]
+    eid = (order % max(E, 1)).to(torch.int32).contiguous()
+    return DGCFStructure(csr, eid, num_user, E)

@@ -999,7 +999,8 @@ _MOVED = {
         "adam_step", "adam_bias_table", "unique_rows", "adam_lowrank_strips", "adam_lowrank", "_LinearRows",
         "linear_rows", "adam_multi", "adam_multi_max", "_SpMMAdd", "spmm_add", "edge_dropout_norm", "_SpMMValues",
         "spmm_values", "edge_dot_raw", "_EdgeDot", "edge_dot", "_NGCFLayer", "ngcf_layer", "weighted_sample_keep", "weighted_sample_keys",
-        "_RowCosineScale", "row_cosine_scale",
+        "_RowCosineScale", "row_cosine_scale", "dgcf_check_shape", "dgcf_softmax", "dgcf_propagate_raw", "dgcf_p_schedule",
+        "dgcf_forward_raw", "_DGCFForward", "dgcf_forward", "_DGCFCor", "dgcf_cor_loss",
     ),
 }
 

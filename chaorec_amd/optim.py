@@ -363,6 +363,10 @@ class GraphedTrainStep:
         had_state = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in optimizer.state[p].items()}
                      for p in params if optimizer.state.get(p)}
         saved_step = optimizer._step_dev.clone() if getattr(optimizer, "_step_dev", None) is not None else None
+        # model state the step updates in place (DGCF's intent scores: opt-in through capture_state_tensors()) goes back too
+        state_fn = getattr(model, "capture_state_tensors", None)
+        model_state = list(state_fn()) if callable(state_fn) else []
+        saved_state = [t.detach().clone() for t in model_state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -382,6 +386,8 @@ class GraphedTrainStep:
                             v.copy_(old) if old is not None else v.zero_()
             if getattr(optimizer, "_step_dev", None) is not None:
                 optimizer._step_dev.copy_(saved_step) if saved_step is not None else optimizer._step_dev.zero_()
+            for t, q in zip(model_state, saved_state):
+                t.copy_(q)
         self.graph = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)
         # (a step that holds collectives -- after_backward = a sharded model's sync_grads -- is captured in thread-local

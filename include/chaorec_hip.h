@@ -850,6 +850,43 @@ int chaorec_normalize_rows_fwd_f32(const float *a, const float *b, int64_t rows_
 int chaorec_normalize_rows_bwd_f32(const float *grad_y, const float *y, const float *norm, int64_t skip_rows,
                                    int64_t n_rows, int32_t D, float eps, float *grad_x, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * DGCF (Model/DGCF.py) -- csrc/dgcf.hip.  Intent state is ENTRY-MAJOR [E, K] (the reference keeps S as [K, E]); the graph is
+ * the LightGCN-normalised CSR (norm = deg^-1/2[row] deg^-1/2[col], Model/DGCF.py:31-37) with eid [nnz] int32 = the undirected
+ * edge (train_data row) of every entry.  Shapes: K in {1, 2, 4, 8}, D a power of two <= 256, D % (4K) == 0
+ * (chaorec_dgcf_check_shape: 0 or CHAOREC_E_INVALID with the limit in chaorec_last_error()).
+ * ------------------------------------------------------------------------------------- */
+int chaorec_dgcf_check_shape(int32_t D, int32_t K);
+
+/* P = softmax(S, over the K intents of every edge): `self.S = torch.softmax(self.S, dim=0)` (Model/DGCF.py:110). */
+int chaorec_dgcf_softmax_f32(const float *S, float *P, int64_t E, int32_t K, void *stream);
+
+/* One (layer, iteration) of DGCF.forward (Model/DGCF.py:112-140) over rows [row_begin, row_end): the K per-factor
+ * conv_embed propagates of width D/K as one launch,  acc[r] = sum_e (norm_e * P[eid_e, k]) x[col_e]  with k = the slice of
+ * the column;  y[r] = acc (y may be NULL),  zout[r] = z[r] + acc (zout may be NULL: the layer sum of :145, or the + G of the
+ * backward).  Rows r < route_end are also ROUTED (:124-140, the user rows): per entry e of the row and intent k,
+ *   S[eid_e, k] = P[eid_e, k] + < normalize(acc_k[r]), tanh(normalize(x_k[col_e])) >  and  P_next[eid_e, :] = softmax(S[eid_e, :])
+ * (P_next != P: rows that are only propagated keep reading P).  route_end <= row_begin: no routing (S, P_next unused).
+ * A_P is symmetric, so the backward is the same launch with the layer's P.  x, y, z, zout [n_rows, D] fp32, 16-byte aligned. */
+int chaorec_dgcf_propagate_f32(const int64_t *rowptr, const int32_t *col, const float *norm, const int32_t *eid,
+                               const float *P, const float *x, float *y, const float *z, float *zout, int64_t row_begin,
+                               int64_t row_end, int64_t route_end, int32_t D, int32_t K, float *S, float *P_next,
+                               void *stream);
+
+/* DGCF.cor_loss (Model/DGCF.py:179-195 with utils.distance_correlation, utils.py:83-108): the n rows table[idx[i]] cut
+ * into K slices, sum over k < K-1 of dCor(slice_k, slice_{k+1}), / ((K+1) K / 2) -> loss[0].  No n x n matrix: one pass
+ * over the pairs gives every slice's distance row sums and the pair sums (ordered: per-workgroup partials, one fixed-order
+ * combine, fp64 sums), so two runs give the same bits.  K >= 2.  The workspace (chaorec_dgcf_dcor_workspace_bytes) keeps
+ * what the backward needs: pass it unchanged to chaorec_dgcf_dcor_bwd_f32. */
+size_t chaorec_dgcf_dcor_workspace_bytes(int64_t n, int32_t D, int32_t K);
+int chaorec_dgcf_dcor_fwd_f32(const float *table, const int64_t *idx, int64_t n, int32_t D, int32_t K, float *loss, void *ws,
+                              size_t ws_bytes, void *stream);
+/* The gradient of that loss times grad_out[0]: grad_rows [n, D] per gathered row, then grad_table [n_table_rows, D] =
+ * zero except rows idx, which receive the sum over their repeats in gathered order (sorted_idx / perm: a stable sort of idx). */
+int chaorec_dgcf_dcor_bwd_f32(const int64_t *sorted_idx, const int64_t *perm, int64_t n, int32_t D, int32_t K,
+                              const float *grad_out, const void *ws, float *grad_rows, float *grad_table,
+                              int64_t n_table_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
