@@ -288,6 +288,28 @@ def capture_with_retry(capture, reset, what="step", attempts=None):
     return attempts
 
 
+def capture_graphs(bodies, reset, what="step"):
+    """One hipGraph per callable of `bodies` (each enqueues the launches of its graph) -> (the graphs in that order, the
+    attempts it took).  With no process group: one capture in the default global mode.  With one (the bodies may hold
+    collectives): settle_before_capture(), thread-local mode (capture_mode) and capture_with_retry, `reset()` between
+    attempts -- the watchdog race it handles needs RCCL's watchdog thread, which only a process group starts."""
+    graphs = []
+
+    def capture():
+        settle_before_capture()
+        graphs.clear()
+        for body in bodies:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode=capture_mode()):
+                body()
+            graphs.append(g)
+
+    if not dist.is_initialized():
+        capture()
+        return graphs, 1
+    return graphs, capture_with_retry(capture, reset, what=what)
+
+
 _SIDE_GROUPS = {}         # id of the main group (None: the default group) -> (the main group object, its side communicator)
 
 

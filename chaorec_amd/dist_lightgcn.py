@@ -11,8 +11,9 @@ import torch.nn as nn
 
 from . import _lib, graph, ops  # noqa: F401
 from .dist import (  # noqa: F401  (dist.py imports this module at its END: every name below exists by then)
-    MODES_USED, STATS, UserShard, _Pending, _active, _count, _p2p_usable, _sum_exchange_async, capture_mode,
-    capture_with_retry, exchange_buffer, joined_shard_csr, padded_rows, resolve_mode, settle_before_capture)
+    MODES_USED, STATS, UserShard, _Pending, _active, _count, _p2p_usable, _sum_exchange_async, exchange_buffer,
+    joined_shard_csr, padded_rows, resolve_mode)
+from .optim import _frontier_modes, _FusedStep
 
 
 class _ShardedLayerMean(torch.autograd.Function):
@@ -204,10 +205,19 @@ class _HipStepKernels:
     sparse_widths = (64, 256)           # chaorec_spmm_csr_rowsparse_f32 / _rowlist_f32 are built for these D
 
 
+def _shard_frontier_modes(n_rows, n_layers, D, split, kernels=_HipStepKernels, sparse_bwd=None):
+    """optim.FusedLightGCNStep.frontier_modes for a shard of n_rows rows: the widths are `kernels.sparse_widths`, and the
+    row-sparse backward exists for the split launch sequence only.  sparse_bwd: the caller's decision, None = by size."""
+    lo, hi = getattr(kernels, "sparse_widths", (1, 0))
+    if sparse_bwd is None and not split:
+        sparse_bwd = False
+    return _frontier_modes(n_rows, n_layers, D, lambda d: lo <= d <= hi and d % 4 == 0, sparse_bwd)
+
+
 SPLIT_BYTES = int(_os.environ.get("CHAOREC_DIST_SPLIT_BYTES", str(64 << 20)))     # item partial size from which a step splits
 
 
-class FusedShardedLightGCNStep:
+class FusedShardedLightGCNStep(_FusedStep):
     """optim.FusedLightGCNStep for a user-row shard: one training iteration of Model/LightGCN.py:76-135 +
     train_and_evaluate.py:43-48 on rank g's users as a fixed launch sequence -- no autograd tape, no optimizer launch for
     the user rows, Adam for them in the last backward propagate's epilogue:
@@ -236,22 +246,12 @@ class FusedShardedLightGCNStep:
         row-sparse backward (CHAOREC_LIGHT_FORWARD=0 switches it off), True / False: optim.FusedLightGCNStep's light step for
         a shard -- the last two forward layers over the frontier's rows only (see _launch_split), model.result_u / result_i
         withheld until a step with full_result=True."""
-        from .optim import FusedAdam
-        if not isinstance(optimizer, FusedAdam) or len(optimizer.param_groups) != 1:
-            raise TypeError("FusedShardedLightGCNStep needs a FusedAdam with one parameter group")
-        if model.n_layers < 1:
-            raise ValueError("FusedShardedLightGCNStep: n_layers >= 1")
-        if (edges is None) == (not given_batch):
-            raise ValueError("FusedShardedLightGCNStep: either edges (in-launch draw) or given_batch=True")
-        self.model, self.optimizer, self.B, self.L = model, optimizer, int(batch_size), model.n_layers
+        uw, iw = self._setup(model, optimizer, batch_size, edges, given_batch, capture, steps_per_replay)
         self.K = kernels or _HipStepKernels
         self.group = group if group is not None else model.group
-        self.edges, self.seed, self.step_dev, self.loss_accum = edges, seed, step_dev, loss_accum
+        self.seed, self.step_dev, self.loss_accum = seed, step_dev, loss_accum
         shard = model.shard
         U, I = shard.num_user_local, shard.num_item
-        uw, iw = model.user_embedding.weight, model.item_embedding.weight
-        if [id(p) for p in optimizer.param_groups[0]["params"]] != [id(uw), id(iw)]:
-            raise ValueError("FusedShardedLightGCNStep: the optimizer must hold exactly the two embedding tables")
         D = uw.shape[1]
         dev = uw.device
         self.U, self.I, self.N, self.D = U, I, U + I, D
@@ -262,10 +262,7 @@ class FusedShardedLightGCNStep:
         flat[U:U + I].copy_(iw.data)
         uw.data, iw.data = flat[:U], flat[U:U + I]
         self.flat = flat
-        optimizer.make_moments_adjacent([uw, iw])          # (existing moments are migrated into one buffer, not refused)
-        st_u, st_i = optimizer.state[uw], optimizer.state[iw]
-        self.m = torch.as_strided(st_u["exp_avg"], (self.N, D), (D, 1))
-        self.v = torch.as_strided(st_u["exp_avg_sq"], (self.N, D), (D, 1))
+        self._bind_moments(uw, iw, self.N, D)
         new = lambda: torch.zeros((self.N_pad, D), dtype=torch.float32, device=dev)       # (pad rows stay zero)
         self.ybuf = [new() for _ in range(max(self.L, 1))]          # x_1 .. x_L, then the backward's g buffers
         self.final, self.G, self.S = new(), new(), new()
@@ -286,21 +283,15 @@ class FusedShardedLightGCNStep:
         # rows per rank, the first backward propagate's result lives in their neighbours.  One bitmap per side and level:
         # bits = [users R0, items R0, users N1, items N1]; the ITEM bitmaps are made the union over the ranks (the seed and
         # every item partial are sums over the ranks), the user ones are local.
-        if sparse_bwd is None:
-            mode = _os.environ.get("CHAOREC_SPARSE_BACKWARD", "auto")
-            lo, hi = getattr(self.K, "sparse_widths", (1, 0))
-            sparse_bwd = self.split and lo <= D <= hi and D % 4 == 0 and self.L >= 2 and mode != "0" and \
-                (mode == "1" or self.N >= int(_os.environ.get("CHAOREC_SPARSE_BACKWARD_MIN_ROWS", "400000")))
+        _, sparse_bwd, light_by_size = _shard_frontier_modes(self.N, self.L, D, self.split, self.K, sparse_bwd)
         if sparse_bwd and not self.split:
             raise ValueError("FusedShardedLightGCNStep: the row-sparse backward exists for the split launch sequence only")
         self.sparse_bwd = bool(sparse_bwd)
         if light_forward is None:
-            light_forward = self.sparse_bwd and 2 <= self.L <= 4 and _os.environ.get("CHAOREC_LIGHT_FORWARD", "auto") != "0"
+            light_forward = light_by_size
         if light_forward and not (self.sparse_bwd and 2 <= self.L <= 4):
             raise ValueError("FusedShardedLightGCNStep: the light forward needs the row-sparse backward and 2 <= n_layers <= 4")
         self.light = bool(light_forward)
-        self.result_complete = True
-        self.graph_full = None
         self._compact = {}                   # (buffer, cap) -> ([cap, D] packed rows, bitmap prefix): _exchange_frontier
         self._cap0 = min(I, 2 * self.B * self.world)      # the batch items of all ranks: a static bound
         self._frontier_overflow = torch.zeros(1, dtype=torch.int32, device=dev)    # (sticky: check_frontier())
@@ -327,60 +318,10 @@ class FusedShardedLightGCNStep:
             # the first backward item partial: non-zero in the frontier's rows only, ALL-ZERO between steps (its exchange
             # sums whole buffers; the rows a step wrote are zeroed again by that step)
             self.Z = torch.zeros((self.N_pad - U, D), dtype=torch.float32, device=dev)
-        self.replays = 0
-        self.graph = self.graph1 = None
-        # k steps per hipGraph (in-launch batches only): a replay boundary costs ~5.5 us on this stack, the launches inside
-        # a graph follow each other without a gap
-        self.steps_per_replay = int(steps_per_replay) if (capture and edges is not None) else 1
         if capture:
             for c in (self.csr, shard.ui, shard.iu):
                 c.schedule(D)                   # lazily built by the first SpMM: must exist before capture
-            # whatever happens below (a capture that raises included), the model, the Adam moments and the step / loss
-            # counters leave this constructor as they entered it: a caller that falls back to capture=False then starts
-            # from the same state as the captured run would have
-            saved = self._save_state()
-            try:
-                s = torch.cuda.Stream(device=dev)
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._launch()                  # eager first: communicators are set up outside capture
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                self._restore_state(saved)
-                if self.light:
-                    with torch.cuda.stream(s):
-                        self._launch(light=False)       # (eager first, like the light one above)
-                    torch.cuda.current_stream().wait_stream(s)
-                    torch.cuda.synchronize()
-                    self._restore_state(saved)
-                def capture_all():                      # (every eager launch is behind us: captures only from here on)
-                    settle_before_capture()
-                    self.graph1 = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph1, capture_error_mode=capture_mode()):
-                        self._launch()
-                    self.graph = self.graph1
-                    if self.light:
-                        self.graph_full = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(self.graph_full, capture_error_mode=capture_mode()):
-                            self._launch(light=False)
-                    if self.steps_per_replay > 1:
-                        self.graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(self.graph, capture_error_mode=capture_mode()):
-                            for _ in range(self.steps_per_replay):
-                                self._launch()
-
-                def reset():
-                    self.graph = self.graph1 = self.graph_full = None
-                    torch.cuda.synchronize()
-                    self._restore_state(saved)
-
-                self.capture_attempts = capture_with_retry(capture_all, reset, what="FusedShardedLightGCNStep")
-                for gph in {id(g_): g_ for g_ in (self.graph1, self.graph, self.graph_full) if g_ is not None}.values():
-                    gph.replay()
-                torch.cuda.synchronize()
-            finally:
-                torch.cuda.synchronize()
-                self._restore_state(saved)
+            self._capture(dev)
 
     def check_frontier(self):
         """Raise if a compact frontier exchange ever saw more flagged rows than its static capacity (the pack kernel drops
@@ -394,25 +335,12 @@ class FusedShardedLightGCNStep:
                                f"exchange): the batch size changed, a later frontier outgrew the first step's by more than "
                                f"2 x, or a row bitmap was not cleared after an aborted replay")
 
-    def _counters(self):
-        return [t for t in (self.step_dev, self.loss_accum, self.optimizer._step_dev) if t is not None]
-
-    def _save_state(self):
-        return ([self.flat.clone(), self.m.clone(), self.v.clone()], [t.clone() for t in self._counters()])
-
-    def _restore_state(self, saved):
-        with torch.no_grad():
-            for dst, src in zip((self.flat, self.m, self.v), saved[0]):
-                dst.copy_(src)
-            for dst, src in zip(self._counters(), saved[1]):
-                dst.copy_(src)
-            self.G.zero_()
-            if self.sparse_bwd:
-                self._bits_all.zero_()
-                self.Z.zero_()
-                self.S.zero_()
-                if self.light:
-                    self.Z0.zero_()
+    def _state_tensors(self):
+        counters = [t for t in (self.step_dev, self.loss_accum, self.optimizer._step_dev) if t is not None]
+        zeroed = [self.G]
+        if self.sparse_bwd:
+            zeroed += [self._bits_all, self.Z, self.S] + ([self.Z0] if self.light else [])
+        return [self.flat, self.m, self.v] + counters, zeroed
 
     def _union_item_bits(self, bits):
         """An item-row bitmap becomes the union over the ranks (one small all-gather + one launch; issued BEFORE the
@@ -480,7 +408,8 @@ class FusedShardedLightGCNStep:
         return self._cap1 if self._cap1 > 0 else None
 
     @torch.no_grad()
-    def _launch(self, light=None):
+    def _launch(self, j=0, k=1, light=None):
+        """One step (j and k: the base's k-step replay; every step of one is the same launch sequence here)."""
         K, model, opt, L, B, D = self.K, self.model, self.optimizer, self.L, self.B, self.D
         U, I, N = self.U, self.I, self.N
         if model.user_embedding.weight.data_ptr() != self.flat.data_ptr() or \
@@ -689,38 +618,9 @@ class FusedShardedLightGCNStep:
             self._union_item_bits(bi1)
             K.expand_row_bits(shard.iu, bi0, bu1, self._list_u, self._list_n[0:1], bits_self=bu0)
 
-    def __call__(self, users=None, pos=None, neg=None, single=False, full_result=False):
-        """One replay = `steps_per_replay` training steps (single=True: exactly one) -> this rank's last batch loss
-        (device scalar; the global loss is the mean over ranks).  users / pos / neg (shard-local ids, items as
-        item + U_g) only in given_batch mode."""
-        if self.edges is None:
-            self.ids[0].copy_(users, non_blocking=True)
-            torch.sub(pos.to(self.ids[1].device), self.U, out=self.ids[1])
-            torch.sub(neg.to(self.ids[2].device), self.U, out=self.ids[2])
-        full = bool(full_result) and self.light
-        if self.graph is not None:
-            (self.graph_full if full else self.graph1 if single else self.graph).replay()
-        else:
-            self._launch(light=False if full else None)
-        self.replays += 1
-        self._publish(full or not self.light)
-        return self.static_loss
-
-    def run(self, n_steps, full_last=True):
-        """n_steps training steps: whole replays first, single-step replays for the remainder; with the light forward the
-        last one is a full step (full_last: the evaluation comes next)."""
-        k = self.steps_per_replay
-        tail = 1 if (self.light and full_last and n_steps > 0) else 0
-        n = n_steps - tail
-        for _ in range(n // k):
-            self()
-        for _ in range(n % k):
-            self(single=True)
-        if tail:
-            self(full_result=True)
+    def _after_run(self):
         if self._compact:                          # (compact frontier exchanges ran: one sync per run() for their overflow flag)
             self.check_frontier()
-        return self.static_loss
 
 
 def build_weak_scaling_job(dataset, world, rank, D, L, reg, device, seed=42, group=None, synthetic=False):

@@ -388,29 +388,17 @@ class GraphedTrainStep:
                 optimizer._step_dev.copy_(saved_step) if saved_step is not None else optimizer._step_dev.zero_()
             for t, q in zip(model_state, saved_state):
                 t.copy_(q)
-        self.graph = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)
-        # (a step that holds collectives -- after_backward = a sharded model's sync_grads -- is captured in thread-local
-        #  mode: RCCL's watchdog thread polls events while we capture, dist.capture_mode)
-        import torch.distributed as _td
-        mode = "thread_local" if (_td.is_available() and _td.is_initialized()) else "global"
-        if mode == "thread_local":
-            from .dist import capture_with_retry, settle_before_capture
+        from .dist import capture_graphs
 
-            def capture():
-                settle_before_capture()          # (RCCL's watchdog must have retired the warm-up's eager collectives)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode=mode):
-                    self.static_loss = self._eager(self.static)
+        def body():
+            self.static_loss = self._eager(self.static)
 
-            def reset():                         # (a capture that failed has run nothing: only its leftovers go)
-                torch.cuda.synchronize()
-                self.optimizer.zero_grad(set_to_none=True)
+        def reset():                             # (a capture that failed has run nothing: only its leftovers go)
+            torch.cuda.synchronize()
+            self.optimizer.zero_grad(set_to_none=True)
 
-            self.capture_attempts = capture_with_retry(capture, reset, what=type(model).__name__ + " train step")
-        else:
-            with torch.cuda.graph(self.graph, capture_error_mode=mode):
-                self.static_loss = self._eager(self.static)
+        (self.graph,), self.capture_attempts = capture_graphs([body], reset, what=type(model).__name__ + " train step")
         # the captured forward's output buffer: every replay rewrites it, and model.result must keep pointing at it
         # (an eager step in between -- the short last batch of an epoch -- rebinds model.result to its own tensor)
         plain_attr = not isinstance(getattr(type(model), "result", None), property)   # (a sharded model derives it)
@@ -457,7 +445,144 @@ class GraphedTrainStep:
         return self.static_loss
 
 
-class FusedLightGCNStep:
+def _frontier_modes(n_rows, n_layers, D, width_ok, sparse_bwd=None):
+    """-> (wide_ok: the frontier launches exist for this shape, the row-sparse backward, the light forward) of a fused step
+    over n_rows rows.  width_ok(D): the widths the caller's frontier launches are built for.  sparse_bwd: the caller's own
+    decision, None = by size (CHAOREC_SPARSE_BACKWARD = auto / 0 / 1, CHAOREC_SPARSE_BACKWARD_MIN_ROWS); the light forward
+    comes with the row-sparse backward for 2 <= n_layers <= 4 unless CHAOREC_LIGHT_FORWARD=0."""
+    wide_ok = n_layers >= 2 and width_ok(D)
+    if sparse_bwd is None:
+        mode = os.environ.get("CHAOREC_SPARSE_BACKWARD", "auto")
+        sparse_bwd = wide_ok and mode != "0" and (
+            mode == "1" or n_rows >= int(os.environ.get("CHAOREC_SPARSE_BACKWARD_MIN_ROWS", "400000")))
+    light = bool(sparse_bwd) and 2 <= n_layers <= 4 and os.environ.get("CHAOREC_LIGHT_FORWARD", "auto") != "0"
+    return wide_ok, sparse_bwd, light
+
+
+class _FusedStep:
+    """What FusedLightGCNStep and dist_lightgcn.FusedShardedLightGCNStep share around their launch sequences: the
+    constructor checks, the moment views, state save / restore, the capture protocol and replay.  A subclass supplies
+      _launch(j=0, k=1, light=None)  step j of a k-step replay (light: None = as built)
+      _publish(complete)             model.result after a step: the whole table, or none after a light step
+      _state_tensors()               -> (what a step updates: table, moments, counters; scratch all-zero between steps)
+      U                              the first item row: a given batch's item ids are item + U
+    and may override _after_run() (end of run())."""
+
+    def _setup(self, model, optimizer, batch_size, edges, given_batch, capture, steps_per_replay):
+        """The checks both steps make and the state they share; -> the two embedding tables."""
+        name = type(self).__name__
+        if not isinstance(optimizer, FusedAdam) or len(optimizer.param_groups) != 1:
+            raise TypeError(f"{name} needs a FusedAdam with one parameter group")
+        if model.n_layers < 1:
+            raise ValueError(f"{name}: n_layers >= 1")
+        if (edges is None) == (not given_batch):
+            raise ValueError(f"{name}: either edges (in-launch draw) or given_batch=True")
+        uw, iw = model.user_embedding.weight, model.item_embedding.weight
+        if [id(p) for p in optimizer.param_groups[0]["params"]] != [id(uw), id(iw)]:
+            raise ValueError(f"{name}: the optimizer must hold exactly the two embedding tables")
+        self.model, self.optimizer, self.B, self.L, self.edges = model, optimizer, int(batch_size), model.n_layers, edges
+        # k steps per hipGraph (in-launch batches only): a replay boundary costs ~5 us, the launches inside a graph follow
+        # each other without a gap
+        self.steps_per_replay = int(steps_per_replay) if (capture and edges is not None) else 1
+        self.graph = self.graph1 = self.graph_full = None
+        self.replays = 0
+        self.result_complete = True
+        return uw, iw
+
+    def _bind_moments(self, uw, iw, N, D):
+        """Adam's moments of the two tables in one buffer each, as the [N, D] views m / v; -> their two state dicts."""
+        self.optimizer.make_moments_adjacent([uw, iw])
+        st_u, st_i = self.optimizer.state[uw], self.optimizer.state[iw]
+        self.m = torch.as_strided(st_u["exp_avg"], (N, D), (D, 1))
+        self.v = torch.as_strided(st_u["exp_avg_sq"], (N, D), (D, 1))
+        return st_u, st_i
+
+    def _save_state(self):
+        return [t.clone() for t in self._state_tensors()[0]]
+
+    def _restore_state(self, saved):
+        kept, zeroed = self._state_tensors()
+        with torch.no_grad():
+            for dst, src in zip(kept, saved):
+                dst.copy_(src)
+            for t in zeroed:
+                t.zero_()
+
+    def _capture(self, dev):
+        """graph1 (one step), graph_full (one full step of a light-forward step) and graph (steps_per_replay steps; graph1
+        when that is 1).  Eager warm-up launches first (they build lazily made state: communicators, frontier capacities),
+        each followed by a restore.  A graph's first replay uploads it (tens of us for the k-step one): each is replayed once
+        here, so that the first replay a caller times is like every other.  The model, the moments and the counters leave
+        as they came, whatever raises (a caller that falls back to capture=False starts from the same state: ADVICE r3)."""
+        from .dist import capture_graphs
+        saved = self._save_state()
+        try:
+            s = torch.cuda.Stream(device=dev)
+            for light in ((None, False) if self.light else (None,)):
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self._launch(light=light)
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                self._restore_state(saved)
+            k = self.steps_per_replay
+            bodies = [self._launch]
+            if self.light:
+                bodies.append(lambda: self._launch(light=False))
+            if k > 1:
+                bodies.append(lambda: [self._launch(j, k) for j in range(k)])
+
+            def reset():
+                torch.cuda.synchronize()
+                self._restore_state(saved)
+
+            graphs, self.capture_attempts = capture_graphs(bodies, reset, what=type(self).__name__)
+            self.graph1, self.graph = graphs[0], graphs[-1] if k > 1 else graphs[0]
+            self.graph_full = graphs[1] if self.light else None
+            for g in graphs:
+                g.replay()
+        finally:
+            torch.cuda.synchronize()
+            self._restore_state(saved)
+
+    def __call__(self, users=None, pos=None, neg=None, single=False, full_result=False):
+        """One replay = `steps_per_replay` training steps (single=True: exactly one, whatever the replay size) -> the
+        LAST step's loss (device scalar, rewritten by the next call; per-step sums go to loss_accum).  users / pos / neg
+        (items as item + U, the reference's batch format) only in given_batch mode.  full_result=True (a step built with the
+        light forward): ONE step that leaves the whole propagated table in model.result -- the step before an evaluation."""
+        if self.edges is None:
+            self.ids[0].copy_(users, non_blocking=True)
+            torch.sub(pos.to(self.ids[1].device), self.U, out=self.ids[1])
+            torch.sub(neg.to(self.ids[2].device), self.U, out=self.ids[2])
+        full = bool(full_result) and self.light
+        if self.graph is not None:
+            (self.graph_full if full else self.graph1 if single else self.graph).replay()
+        else:
+            self._launch(light=False if full else None)
+        self.replays += 1
+        self._publish(full or not self.light)
+        return self.static_loss
+
+    def run(self, n_steps, full_last=True):
+        """n_steps training steps: whole replays first, single-step replays for the remainder.  full_last (light forward
+        only): the last of them leaves the whole propagated table behind -- an epoch's steps, with the evaluation next."""
+        k = self.steps_per_replay
+        tail = 1 if (self.light and full_last and n_steps > 0) else 0
+        n = n_steps - tail
+        for _ in range(n // k):
+            self()
+        for _ in range(n % k):
+            self(single=True)
+        if tail:
+            self(full_result=True)
+        self._after_run()
+        return self.static_loss
+
+    def _after_run(self):
+        pass
+
+
+class FusedLightGCNStep(_FusedStep):
     """One LightGCN training iteration -- train_and_evaluate.py:43-48: zero_grad, model.loss() (Model/LightGCN.py:
     123-135: L propagates + layer mean, BPR + L2), loss.backward(), Adam step -- as 2L + 2 kernel launches (2L + 1 + 1/k in a k-step replay) with no
     autograd tape and no optimizer launch, captured in one hipGraph:
@@ -484,34 +609,21 @@ class FusedLightGCNStep:
                  given_batch=False, loss_accum=None, capture=True, steps_per_replay=1, light_forward=None):
         """light_forward: None = by size (with the row-sparse backward; CHAOREC_LIGHT_FORWARD=auto/0/1), True / False: the
         forward propagates of a step restricted to the rows its loss reads (see _launch) / every row of every layer."""
-        if not isinstance(optimizer, FusedAdam) or len(optimizer.param_groups) != 1:
-            raise TypeError("FusedLightGCNStep needs a FusedAdam with one parameter group")
-        L = model.n_layers
-        if L < 1:
-            raise ValueError("FusedLightGCNStep: n_layers >= 1")
+        uw, iw = self._setup(model, optimizer, batch_size, edges, given_batch, capture, steps_per_replay)
         if not model.graph.symmetric:
             raise ValueError("FusedLightGCNStep: the propagate graph must be its own transpose")
-        if (edges is None) == (not given_batch):
-            raise ValueError("FusedLightGCNStep: either edges (in-launch draw) or given_batch=True")
-        self.model, self.optimizer, self.B, self.L = model, optimizer, int(batch_size), L
-        self.edges, self.seed, self.step_dev, self.perm, self.perm_pos = edges, seed, step_dev, perm, perm_pos
-        group = optimizer.param_groups[0]
-        uw, iw = model.user_embedding.weight, model.item_embedding.weight
-        if [id(p) for p in group["params"]] != [id(uw), id(iw)]:
-            raise ValueError("FusedLightGCNStep: the optimizer must hold exactly the two embedding tables")
-        optimizer.make_moments_adjacent([uw, iw])
-        st_u, st_i = optimizer.state[uw], optimizer.state[iw]
+        L = self.L
+        self.seed, self.step_dev, self.perm, self.perm_pos = seed, step_dev, perm, perm_pos
         flat = model._flat
         N, D = flat.shape
+        st_u, st_i = self._bind_moments(uw, iw, N, D)
         esz = 4
         if not (uw.data_ptr() == flat.data_ptr() and iw.data_ptr() == flat.data_ptr() + uw.numel() * esz
                 and st_i["exp_avg"].data_ptr() == st_u["exp_avg"].data_ptr() + uw.numel() * esz
                 and st_i["exp_avg_sq"].data_ptr() == st_u["exp_avg_sq"].data_ptr() + uw.numel() * esz):
             raise ValueError("FusedLightGCNStep: embedding tables / moments are not one contiguous run")
         dev = flat.device
-        self.N, self.D = N, D
-        self.m = torch.as_strided(st_u["exp_avg"], (N, D), (D, 1))
-        self.v = torch.as_strided(st_u["exp_avg_sq"], (N, D), (D, 1))
+        self.N, self.D, self.U = N, D, model.num_user
         self.fbuf = [torch.empty((N, D), dtype=torch.float32, device=dev) for _ in range(max(L - 1, 0))]   # x_1 .. x_{L-1}
         self.buf = (self.fbuf + [torch.empty((N, D), dtype=torch.float32, device=dev) for _ in range(2)])[:2]   # g_l
         self.final = torch.empty((N, D), dtype=torch.float32, device=dev)
@@ -563,65 +675,20 @@ class FusedLightGCNStep:
             self._row_list = torch.empty(N, dtype=torch.int32, device=dev)                  # N1's rows, in no particular order
             self._list0 = torch.empty(3 * self.B, dtype=torch.int32, device=dev)            # R0's rows
             self._long = ops.long_row_buffers(model.graph)                                  # (the list launches' long rows)
-        self.result_complete = True
-        self.steps_per_replay = int(steps_per_replay) if (capture and edges is not None) else 1
-        self.replays = 0
-        self.graph = self.graph1 = self.graph_full = None
+        if self.steps_per_replay > 1:
+            # k steps per replay: the loss bookkeeping (reduction of the per-sample terms, epoch loss, batch counter
+            # and permutation cursor) runs ONCE, after the last step -- nothing inside a step reads it, only the next
+            # step's batch draw does, and that takes its position as cursor + j B with j fixed per captured launch
+            k = self.steps_per_replay
+            self.ws_steps = torch.empty((k, 4 * self.B), dtype=torch.float32, device=dev)
+            self._fin_scratch = torch.zeros(2 * k + 1, dtype=torch.float32, device=dev)    # (+ the launch's ticket)
         if capture:
-            # schedules, lazily built by the first SpMM call, must exist before capture
-            model.graph.schedule(D)
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream())
-            saved = self._save_state()
-            with torch.cuda.stream(s):
-                self._launch()
-                if self.light:
-                    self._launch(light=False)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            self._restore_state(saved)
-            self.graph1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph1):
-                self._launch()
-            if self.light:
-                self.graph_full = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_full):
-                    self._launch(light=False)
-            self.graph = self.graph1
-            if self.steps_per_replay > 1:
-                # k steps per replay: the loss bookkeeping (reduction of the per-sample terms, epoch loss, batch counter
-                # and permutation cursor) runs ONCE, after the last step -- nothing inside a step reads it, only the next
-                # step's batch draw does, and that takes its position as cursor + j B with j fixed per captured launch
-                k = self.steps_per_replay
-                self.ws_steps = torch.empty((k, 4 * self.B), dtype=torch.float32, device=dev)
-                self._fin_scratch = torch.zeros(2 * k + 1, dtype=torch.float32, device=dev)    # (+ the launch's ticket)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    for j in range(k):
-                        self._launch(j, k)
-            # the first launch of a captured graph uploads it (tens of us for the k-step one): do it here, on a copy
-            # of the state, so that the first replay a caller times is like every other
-            saved = self._save_state()
-            for gph in {id(g_): g_ for g_ in (self.graph1, self.graph, self.graph_full) if g_ is not None}.values():
-                gph.replay()
-            torch.cuda.synchronize()
-            self._restore_state(saved)
+            model.graph.schedule(D)             # (lazily built by the first SpMM call: must exist before capture)
+            self._capture(dev)
 
-    def _counters(self):
-        return [t for t in (self.step_dev, self.perm_pos, self.loss_accum, self.optimizer._step_dev) if t is not None]
-
-    def _save_state(self):
-        return ([self.model._flat.clone(), self.m.clone(), self.v.clone()], [t.clone() for t in self._counters()])
-
-    def _restore_state(self, saved):
-        with torch.no_grad():
-            for dst, src in zip((self.model._flat, self.m, self.v), saved[0]):
-                dst.copy_(src)
-            for dst, src in zip(self._counters(), saved[1]):
-                dst.copy_(src)
-            self.G.zero_()
-            if self.bits is not None:
-                self._bits_all.zero_()
+    def _state_tensors(self):
+        counters = [t for t in (self.step_dev, self.perm_pos, self.loss_accum, self.optimizer._step_dev) if t is not None]
+        return [self.model._flat, self.m, self.v] + counters, [self.G] + ([self._bits_all] if self.sparse_bwd else [])
 
     @staticmethod
     def frontier_modes(n_rows, n_layers, D):
@@ -629,12 +696,8 @@ class FusedLightGCNStep:
         graph of n_rows rows: what __init__ decides when it is not told (CHAOREC_SPARSE_BACKWARD / CHAOREC_LIGHT_FORWARD =
         auto / 0 / 1; CHAOREC_SPARSE_BACKWARD_MIN_ROWS).  Also for callers that plan around a light step (the training
         loop picks its replay length so that a light epoch's steps fill whole replays)."""
-        mode = os.environ.get("CHAOREC_SPARSE_BACKWARD", "auto")
-        wide_ok = n_layers >= 2 and D % 4 == 0 and (D // 4) in (16, 32, 64)
-        sparse_bwd = wide_ok and mode != "0" and (mode == "1" or n_rows >= int(os.environ.get("CHAOREC_SPARSE_BACKWARD_MIN_ROWS",
-                                                                                              "400000")))
-        light = sparse_bwd and n_layers <= 4 and os.environ.get("CHAOREC_LIGHT_FORWARD", "auto") != "0"
-        return wide_ok, sparse_bwd, light
+        # (a shard's rule takes any multiple of 4 in [64, 256]: making the two agree changes behaviour, a separate issue)
+        return _frontier_modes(n_rows, n_layers, D, lambda d: d % 4 == 0 and d // 4 in (16, 32, 64))
 
     @torch.no_grad()
     def _launch(self, j=0, k=1, light=None):
@@ -701,35 +764,3 @@ class FusedLightGCNStep:
         and a reader of the rest must fail (Model.LightGCN.gene_ranklist says how to get the table)."""
         self.result_complete = bool(complete)
         self.model.result = self.final if complete else None
-
-    def __call__(self, users=None, pos=None, neg=None, single=False, full_result=False):
-        """One replay = `steps_per_replay` training steps (single=True: exactly one, whatever the replay size) -> the
-        LAST step's loss (device scalar, rewritten by the next call; per-step sums go to loss_accum).  users / pos / neg
-        (GLOBAL item ids, the reference's batch format) only in given_batch mode.  full_result=True (a step built with the
-        light forward): ONE step that leaves the whole propagated table in model.result -- the step before an evaluation."""
-        if self.edges is None:
-            self.ids[0].copy_(users, non_blocking=True)
-            torch.sub(pos.to(self.ids[1].device), self.model.num_user, out=self.ids[1])
-            torch.sub(neg.to(self.ids[2].device), self.model.num_user, out=self.ids[2])
-        full = bool(full_result) and self.light
-        if self.graph is not None:
-            (self.graph_full if full else self.graph1 if single else self.graph).replay()
-        else:
-            self._launch(light=False if full else None)
-        self.replays += 1
-        self._publish(full or not self.light)
-        return self.static_loss
-
-    def run(self, n_steps, full_last=True):
-        """n_steps training steps: whole replays first, single-step replays for the remainder.  full_last (light forward
-        only): the last of them leaves the whole propagated table behind -- an epoch's steps, with the evaluation next."""
-        k = self.steps_per_replay
-        tail = 1 if (self.light and full_last and n_steps > 0) else 0
-        n = n_steps - tail
-        for _ in range(n // k):
-            self()
-        for _ in range(n % k):
-            self(single=True)
-        if tail:
-            self(full_result=True)
-        return self.static_loss

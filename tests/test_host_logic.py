@@ -677,10 +677,21 @@ def test_frontier_modes_by_size_and_the_replay_length_of_a_light_epoch(monkeypat
     assert FusedLightGCNStep.frontier_modes(3_250_000, 3, 128) == (True, True, True)         # the config-5 shard
     assert FusedLightGCNStep.frontier_modes(3_250_000, 5, 128) == (True, True, False)        # light forward: L <= 4
     assert FusedLightGCNStep.frontier_modes(3_250_000, 3, 96)[0] is False                    # D / 4 not a lane-group size
+    # the shard's rule (dist_lightgcn.FusedShardedLightGCNStep): its launches' widths, and the split launch sequence only
+    from chaorec_amd.dist_lightgcn import _shard_frontier_modes as shard_modes
+    assert shard_modes(3_250_000, 3, 96, split=True) == (True, True, True)       # D = 96: row-sparse on a shard, dense on one GPU
+    assert shard_modes(3_250_000, 3, 128, split=False) == (True, False, False)
+    assert shard_modes(3_250_000, 3, 128, split=False, sparse_bwd=True)[1:] == (True, True)   # (the step refuses it)
+    assert shard_modes(3_250_000, 3, 288, split=True)[1] is False                # D > 256
+    assert shard_modes(44147, 3, 64, split=True) == (True, False, False)
+    assert shard_modes(1000, 2, 64, split=True, sparse_bwd=True) == (True, True, True)       # asked for: light by default
+    assert shard_modes(3_250_000, 1, 64, split=True, sparse_bwd=True) == (False, True, False)
     monkeypatch.setenv("CHAOREC_LIGHT_FORWARD", "0")
     assert FusedLightGCNStep.frontier_modes(3_250_000, 3, 128) == (True, True, False)
+    assert shard_modes(3_250_000, 3, 128, split=True) == (True, True, False)
     monkeypatch.setenv("CHAOREC_SPARSE_BACKWARD", "1")
     assert FusedLightGCNStep.frontier_modes(1000, 2, 64)[1] is True
+    assert shard_modes(1000, 2, 64, split=True)[1] is True and shard_modes(1000, 2, 64, split=False)[1] is False
 
 
 def test_pair_structure_layout():
