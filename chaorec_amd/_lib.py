@@ -3,9 +3,14 @@
 The HIP library IS the product's compute path: there is no CPU or eager-PyTorch fallback.
 `load()` raises if the shared object is missing, and every op in chaorec_amd.ops raises on
 non-CUDA tensors.
+
+The header is the only description of the ABI: SIGNATURES and ABI_VERSION are parsed from it at import, and `load()`
+makes every export that returns a status raise on a non-zero one.  Adding an export = its prototype in the header, its
+kernel, and its wrapper in ops*.py; nothing here changes (but INT_VALUE_EXPORTS, if its `int` result is a value).
 """
 import ctypes
 import os
+import re
 import shutil
 import subprocess
 
@@ -17,185 +22,54 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
                "-mllvm", "-amdgpu-mfma-vgpr-form"]   # MFMA results in VGPRs: no v_accvgpr_read per compared score
 
 _lib = None
-ABI_VERSION = 16
+_HEADER = os.path.join(os.path.dirname(_CSRC), "..", "include", "chaorec_hip.h")
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+# exports whose `int` result the caller reads; every other `int` result is a status that load() checks
+INT_VALUE_EXPORTS = {"chaorec_abi_version", "chaorec_spmm_rows_per_wave", "chaorec_spmm_long_threshold",
+                     "chaorec_adam_lowrank_strips", "chaorec_adam_multi_max",
+                     "chaorec_dgcf_check_shape"}   # a status, turned into a ValueError by ops_extra.dgcf_check_shape
 
-c_i64p = ctypes.c_void_p
-c_ptr = ctypes.c_void_p
 
-# name -> (restype, argtypes); mirrors include/chaorec_hip.h one to one
-SIGNATURES = {
-    "chaorec_abi_version": (ctypes.c_int, []),
-    "chaorec_last_error": (ctypes.c_char_p, []),
-    "chaorec_spmm_csr_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                            ctypes.c_int32, ctypes.c_float, c_ptr, ctypes.c_float, c_ptr, c_ptr,
-                                            ctypes.c_float, c_ptr, ctypes.c_int32, c_ptr]),
-    "chaorec_spmm_csr_mean_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                                 ctypes.c_int32, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_float, c_ptr,
-                                                 ctypes.c_int32, c_ptr]),
-    "chaorec_spmm_csr_adam_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                                 ctypes.c_int32, ctypes.c_float, c_ptr, ctypes.c_float, c_ptr,
-                                                 ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float,
-                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                 ctypes.c_int32, c_ptr, ctypes.c_int64, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_spmm_csr_rowsparse_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                                      ctypes.c_int32, ctypes.c_float, c_ptr, ctypes.c_float, c_ptr,
-                                                      ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int32, c_ptr]),
-    "chaorec_expand_row_bits": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, c_ptr,
-                                               ctypes.c_int64, c_ptr]),
-    "chaorec_zero_rows_by_bits_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_or_words_u32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int64, c_ptr]),
-    "chaorec_rows_list_from_bits": (ctypes.c_int, [c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_rows_mean_by_bits_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_float, c_ptr, ctypes.c_int64, ctypes.c_int32,
-                                                     c_ptr, c_ptr]),
-    "chaorec_spmm_csr_rowlist_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32,
-                                                    ctypes.c_float, c_ptr, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr,
-                                                    ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr,
-                                                    ctypes.c_int64, ctypes.c_int32, c_ptr]),
-    "chaorec_batch_rows": (ctypes.c_int, [c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                          ctypes.c_uint64, ctypes.c_uint64, c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr,
-                                          c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_bpr_fwd_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64,
-                                               ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, c_ptr, c_ptr, c_ptr,
-                                               c_ptr, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                               c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                               ctypes.c_float, ctypes.c_float, c_ptr, c_ptr]),
-    "chaorec_bpr_fwd_bwd_at_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64,
-                                                  ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, c_ptr, c_ptr, c_ptr,
-                                                  c_ptr, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                  c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr,
-                                                  c_ptr, c_ptr, ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, ctypes.c_int64,
-                                                  c_ptr]),
-    "chaorec_bpr_finalize_steps_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                      ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                                      c_ptr, c_ptr]),
-    "chaorec_bpr_finalize_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr,
-                                                c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, ctypes.c_float, c_ptr,
-                                                c_ptr]),
-    "chaorec_spmm_rows_per_wave": (ctypes.c_int, [ctypes.c_int32]),
-    "chaorec_spmm_long_threshold": (ctypes.c_int, []),
-    "chaorec_spmm_schedule_len": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
-    "chaorec_spmm_build_schedule": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr,
-                                                   ctypes.c_int64]),
-    "chaorec_bpr_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_bpr_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int32,
-                                           c_ptr, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_bpr_bwd_ordered_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int32,
-                                                   c_ptr, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_sample_negatives": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_uint64, ctypes.c_uint64, c_ptr, ctypes.c_int64, c_ptr, c_ptr]),
-    "chaorec_draw_batch": (ctypes.c_int, [c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int32, ctypes.c_int64,
-                                          ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                          ctypes.c_int64, c_ptr]),
-    "chaorec_exchange_pull_sum_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_ptr, c_ptr]),
-    "chaorec_exchange_pull_gather_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int64, c_ptr, c_ptr]),
-    "chaorec_rows_copy_by_bits_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_exchange_pull_sum_rows_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                          ctypes.c_int32, c_ptr, c_ptr, c_ptr]),
-    "chaorec_exchange_pull_gather_rows_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                             c_ptr, c_ptr, c_ptr]),
-    "chaorec_frontier_pack_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_frontier_unpack_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_shift_cat_i64": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_score_topk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                            ctypes.c_int32]),
-    "chaorec_score_topk_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                              c_ptr, c_ptr, ctypes.c_float, ctypes.c_int32, ctypes.c_int64,
-                                              c_ptr, c_ptr, c_ptr, ctypes.c_size_t, ctypes.c_int32, c_ptr]),
-    "chaorec_score_topk_hinted_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                     c_ptr, c_ptr, ctypes.c_float, ctypes.c_int32, ctypes.c_int64,
-                                                     c_ptr, c_ptr, c_ptr, ctypes.c_size_t, c_ptr, c_ptr,
-                                                     ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_score_topk_stats": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                c_ptr, c_ptr]),
-    "chaorec_rank_metrics_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
-    "chaorec_rank_metrics_f64": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, c_ptr, c_ptr, c_ptr, ctypes.c_int64,
-                                                c_ptr, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_size_t, c_ptr]),
-    "chaorec_gemm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_ptr,
-                                        ctypes.c_size_t, c_ptr]),
-    "chaorec_gemm_nt_bf16x3_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_nt_bf16x3": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, c_ptr,
-                                              ctypes.c_size_t, c_ptr]),
-    "chaorec_adam_step_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_float,
-                                             ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                             ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_edge_dropout_norm": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
-                                                 ctypes.c_uint64, ctypes.c_uint64, c_ptr, ctypes.c_uint32, c_ptr, c_ptr,
-                                                 c_ptr, c_ptr, c_ptr]),
-    "chaorec_row_cosine_scale_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr]),
-    "chaorec_row_cosine_scale_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64,
-                                                        ctypes.c_int32, c_ptr]),
-    "chaorec_bpr_fwd_drawn_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr, c_ptr, ctypes.c_int64,
-                                                 ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, c_ptr, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr, c_ptr,
-                                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_reduce_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_colsum_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_ptr, c_ptr,
-                                          ctypes.c_size_t, c_ptr]),
-    "chaorec_sum_f32": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_float, c_ptr, c_ptr, ctypes.c_size_t, c_ptr]),
-    "chaorec_weighted_sample_workspace_bytes": (ctypes.c_size_t, []),
-    "chaorec_weighted_sample_keep": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
-                                                    ctypes.c_uint64, c_ptr, c_ptr, ctypes.c_size_t, c_ptr, c_ptr,
-                                                    c_ptr]),
-    "chaorec_weighted_sample_keys": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, c_ptr,
-                                                    c_ptr, c_ptr]),
-    "chaorec_leaky_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_float, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_mul_pair_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_rows_mean_f32": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_float, c_ptr, ctypes.c_int64, c_ptr]),
-    "chaorec_adam_lowrank_strips": (ctypes.c_int32, [ctypes.c_int32]),
-    "chaorec_adam_bias_table": (ctypes.c_int, [c_ptr, ctypes.c_int32, ctypes.c_float, ctypes.c_float, c_ptr]),
-    "chaorec_adam_lowrank_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                ctypes.c_float, ctypes.c_float, ctypes.c_int32, c_ptr, ctypes.c_int32,
-                                                c_ptr, c_ptr, ctypes.c_int32, c_ptr, c_ptr, ctypes.c_int32,
-                                                ctypes.c_int32, c_ptr]),
-    "chaorec_gemm_tn_bf16x3_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_tn_bf16x3": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_ptr, ctypes.c_size_t,
-                                              c_ptr]),
-    "chaorec_gemm_nn_bf16x3_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_nn_bf16x3": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, c_ptr,
-                                              ctypes.c_size_t, c_ptr]),
-    "chaorec_bpr_multi_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_bpr_multi_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_int32,
-                                                 ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_bpr_multi_bwd_ordered_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int32, c_ptr, c_ptr, c_ptr, ctypes.c_int32,
-                                                         ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_gemm_nt_bf16x3_dual": (ctypes.c_int, [c_ptr] * 7 + [ctypes.c_int64] * 9 + [ctypes.c_int32, ctypes.c_int32, c_ptr]),
-    "chaorec_gemm_nn_bf16x3_dual_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_nn_bf16x3_dual": (ctypes.c_int, [c_ptr] * 5 + [ctypes.c_int64] * 9 + [c_ptr, ctypes.c_size_t, c_ptr]),
-    "chaorec_gemm_tn_bf16x3_dual_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    "chaorec_gemm_tn_bf16x3_dual": (ctypes.c_int, [c_ptr] * 5 + [ctypes.c_int64] * 9 + [c_ptr, ctypes.c_size_t, c_ptr]),
-    "chaorec_edge_dot_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr]),
-    "chaorec_leaky_cat_add_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_float, c_ptr]),
-    "chaorec_leaky_split_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int64,
-                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_ptr]),
-    "chaorec_normalize_rows_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                      ctypes.c_float, c_ptr, c_ptr, c_ptr]),
-    "chaorec_normalize_rows_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int64,
-                                                      ctypes.c_int32, ctypes.c_float, c_ptr, c_ptr]),
-    "chaorec_adam_multi_max": (ctypes.c_int32, []),
-    "chaorec_adam_multi_f32": (ctypes.c_int, [ctypes.c_int32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                              ctypes.c_int32, c_ptr, c_ptr]),
-    "chaorec_unique_rows": (ctypes.c_int, [c_ptr, ctypes.c_int64, ctypes.c_int64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "chaorec_dgcf_check_shape": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
-    "chaorec_dgcf_softmax_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, c_ptr]),
-    "chaorec_dgcf_propagate_f32": (ctypes.c_int, [c_ptr] * 9 + [ctypes.c_int64] * 3 + [ctypes.c_int32, ctypes.c_int32, c_ptr,
-                                                                                       c_ptr, c_ptr]),
-    "chaorec_dgcf_dcor_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
-    "chaorec_dgcf_dcor_fwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr,
-                                                 ctypes.c_size_t, c_ptr]),
-    "chaorec_dgcf_dcor_bwd_f32": (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_ptr, c_ptr,
-                                                 c_ptr, c_ptr, ctypes.c_int64, c_ptr]),
-}
+def _ctype(decl, name, is_return=False):
+    """One return type or one parameter (its name optional) -> the ctypes type; never a guess."""
+    words = decl.replace("*", " * ").split()
+    if re.search(r"[^\w\s*]", decl):      # an array, a function pointer, `...`: not this header's style
+        words = []
+    if "*" in words:
+        if not is_return:
+            return ctypes.c_void_p
+        if words == ["const", "char", "*"]:
+            return ctypes.c_char_p
+    elif words and words[0] in _SCALARS and len(words) <= (1 if is_return else 2):
+        return _SCALARS[words[0]]
+    raise ValueError(f"chaorec_hip.h: {name}: no ctypes type for '{decl.strip()}'")
+
+
+def parse_header(text):
+    """(ABI version, {name: (restype, [argtypes])}) of a header in chaorec_hip.h's plain style: comments, preprocessor
+    lines and the extern "C" braces aside, it is nothing but `type chaorec_name(type [name], ...);` prototypes."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+CHAOREC_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    if not version:
+        raise ValueError("chaorec_hip.h: no '#define CHAOREC_ABI_VERSION <number>'")
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
+    sigs = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(chaorec_\w+) ?\((.*)\)", stmt)
+        if not m or m.group(2) in sigs:
+            raise ValueError(f"chaorec_hip.h: not the one prototype of a chaorec_* function: '{stmt}'")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_ctype(ret, name, True), [_ctype(p, name) for p in params])
+    return int(version.group(1)), sigs
+
+
+if not os.path.exists(_HEADER):
+    raise RuntimeError(f"{os.path.normpath(_HEADER)} is missing: the ctypes binding of libchaorec_hip.so is derived from "
+                       "it (chaorec_amd ships with its include/ directory).")
+with open(_HEADER) as _f:
+    ABI_VERSION, SIGNATURES = parse_header(_f.read())   # name -> (restype, argtypes), applied to the CDLL by load()
 
 
 def _experiment_flags():
@@ -224,7 +98,7 @@ def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".h", ".hpp"))]
-    hdrs += [os.path.join(os.path.dirname(_CSRC), "..", "include", "chaorec_hip.h"), os.path.abspath(__file__)]
+    hdrs += [_HEADER, os.path.abspath(__file__)]
     extra, drop = _experiment_flags()
     lib_path = current_lib_path()
     if not force and os.path.exists(lib_path) and all(os.path.getmtime(lib_path) >= os.path.getmtime(d) for d in srcs + hdrs):
@@ -281,17 +155,19 @@ def load():
     # (python __graft_entry__.py smoke: build() loads the library, smoke() then imported torch)
     import torch  # noqa: F401
     lib = ctypes.CDLL(lib_path)
+    def raise_on_status(rc, fn, args):
+        if rc != 0:
+            msg = lib.chaorec_last_error()
+            raise RuntimeError(f"{fn.__name__} failed ({rc}): {msg.decode() if msg else ''}")
+        return rc
+
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library drift
         fn.restype = res
         fn.argtypes = args
+        if res is ctypes.c_int and name not in INT_VALUE_EXPORTS:
+            fn.errcheck = raise_on_status   # a status is checked here, under the called function's own name
     if lib.chaorec_abi_version() != ABI_VERSION:
         raise RuntimeError("libchaorec_hip.so ABI version mismatch")
     _lib = lib
     return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().chaorec_last_error()
-        raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")

@@ -474,22 +474,18 @@ class P2PExchange:
         if bits is not None:
             D = buf.shape[1]
             nb = buf.shape[0] // self.world
-            _lib.check(lib.chaorec_rows_copy_by_bits_f32(ops._ptr(box["P"]), ops._ptr(buf), n_rows, D, ops._ptr(bits), stream),
-                       "chaorec_rows_copy_by_bits_f32")
+            lib.chaorec_rows_copy_by_bits_f32(ops._ptr(box["P"]), ops._ptr(buf), n_rows, D, ops._ptr(bits), stream)
             self._barrier()
-            _lib.check(lib.chaorec_exchange_pull_sum_rows_f32(box["pP"], self.world, self.rank * nb, nb, n_rows, D, ops._ptr(bits),
-                                                              ops._ptr(box["R"]), stream), "chaorec_exchange_pull_sum_rows_f32")
+            lib.chaorec_exchange_pull_sum_rows_f32(box["pP"], self.world, self.rank * nb, nb, n_rows, D, ops._ptr(bits),
+                                                   ops._ptr(box["R"]), stream)
             self._barrier()
-            _lib.check(lib.chaorec_exchange_pull_gather_rows_f32(box["pR"], self.world, nb, n_rows, D, ops._ptr(bits), ops._ptr(buf),
-                                                                 stream), "chaorec_exchange_pull_gather_rows_f32")
+            lib.chaorec_exchange_pull_gather_rows_f32(box["pR"], self.world, nb, n_rows, D, ops._ptr(bits), ops._ptr(buf), stream)
             return
         box["P"].copy_(buf.reshape(-1))
         self._barrier()
-        _lib.check(lib.chaorec_exchange_pull_sum_f32(box["pP"], self.world, self.rank * block, block, ops._ptr(box["R"]),
-                                                     stream), "chaorec_exchange_pull_sum_f32")
+        lib.chaorec_exchange_pull_sum_f32(box["pP"], self.world, self.rank * block, block, ops._ptr(box["R"]), stream)
         self._barrier()
-        _lib.check(lib.chaorec_exchange_pull_gather_f32(box["pR"], self.world, block, ops._ptr(buf), stream),
-                   "chaorec_exchange_pull_gather_f32")
+        lib.chaorec_exchange_pull_gather_f32(box["pR"], self.world, block, ops._ptr(buf), stream)
 
 
 def _p2p_usable(buf, group):

@@ -139,10 +139,9 @@ class CSR:
                 val = self.val.cpu().contiguous()
                 n = lib.chaorec_spmm_schedule_len(self.n_rows, int(D))
                 out = torch.empty(n, dtype=torch.int32)
-                rc = lib.chaorec_spmm_build_schedule(ctypes.c_void_p(rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
-                                                     ctypes.c_void_p(val.data_ptr()), self.n_rows, int(D),
-                                                     ctypes.c_void_p(out.data_ptr()), n)
-                _lib.check(rc, "chaorec_spmm_build_schedule")
+                lib.chaorec_spmm_build_schedule(ctypes.c_void_p(rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
+                                                ctypes.c_void_p(val.data_ptr()), self.n_rows, int(D),
+                                                ctypes.c_void_p(out.data_ptr()), n)
                 self._orders[g] = out.to(self.rowptr.device)
             self._order_dims[g] = int(D)
         return self._orders[g]

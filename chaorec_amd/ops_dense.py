@@ -29,10 +29,8 @@ def gemm_raw(A, B, transA=False, transB=False, bias=None, out=None, accumulate=F
     lib = _lib.load()
     nbytes = lib.chaorec_gemm_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device) if nbytes else None
-    rc = lib.chaorec_gemm_f32(_ptr(A), _ptr(B), _ptr(out), _ptr(bias), M, N, K, A.shape[1], B.shape[1],
-                              out.stride(0), int(transA), int(transB), int(accumulate), act, _ptr(ws), nbytes,
-                              _stream())
-    _lib.check(rc, "chaorec_gemm_f32")
+    lib.chaorec_gemm_f32(_ptr(A), _ptr(B), _ptr(out), _ptr(bias), M, N, K, A.shape[1], B.shape[1],
+                         out.stride(0), int(transA), int(transB), int(accumulate), act, _ptr(ws), nbytes, _stream())
     return out
 
 
@@ -52,9 +50,8 @@ def gemm_nt_bf16x3(x, weight, bias=None, act=0, out=None):
     lib = _lib.load()
     nbytes = lib.chaorec_gemm_nt_bf16x3_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    rc = lib.chaorec_gemm_nt_bf16x3(_ptr(x), _ptr(weight), _ptr(out), _ptr(bias), M, N, K, x.stride(0), weight.stride(0),
-                                    out.stride(0), act, _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "chaorec_gemm_nt_bf16x3")
+    lib.chaorec_gemm_nt_bf16x3(_ptr(x), _ptr(weight), _ptr(out), _ptr(bias), M, N, K, x.stride(0), weight.stride(0),
+                               out.stride(0), act, _ptr(ws), nbytes, _stream())
     return out
 
 
@@ -72,9 +69,8 @@ def gemm_tn_bf16x3(gy, x, out=None):
     lib = _lib.load()
     nbytes = lib.chaorec_gemm_tn_bf16x3_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    rc = lib.chaorec_gemm_tn_bf16x3(_ptr(gy), _ptr(x), _ptr(out), M, N, K, gy.stride(0), x.stride(0), out.stride(0),
-                                    _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "chaorec_gemm_tn_bf16x3")
+    lib.chaorec_gemm_tn_bf16x3(_ptr(gy), _ptr(x), _ptr(out), M, N, K, gy.stride(0), x.stride(0), out.stride(0),
+                               _ptr(ws), nbytes, _stream())
     return out
 
 
@@ -96,9 +92,8 @@ def gemm_nn_bf16x3(gy, weight, out=None, accumulate=False):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device) if nbytes else None
     if accumulate and out is None:
         raise ValueError("gemm_nn_bf16x3: accumulate needs `out`")
-    rc = lib.chaorec_gemm_nn_bf16x3(_ptr(gy), _ptr(weight), _ptr(out), M, N, K, gy.stride(0), weight.stride(0),
-                                    out.stride(0), int(bool(accumulate)), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "chaorec_gemm_nn_bf16x3")
+    lib.chaorec_gemm_nn_bf16x3(_ptr(gy), _ptr(weight), _ptr(out), M, N, K, gy.stride(0), weight.stride(0),
+                               out.stride(0), int(bool(accumulate)), _ptr(ws), nbytes, _stream())
     return out
 
 
@@ -115,9 +110,8 @@ def gemm_nt_bf16x3_dual(x, w1, w2, b1, b2, act1, act2):
     M, K, N1, N2 = x.shape[0], x.shape[1], w1.shape[0], w2.shape[0]
     y1 = torch.empty((M, N1), dtype=torch.float32, device=x.device)
     y2 = torch.empty((M, N2), dtype=torch.float32, device=x.device)
-    rc = _lib.load().chaorec_gemm_nt_bf16x3_dual(_ptr(x), _ptr(w1), _ptr(w2), _ptr(y1), _ptr(y2), _ptr(b1), _ptr(b2), M, N1, N2, K,
-                                                 x.stride(0), w1.stride(0), w2.stride(0), N1, N2, act1, act2, _stream())
-    _lib.check(rc, "chaorec_gemm_nt_bf16x3_dual")
+    _lib.load().chaorec_gemm_nt_bf16x3_dual(_ptr(x), _ptr(w1), _ptr(w2), _ptr(y1), _ptr(y2), _ptr(b1), _ptr(b2), M, N1, N2, K,
+                                            x.stride(0), w1.stride(0), w2.stride(0), N1, N2, act1, act2, _stream())
     return y1, y2
 
 
@@ -131,9 +125,8 @@ def gemm_nn_bf16x3_dual(g1, g2, w1, w2):
     lib = _lib.load()
     nbytes = lib.chaorec_gemm_nn_bf16x3_dual_workspace_bytes(M, N, K1 + K2)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=g1.device) if nbytes else None
-    rc = lib.chaorec_gemm_nn_bf16x3_dual(_ptr(g1), _ptr(g2), _ptr(w1), _ptr(w2), _ptr(out), M, N, K1, K2, g1.stride(0), g2.stride(0),
-                                         w1.stride(0), w2.stride(0), N, _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "chaorec_gemm_nn_bf16x3_dual")
+    lib.chaorec_gemm_nn_bf16x3_dual(_ptr(g1), _ptr(g2), _ptr(w1), _ptr(w2), _ptr(out), M, N, K1, K2, g1.stride(0), g2.stride(0),
+                                    w1.stride(0), w2.stride(0), N, _ptr(ws), nbytes, _stream())
     return out
 
 
@@ -148,9 +141,8 @@ def gemm_tn_bf16x3_dual(g1, g2, x):
     lib = _lib.load()
     nbytes = lib.chaorec_gemm_tn_bf16x3_dual_workspace_bytes(M1 + M2, N, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    rc = lib.chaorec_gemm_tn_bf16x3_dual(_ptr(g1), _ptr(g2), _ptr(x), _ptr(o1), _ptr(o2), M1, M2, N, K, g1.stride(0), g2.stride(0),
-                                         x.stride(0), N, N, _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "chaorec_gemm_tn_bf16x3_dual")
+    lib.chaorec_gemm_tn_bf16x3_dual(_ptr(g1), _ptr(g2), _ptr(x), _ptr(o1), _ptr(o2), M1, M2, N, K, g1.stride(0), g2.stride(0),
+                                    x.stride(0), N, N, _ptr(ws), nbytes, _stream())
     return o1, o2
 
 
@@ -172,8 +164,7 @@ def _leaky_bwd_raw(y, gy, act):
     if gy.numel() % 4 == 0:
         gy = gy.contiguous()
         g = torch.empty_like(gy)
-        _lib.check(_lib.load().chaorec_leaky_bwd_f32(_ptr(y), _ptr(gy), slope, _ptr(g), g.numel(), _stream()),
-                   "chaorec_leaky_bwd_f32")
+        _lib.load().chaorec_leaky_bwd_f32(_ptr(y), _ptr(gy), slope, _ptr(g), g.numel(), _stream())
         return g
     return torch.where(y > 0, gy, gy * slope)
 
@@ -247,8 +238,7 @@ def leaky_cat_add(s, u, id_rows=None, out=None, slope=0.01):
     n, d1, d2 = s.shape[0], s.shape[1], u.shape[1]
     if out is None:
         out = torch.empty((n, d1 + d2), dtype=torch.float32, device=s.device)
-    _lib.check(_lib.load().chaorec_leaky_cat_add_f32(_ptr(s), _ptr(u), _ptr(id_rows), _ptr(out), n, d1, d2, slope, _stream()),
-               "chaorec_leaky_cat_add_f32")
+    _lib.load().chaorec_leaky_cat_add_f32(_ptr(s), _ptr(u), _ptr(id_rows), _ptr(out), n, d1, d2, slope, _stream())
     return out
 
 
@@ -261,8 +251,8 @@ def leaky_split_bwd(gcat, cat, uy, d1, want_gid=False, slope=0.01):
     gs = torch.empty((n, d1), dtype=torch.float32, device=gcat.device)
     gu = torch.empty((n, d2), dtype=torch.float32, device=gcat.device)
     gid = torch.empty((n, d2), dtype=torch.float32, device=gcat.device) if want_gid else None
-    _lib.check(_lib.load().chaorec_leaky_split_bwd_f32(_ptr(gcat), _ptr(cat), _ptr(uy), _ptr(gs), _ptr(gu), _ptr(gid), n, d1,
-                                                       d2, slope, _stream()), "chaorec_leaky_split_bwd_f32")
+    _lib.load().chaorec_leaky_split_bwd_f32(_ptr(gcat), _ptr(cat), _ptr(uy), _ptr(gs), _ptr(gu), _ptr(gid), n, d1,
+                                            d2, slope, _stream())
     return gs, gu, gid
 
 
@@ -369,8 +359,7 @@ class _NormalizeRows(torch.autograd.Function):
         na, nb, D = a.shape[0], (b.shape[0] if b is not None else 0), a.shape[1]
         y = torch.empty((na + nb, D), dtype=torch.float32, device=a.device)
         norm = torch.empty(na + nb, dtype=torch.float32, device=a.device)
-        _lib.check(_lib.load().chaorec_normalize_rows_fwd_f32(_ptr(a), _ptr(b), na, na + nb, D, eps, _ptr(y), _ptr(norm),
-                                                              _stream()), "chaorec_normalize_rows_fwd_f32")
+        _lib.load().chaorec_normalize_rows_fwd_f32(_ptr(a), _ptr(b), na, na + nb, D, eps, _ptr(y), _ptr(norm), _stream())
         ctx.save_for_backward(y, norm)
         ctx.na, ctx.eps = na, eps
         return y
@@ -381,8 +370,8 @@ class _NormalizeRows(torch.autograd.Function):
         gy = gy.contiguous()
         skip = 0 if ctx.needs_input_grad[0] else ctx.na
         gx = torch.empty_like(y)
-        _lib.check(_lib.load().chaorec_normalize_rows_bwd_f32(_ptr(gy), _ptr(y), _ptr(norm), skip, y.shape[0], y.shape[1],
-                                                              ctx.eps, _ptr(gx), _stream()), "chaorec_normalize_rows_bwd_f32")
+        _lib.load().chaorec_normalize_rows_bwd_f32(_ptr(gy), _ptr(y), _ptr(norm), skip, y.shape[0], y.shape[1],
+                                                   ctx.eps, _ptr(gx), _stream())
         return (gx[:ctx.na] if ctx.needs_input_grad[0] else None), (gx[ctx.na:] if ctx.needs_input_grad[1] else None), None
 
 

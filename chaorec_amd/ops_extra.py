@@ -19,19 +19,16 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999
     launch can be captured in a hipGraph.  `numel` > param.numel(): the four arrays continue contiguously past this
     tensor (adjacent parameters updated by one launch, see optim.FusedAdam)."""
     _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev)
-    rc = _lib.load().chaorec_adam_step_f32(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                           param.numel() if numel is None else int(numel),
-                                           lr, betas[0], betas[1], eps, weight_decay, int(step), _ptr(step_dev),
-                                           _stream())
-    _lib.check(rc, "chaorec_adam_step_f32")
+    _lib.load().chaorec_adam_step_f32(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                      param.numel() if numel is None else int(numel),
+                                      lr, betas[0], betas[1], eps, weight_decay, int(step), _ptr(step_dev), _stream())
 
 
 def adam_bias_table(n_steps, betas, device):
     """float [n_steps, 2]: (1 - beta1^s, sqrt(1 - beta2^s)) per step s (entry 0 unused), computed by the device with the
     same double-precision expression every Adam launch uses for its own step."""
     t = torch.empty((int(n_steps), 2), dtype=torch.float32, device=device)
-    _lib.check(_lib.load().chaorec_adam_bias_table(_ptr(t), int(n_steps), betas[0], betas[1], _stream()),
-               "chaorec_adam_bias_table")
+    _lib.load().chaorec_adam_bias_table(_ptr(t), int(n_steps), betas[0], betas[1], _stream())
     return t
 
 
@@ -42,8 +39,8 @@ def unique_rows(rows, claim, stamp_dev, out_list, out_count):
     rows = rows.to(torch.int64).contiguous()
     if out_list.numel() < rows.numel():
         raise ValueError("unique_rows: the list must hold as many ids as `rows`")
-    _lib.check(_lib.load().chaorec_unique_rows(_ptr(rows), rows.numel(), claim.numel(), _ptr(claim), _ptr(stamp_dev),
-                                               _ptr(out_list), _ptr(out_count), _stream()), "chaorec_unique_rows")
+    _lib.load().chaorec_unique_rows(_ptr(rows), rows.numel(), claim.numel(), _ptr(claim), _ptr(stamp_dev),
+                                    _ptr(out_list), _ptr(out_count), _stream())
 
 
 def adam_lowrank_strips(K):
@@ -81,13 +78,12 @@ def adam_lowrank(param, gy, weight, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0
         R = gy.shape[1]
     if not (param.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous()):
         raise ValueError("adam_lowrank: contiguous tables")
-    rc = _lib.load().chaorec_adam_lowrank_f32(_ptr(param), _ptr(gy if mode != 2 else None),
-                                              _ptr(weight if mode <= 1 else None), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                              n, K, R, lr, betas[0], betas[1], eps, weight_decay, int(step),
-                                              _ptr(step_dev), int(mode), _ptr(last), _ptr(bc_table),
-                                              0 if bc_table is None else bc_table.shape[0], _ptr(rl), _ptr(rc_), cap,
-                                              int(bool(rows_given)), _stream())
-    _lib.check(rc, "chaorec_adam_lowrank_f32")
+    _lib.load().chaorec_adam_lowrank_f32(_ptr(param), _ptr(gy if mode != 2 else None),
+                                         _ptr(weight if mode <= 1 else None), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                         n, K, R, lr, betas[0], betas[1], eps, weight_decay, int(step),
+                                         _ptr(step_dev), int(mode), _ptr(last), _ptr(bc_table),
+                                         0 if bc_table is None else bc_table.shape[0], _ptr(rl), _ptr(rc_), cap,
+                                         int(bool(rows_given)), _stream())
 
 
 class _LinearRows(torch.autograd.Function):
@@ -155,12 +151,11 @@ def adam_multi(tensors, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_deca
     for t in tensors:
         _need_cuda(t[0], t[1], t[2], t[3])
     numel = (ctypes.c_int64 * n)(*[int(t[4]) for t in tensors])
-    rc = _lib.load().chaorec_adam_multi_f32(n, arr([t[0].data_ptr() for t in tensors]),
-                                            arr([t[1].data_ptr() for t in tensors]),
-                                            arr([t[2].data_ptr() for t in tensors]),
-                                            arr([t[3].data_ptr() for t in tensors]), numel, lr, betas[0], betas[1], eps,
-                                            weight_decay, int(step), _ptr(step_dev), _stream())
-    _lib.check(rc, "chaorec_adam_multi_f32")
+    _lib.load().chaorec_adam_multi_f32(n, arr([t[0].data_ptr() for t in tensors]),
+                                       arr([t[1].data_ptr() for t in tensors]),
+                                       arr([t[2].data_ptr() for t in tensors]),
+                                       arr([t[3].data_ptr() for t in tensors]), numel, lr, betas[0], betas[1], eps,
+                                       weight_decay, int(step), _ptr(step_dev), _stream())
 
 
 def adam_multi_max():
@@ -199,11 +194,10 @@ def edge_dropout_norm(structure, p, seed, step=0, step_dev=None, salt=0, keep=No
     val_t = torch.empty(nnz, dtype=torch.float32, device=dev)
     if keep is not None:
         keep = keep.to(torch.uint8).contiguous()
-    rc = _lib.load().chaorec_edge_dropout_norm(_ptr(structure.entry_row), _ptr(structure.col),
-                                               _ptr(structure.transpose_entry), nnz, structure.n_rows, float(p),
-                                               int(seed) & (2**64 - 1), int(step), _ptr(step_dev), int(salt),
-                                               _ptr(keep), _ptr(structure.deg_ws), _ptr(val), _ptr(val_t), _stream())
-    _lib.check(rc, "chaorec_edge_dropout_norm")
+    _lib.load().chaorec_edge_dropout_norm(_ptr(structure.entry_row), _ptr(structure.col),
+                                          _ptr(structure.transpose_entry), nnz, structure.n_rows, float(p),
+                                          int(seed) & (2**64 - 1), int(step), _ptr(step_dev), int(salt),
+                                          _ptr(keep), _ptr(structure.deg_ws), _ptr(val), _ptr(val_t), _stream())
     return val, val_t
 
 
@@ -221,8 +215,7 @@ def edge_dot_raw(entry_row, col, a, b, n_entries=None):
     if n < 0 or n > int(col.numel()) or n > int(entry_row.numel()):
         raise ValueError(f"edge_dot: n_entries={n} beyond the {int(col.numel())} stored entries / {int(entry_row.numel())} entry rows")
     out = torch.empty(n, dtype=torch.float32, device=a.device)
-    rc = _lib.load().chaorec_edge_dot_f32(_ptr(entry_row), _ptr(col), _ptr(a), _ptr(b), _ptr(out), n, a.shape[1], _stream())
-    _lib.check(rc, "chaorec_edge_dot_f32")
+    _lib.load().chaorec_edge_dot_f32(_ptr(entry_row), _ptr(col), _ptr(a), _ptr(b), _ptr(out), n, a.shape[1], _stream())
     return out
 
 
@@ -301,12 +294,11 @@ class _NGCFLayer(torch.autograd.Function):
         lib = _lib.load()
         gy = gy.contiguous()
         g = torch.empty_like(gy)
-        _lib.check(lib.chaorec_leaky_bwd_f32(_ptr(y), _ptr(gy), 0.2, _ptr(g), g.numel(), _stream()), "chaorec_leaky_bwd_f32")
+        lib.chaorec_leaky_bwd_f32(_ptr(y), _ptr(gy), 0.2, _ptr(g), g.numel(), _stream())
         gs = gemm_raw(g, w1)
         gt = gemm_raw(g, w2)
         gx = torch.empty_like(x)
-        _lib.check(lib.chaorec_mul_pair_bwd_f32(_ptr(gt), _ptr(s), _ptr(x), _ptr(gs), _ptr(gx), gs.numel(), _stream()),
-                   "chaorec_mul_pair_bwd_f32")
+        lib.chaorec_mul_pair_bwd_f32(_ptr(gt), _ptr(s), _ptr(x), _ptr(gs), _ptr(gx), gs.numel(), _stream())
         gw1 = gemm_raw(g, s, transA=True) if ctx.needs_input_grad[2] else None
         gw2 = gemm_raw(g, t, transA=True) if ctx.needs_input_grad[3] else None
         return gs, gx, gw1, gw2
@@ -329,9 +321,8 @@ def weighted_sample_keep(weights, k, seed, step=0, step_dev=None, return_keys=Fa
     ws = torch.empty(nbytes, dtype=torch.uint8, device=weights.device)
     keep = torch.empty(n, dtype=torch.uint8, device=weights.device)
     keys = torch.empty(n, dtype=torch.int64, device=weights.device) if return_keys else None
-    rc = lib.chaorec_weighted_sample_keep(_ptr(weights), n, int(k), int(seed) & (2**64 - 1), int(step), _ptr(step_dev),
-                                          _ptr(ws), nbytes, _ptr(keep), _ptr(keys), _stream())
-    _lib.check(rc, "chaorec_weighted_sample_keep")
+    lib.chaorec_weighted_sample_keep(_ptr(weights), n, int(k), int(seed) & (2**64 - 1), int(step), _ptr(step_dev),
+                                     _ptr(ws), nbytes, _ptr(keep), _ptr(keys), _stream())
     return (keep, keys) if return_keys else keep
 
 
@@ -347,9 +338,8 @@ def weighted_sample_keys(weights, ids=None, seed=0, step=0, step_dev=None):
         if ids.numel() != n:
             raise ValueError("weighted_sample_keys: ids and weights differ in length")
     keys = torch.empty(n, dtype=torch.int64, device=weights.device)
-    rc = _lib.load().chaorec_weighted_sample_keys(_ptr(weights), _ptr(ids), n, int(seed) & (2**64 - 1), int(step),
-                                                  _ptr(step_dev), _ptr(keys), _stream())
-    _lib.check(rc, "chaorec_weighted_sample_keys")
+    _lib.load().chaorec_weighted_sample_keys(_ptr(weights), _ptr(ids), n, int(seed) & (2**64 - 1), int(step),
+                                             _ptr(step_dev), _ptr(keys), _stream())
     return keys
 
 
@@ -364,9 +354,7 @@ class _RowCosineScale(torch.autograd.Function):
         _need_cuda(y, e)
         y, e = _f32c(y), _f32c(e)
         out = torch.empty_like(y)
-        rc = _lib.load().chaorec_row_cosine_scale_fwd_f32(_ptr(y), _ptr(e), _ptr(out), None, y.shape[0], y.shape[1],
-                                                          _stream())
-        _lib.check(rc, "chaorec_row_cosine_scale_fwd_f32")
+        _lib.load().chaorec_row_cosine_scale_fwd_f32(_ptr(y), _ptr(e), _ptr(out), None, y.shape[0], y.shape[1], _stream())
         ctx.save_for_backward(y, e)
         return out
 
@@ -375,9 +363,8 @@ class _RowCosineScale(torch.autograd.Function):
         y, e = ctx.saved_tensors
         g = g.contiguous()
         gy, ge = torch.empty_like(y), torch.empty_like(e)
-        rc = _lib.load().chaorec_row_cosine_scale_bwd_f32(_ptr(g), _ptr(y), _ptr(e), _ptr(gy), _ptr(ge), y.shape[0],
-                                                          y.shape[1], _stream())
-        _lib.check(rc, "chaorec_row_cosine_scale_bwd_f32")
+        _lib.load().chaorec_row_cosine_scale_bwd_f32(_ptr(g), _ptr(y), _ptr(e), _ptr(gy), _ptr(ge), y.shape[0],
+                                                     y.shape[1], _stream())
         return gy, ge
 
 
@@ -400,8 +387,7 @@ def dgcf_check_shape(D, K, n_layers=1, n_iterations=1):
 def dgcf_softmax(S, P):
     """P = softmax(S) over the K intents of every edge (entry-major [E, K])."""
     _need_cuda(S, P)
-    rc = _lib.load().chaorec_dgcf_softmax_f32(_ptr(S), _ptr(P), S.shape[0], S.shape[1], _stream())
-    _lib.check(rc, "chaorec_dgcf_softmax_f32")
+    _lib.load().chaorec_dgcf_softmax_f32(_ptr(S), _ptr(P), S.shape[0], S.shape[1], _stream())
 
 
 def dgcf_propagate_raw(g, P, x, y=None, z=None, zout=None, rows=None, route_end=0, S=None, P_next=None):
@@ -411,10 +397,9 @@ def dgcf_propagate_raw(g, P, x, y=None, z=None, zout=None, rows=None, route_end=
     x = _f32c(x)
     D, K = x.shape[1], P.shape[1]
     r0, r1 = rows if rows is not None else (0, g.n_rows)
-    rc = _lib.load().chaorec_dgcf_propagate_f32(_ptr(g.rowptr), _ptr(g.col), _ptr(g.val), _ptr(g.eid), _ptr(P), _ptr(x),
-                                                _ptr(y), _ptr(z), _ptr(zout), int(r0), int(r1), int(route_end), D, K,
-                                                _ptr(S), _ptr(P_next), _stream())
-    _lib.check(rc, "chaorec_dgcf_propagate_f32")
+    _lib.load().chaorec_dgcf_propagate_f32(_ptr(g.rowptr), _ptr(g.col), _ptr(g.val), _ptr(g.eid), _ptr(P), _ptr(x),
+                                           _ptr(y), _ptr(z), _ptr(zout), int(r0), int(r1), int(route_end), D, K,
+                                           _ptr(S), _ptr(P_next), _stream())
     return y if y is not None else zout
 
 
@@ -505,8 +490,7 @@ class _DGCFCor(torch.autograd.Function):
         lib = _lib.load()
         ws = torch.empty(lib.chaorec_dgcf_dcor_workspace_bytes(n, D, K), dtype=torch.uint8, device=table.device)
         loss = torch.empty(1, dtype=torch.float32, device=table.device)
-        rc = lib.chaorec_dgcf_dcor_fwd_f32(_ptr(table), _ptr(idx), n, D, K, _ptr(loss), _ptr(ws), ws.numel(), _stream())
-        _lib.check(rc, "chaorec_dgcf_dcor_fwd_f32")
+        lib.chaorec_dgcf_dcor_fwd_f32(_ptr(table), _ptr(idx), n, D, K, _ptr(loss), _ptr(ws), ws.numel(), _stream())
         ctx.save_for_backward(idx)
         ctx.ws, ctx.K, ctx.shape = ws, K, tuple(table.shape)
         return loss
@@ -518,9 +502,8 @@ class _DGCFCor(torch.autograd.Function):
         sorted_idx, perm = torch.sort(idx, stable=True)
         grad_rows = torch.empty((n, D), dtype=torch.float32, device=idx.device)
         grad_table = torch.empty((N, D), dtype=torch.float32, device=idx.device)      # (zeroed by the launch itself)
-        rc = _lib.load().chaorec_dgcf_dcor_bwd_f32(_ptr(sorted_idx), _ptr(perm), n, D, ctx.K, _ptr(g.contiguous()), _ptr(ctx.ws),
-                                                   _ptr(grad_rows), _ptr(grad_table), N, _stream())
-        _lib.check(rc, "chaorec_dgcf_dcor_bwd_f32")
+        _lib.load().chaorec_dgcf_dcor_bwd_f32(_ptr(sorted_idx), _ptr(perm), n, D, ctx.K, _ptr(g.contiguous()), _ptr(ctx.ws),
+                                              _ptr(grad_rows), _ptr(grad_table), N, _stream())
         return grad_table, None, None
 
 

@@ -351,13 +351,13 @@ def test_feature_adam_edge_cases(dev):
     assert torch.equal(p[1], torch.ones(4, device=dev))                      # zero gradient, zero moments: untouched
     # argument checks
     for bad in (dict(K=6), dict(R=65), dict(mode=4)):
-        rc = lib.chaorec_adam_lowrank_f32(p.data_ptr(), gy.data_ptr(), W.data_ptr(), m.data_ptr(), v.data_ptr(), 3,
-                                          bad.get("K", 4), bad.get("R", 1), 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None,
-                                          bad.get("mode", 0), None, None, 0, None, None, 0, 0, None)
-        assert rc != 0, bad
-    rc = lib.chaorec_adam_lowrank_f32(p.data_ptr(), gy.data_ptr(), W.data_ptr(), m.data_ptr(), v.data_ptr(), 3, 4, 1, 1e-3,
-                                      0.9, 0.999, 1e-8, 0.0, 1, None, 1, None, None, 0, None, None, 0, 0, None)
-    assert rc != 0                                                            # lazy mode without `last`
+        with pytest.raises(RuntimeError, match="chaorec_adam_lowrank_f32"):
+            lib.chaorec_adam_lowrank_f32(p.data_ptr(), gy.data_ptr(), W.data_ptr(), m.data_ptr(), v.data_ptr(), 3,
+                                         bad.get("K", 4), bad.get("R", 1), 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, None,
+                                         bad.get("mode", 0), None, None, 0, None, None, 0, 0, None)
+    with pytest.raises(RuntimeError, match="chaorec_adam_lowrank_f32"):       # lazy mode without `last`
+        lib.chaorec_adam_lowrank_f32(p.data_ptr(), gy.data_ptr(), W.data_ptr(), m.data_ptr(), v.data_ptr(), 3, 4, 1, 1e-3,
+                                     0.9, 0.999, 1e-8, 0.0, 1, None, 1, None, None, 0, None, None, 0, 0, None)
     with pytest.raises(ValueError):
         ops.adam_lowrank(p, gy, torch.zeros(1, 8, device=dev), m, v, 1)       # W's width is not the table's
     with pytest.raises(RuntimeError):

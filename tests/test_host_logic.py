@@ -20,15 +20,95 @@ def test_abi_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/chaorec_hip.h but not exported"
-    assert declared == set(_lib.SIGNATURES), "ctypes table and header drifted"
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, args in re.findall(r"\b(chaorec_\w+)\s*\(([^;{]*?)\)\s*;", plain):
-        n_args = 0 if args.strip() in ("", "void") else args.count(",") + 1
-        assert len(_lib.SIGNATURES[name][1]) == n_args, f"{name}: ctypes argtypes vs header"
+    # the binding is derived from the header (_lib.parse_header): the test's own regex must find as many names as it parsed
+    assert len(_lib.SIGNATURES) == len(declared) and set(_lib.SIGNATURES) == declared, "header parser lost or invented a name"
     assert _lib.load().chaorec_abi_version() == _lib.ABI_VERSION == 16
     assert _lib.load().chaorec_spmm_rows_per_wave(64) == 4
     assert _lib.load().chaorec_spmm_rows_per_wave(128) == 2
     assert _lib.load().chaorec_score_topk_workspace_bytes(28940, 15207, 50, 64) > 0
+
+
+_MINI_HEADER = """
+/* a comment with ( and ) and ; in it: int chaorec_not_a_function(int x); */
+#ifndef MINI_H
+#define CHAOREC_ABI_VERSION 7  /* 7: a comment that runs on
+                                  to a second line; with chaorec_also_not(one) */
+#define CHAOREC_E_INVALID (-1)
+extern "C" {
+int chaorec_abi_version(void);
+const char *chaorec_last_error(void);
+size_t chaorec_ws_bytes(int64_t, int32_t n_k);
+/* a prototype over several lines, a pointer to const pointers, parameter names left out */
+int chaorec_many_f32(const float *const *terms, int32_t n_terms, float w,
+                     uint64_t seed,   /* (a comment, with a comma) between parameters */
+                     uint32_t salt, float *, const uint8_t *keep,
+                     void *stream);
+int32_t chaorec_strips ( int32_t K ) ;
+}
+#endif
+"""
+
+
+def test_header_parser_maps_every_prototype():
+    from chaorec_amd._lib import parse_header
+    c = ctypes
+    version, sigs = parse_header(_MINI_HEADER)
+    assert version == 7
+    assert list(sigs) == ["chaorec_abi_version", "chaorec_last_error", "chaorec_ws_bytes", "chaorec_many_f32", "chaorec_strips"]
+    assert sigs["chaorec_abi_version"] == (c.c_int, [])
+    assert sigs["chaorec_last_error"] == (c.c_char_p, [])
+    assert sigs["chaorec_ws_bytes"] == (c.c_size_t, [c.c_int64, c.c_int32])
+    assert sigs["chaorec_many_f32"] == (c.c_int, [c.c_void_p, c.c_int32, c.c_float, c.c_uint64, c.c_uint32, c.c_void_p,
+                                                  c.c_void_p, c.c_void_p])
+    assert sigs["chaorec_strips"] == (c.c_int32, [c.c_int32])
+    assert c.sizeof(sigs["chaorec_many_f32"][1][3]) == 8 and sigs["chaorec_many_f32"][1][3](2**64 - 1).value == 2**64 - 1
+
+
+@pytest.mark.parametrize("decl, names", [
+    ("int chaorec_f(double x);", "double x"),                          # a type outside the map (the header has no double scalar)
+    ("int chaorec_f(unsigned int x);", "unsigned int x"),
+    ("int chaorec_f(int32_t a b);", "int32_t a b"),
+    ("long chaorec_f(void);", "long"),
+    ("int chaorec_f(int32_t cnt[4]);", "int32_t cnt[4]"),              # an array parameter is a pointer: write it as one
+    ("int chaorec_f(void (*done)(void));", "void (*done)(void)"),
+    ("float *chaorec_f(void);", "float *"),                            # a pointer result other than const char *
+    ("int chaorec_f(int32_t x)", "chaorec_f"),                         # no semicolon: runs into the next declaration
+    ("int chaorec_f(int32_t x) { return 0; }", "chaorec_f"),
+    ("static const int k = chaorec_f(3);", "chaorec_f"),               # a chaorec_*( that is no prototype
+    ("int chaorec_f(int32_t x); int chaorec_f(int64_t x);", "chaorec_f"),
+    ("typedef int chaorec_t;", "chaorec_t"),
+])
+def test_header_parser_refuses_what_it_cannot_map(decl, names):
+    from chaorec_amd._lib import parse_header
+    head = "#define CHAOREC_ABI_VERSION 1\nint chaorec_abi_version(void);\n"
+    assert len(parse_header(head + "int chaorec_g(void);")[1]) == 2
+    with pytest.raises(ValueError, match=re.escape(names)):
+        parse_header(head + decl + "\nint chaorec_g(void);")
+    with pytest.raises(ValueError, match="CHAOREC_ABI_VERSION"):
+        parse_header("int chaorec_abi_version(void);")
+
+
+def test_failing_status_raises_with_the_called_functions_name():
+    """A status is checked by the binding, under the name of the export that was called.  Both calls fail their argument
+    checks before any HIP call (csrc/spmm.hip: chaorec_spmm_build_schedule, csrc/bpr.hip: chaorec_bpr_bwd_ordered_f32)."""
+    from chaorec_amd import _lib
+    _lib.build()
+    lib = _lib.load()
+    rowptr, out = torch.tensor([0, 1, 2], dtype=torch.int64), torch.zeros(4, dtype=torch.int32)
+    assert lib.chaorec_spmm_schedule_len(2, 64) > 1
+    with pytest.raises(RuntimeError, match=r"^chaorec_spmm_build_schedule failed \(-3\): build_schedule: out_len 1 < "):
+        lib.chaorec_spmm_build_schedule(rowptr.data_ptr(), None, None, 2, 64, out.data_ptr(), 1)
+    with pytest.raises(RuntimeError, match=r"^chaorec_bpr_bwd_ordered_f32 failed \(-1\): bpr_bwd_ordered: NULL argument$"):
+        lib.chaorec_bpr_bwd_ordered_f32(None, None, None, None, None, 4, 64, None, 0.0, None, None, None, None)
+    # an int that is a value, or a status its caller reads, comes back as it is
+    assert lib.chaorec_dgcf_check_shape(64, 3) == -1 and b"4K" in lib.chaorec_last_error()
+    assert lib.chaorec_dgcf_check_shape(64, 4) == 0
+    # and the unchecked `int` exports are exactly the ones _lib names as such
+    unchecked = {name for name, (res, _) in _lib.SIGNATURES.items() if res is ctypes.c_int and getattr(lib, name).errcheck is None}
+    assert unchecked == _lib.INT_VALUE_EXPORTS == {
+        "chaorec_abi_version", "chaorec_spmm_rows_per_wave", "chaorec_spmm_long_threshold", "chaorec_adam_lowrank_strips",
+        "chaorec_adam_multi_max", "chaorec_dgcf_check_shape"}
+    assert all(getattr(lib, name).errcheck is None for name, (res, _) in _lib.SIGNATURES.items() if res is not ctypes.c_int)
 
 
 def test_no_cpu_fallback():
