@@ -290,6 +290,19 @@ def user_hist_csr_from_edges(edge_index, num_user):
     return torch.from_numpy(rowptr), torch.from_numpy(i.astype(np.int32))
 
 
+def item_major_hist(rowptr, col, num_item):
+    """The user-history CSR (rowptr [U + 1], col local item ids) transposed: -> (item_ptr int64 [I + 1], item_users int32
+    ascending per item, item_pos int32 = the entry's place in its user's row).  CPU tensors."""
+    rowptr, col = rowptr.to(torch.int64), col.to(torch.int64)
+    counts = rowptr[1:] - rowptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int64), counts)
+    pos = torch.arange(col.numel(), dtype=torch.int64) - rowptr[rows]
+    order = torch.sort(col, stable=True)[1]
+    item_ptr = torch.zeros(int(num_item) + 1, dtype=torch.int64)
+    torch.cumsum(torch.bincount(col, minlength=int(num_item)), 0, out=item_ptr[1:])
+    return item_ptr, rows[order].to(torch.int32), pos[order].to(torch.int32)
+
+
 def user_item_dict_from_edges(edge_index):
     """the missing user_item_dict.npy blobs are the train edges grouped by user in
     file order (verified against the shipped dicts by tests/golden/gen_golden.py)."""

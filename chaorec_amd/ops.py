@@ -969,6 +969,8 @@ _MOVED = {
         "spmm_values", "edge_dot_raw", "_EdgeDot", "edge_dot", "_NGCFLayer", "ngcf_layer", "weighted_sample_keep", "weighted_sample_keys",
         "_RowCosineScale", "row_cosine_scale", "dgcf_check_shape", "dgcf_softmax", "dgcf_propagate_raw", "dgcf_p_schedule",
         "dgcf_forward_raw", "_DGCFForward", "dgcf_forward", "_DGCFCor", "dgcf_cor_loss",
+        "MULTVAE_LATENT", "MultVAEStructure", "multvae_tick", "_MultVAEEncode", "multvae_encode", "_MultVAEDecode",
+        "multvae_decode",
     ),
 }
 

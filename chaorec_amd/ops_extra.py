@@ -512,3 +512,155 @@ def dgcf_cor_loss(table, idx, K):
     if int(K) < 2:
         return torch.zeros(1, dtype=torch.float32, device=table.device)
     return _DGCFCor.apply(table, idx, int(K))
+
+
+# --------------------------------------------------------------------------------------------
+# MultVAE (csrc/multvae.hip): history-row encoder, all-items multinomial likelihood without [B, I]
+# --------------------------------------------------------------------------------------------
+MULTVAE_LATENT = 64      # p_dims = [64] (Model/MultVAE.py:38): the width the kernels tile
+
+
+class MultVAEStructure:
+    """What the MultVAE kernels walk: the user-history CSR (rowptr int64 [U + 1], col int32 local item ids, ascending)
+    and its item-major transpose with every entry's place in its user's row (graph.item_major_hist)."""
+
+    def __init__(self, rowptr, col, num_item):
+        from .graph import item_major_hist
+        self.num_user, self.num_item = int(rowptr.numel() - 1), int(num_item)
+        self.rowptr, self.col = rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
+        self.item_ptr, self.item_users, self.item_pos = item_major_hist(self.rowptr.cpu(), self.col.cpu(), self.num_item)
+        self.user_ids = torch.arange(self.num_user + 1, dtype=torch.int64)
+
+    def to(self, device):
+        for k in ("rowptr", "col", "item_ptr", "item_users", "item_pos", "user_ids"):
+            setattr(self, k, getattr(self, k).to(device))
+        return self
+
+    def batch(self, users):
+        """users int64 [B] -> (users, slot_ptr [U + 1], perm [B]): user u sits in samples perm[slot_ptr[u] : slot_ptr[u + 1]],
+        ascending (a stable sort; capturable: no host decision)."""
+        users = users.to(torch.int64).contiguous()
+        sorted_u, perm = torch.sort(users, stable=True)
+        return users, torch.searchsorted(sorted_u, self.user_ids).contiguous(), perm.contiguous()
+
+    def keep_offsets(self, users):
+        """Where each sample's keep flags start when they are GIVEN (sample 0's history row, then sample 1's, ...)."""
+        n = self.rowptr[users + 1] - self.rowptr[users]
+        return (torch.cumsum(n, 0) - n).contiguous()
+
+
+def multvae_tick(state, anneal, cap, total_steps):
+    """state[1] = state[0] (the update_count this step reads), state[0] += 1, anneal[0] = min(cap, state[1] / total)."""
+    _need_cuda(state, anneal)
+    _lib.load().chaorec_multvae_tick(_ptr(state), _ptr(anneal), float(cap), int(total_steps), _stream())
+
+
+def _multvae_sumsq(tensors, out):
+    lib = _lib.load()
+    for k, t in enumerate(tensors):
+        n_partial = max(1, min(1024, t.numel() // 4096))
+        partial = torch.empty(n_partial, dtype=torch.float32, device=t.device)
+        lib.chaorec_multvae_sumsq_f32(_ptr(t), t.numel(), _ptr(partial), n_partial, _ptr(out), 1 if k else 0, _stream())
+
+
+def _dense_f32(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"multvae: {what} must be a contiguous float32 tensor")
+    return t
+
+
+class _MultVAEEncode(torch.autograd.Function):
+    """(Wq_t [I, 128], bq [128]) -> z [B, 64], kl [1], sum ||Wq||^2 + ||bq||^2 [1] (Model/MultVAE.py:75-93, :113-114)."""
+
+    @staticmethod
+    def forward(ctx, Wq_t, bq, s, batch, state, seed, training, keep_prob, keep, keep_off, eps):
+        users, slot_ptr, perm = batch
+        _need_cuda(Wq_t, bq, users, s.rowptr, state, keep, keep_off, eps)
+        Wq_t, bq = _dense_f32(Wq_t, "Wq_t"), _dense_f32(bq, "bq")
+        B, dev = users.numel(), Wq_t.device
+        if Wq_t.shape != (s.num_item, 2 * MULTVAE_LATENT):
+            raise ValueError(f"multvae: Wq_t is {tuple(Wq_t.shape)}, the kernels tile [{s.num_item}, {2 * MULTVAE_LATENT}]")
+        if eps is not None:
+            eps = _dense_f32(eps, "eps")
+            if eps.shape != (B, MULTVAE_LATENT):
+                raise ValueError("multvae: eps must be [B, 64]")
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        h, z, eps_out, klrow, kl, sq = f(B, 2 * MULTVAE_LATENT), f(B, MULTVAE_LATENT), f(B, MULTVAE_LATENT), f(B), f(1), f(1)
+        _lib.load().chaorec_multvae_encode_fwd_f32(_ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(Wq_t), _ptr(bq),
+                                                   _ptr(keep), _ptr(keep_off), _ptr(eps), _ptr(state), int(seed), int(training),
+                                                   float(keep_prob), _ptr(h), _ptr(z), _ptr(eps_out), _ptr(klrow), _ptr(kl),
+                                                   _stream())
+        _multvae_sumsq((Wq_t, bq), sq)
+        ctx.save_for_backward(Wq_t, bq, h, eps_out)
+        ctx.s, ctx.batch, ctx.state, ctx.draw = s, batch, state, (int(seed), int(training), float(keep_prob), keep, keep_off)
+        ctx.mark_non_differentiable(h, eps_out)
+        return z, kl, sq, h, eps_out
+
+    @staticmethod
+    def backward(ctx, gz, gkl, gsq, _gh, _ge):
+        Wq_t, bq, h, eps = ctx.saved_tensors
+        s, (users, slot_ptr, perm) = ctx.s, ctx.batch
+        seed, training, keep_prob, keep, keep_off = ctx.draw
+        B, dev = users.numel(), Wq_t.device
+        n_partial = (B + 63) // 64
+        sdh = torch.empty_like(h)
+        partial = torch.empty((n_partial, 2 * MULTVAE_LATENT), dtype=torch.float32, device=dev)
+        dW, db = torch.empty_like(Wq_t), torch.empty_like(bq)
+        _lib.load().chaorec_multvae_encode_bwd_f32(
+            _ptr(users), B, s.num_user, _ptr(s.rowptr), s.num_item, _ptr(s.item_ptr), _ptr(s.item_users), _ptr(s.item_pos),
+            _ptr(slot_ptr), _ptr(perm), _ptr(Wq_t), _ptr(bq), _ptr(keep), _ptr(keep_off), _ptr(ctx.state), seed, training,
+            keep_prob, _ptr(h), _ptr(eps), _ptr(_f32c(gz)), _ptr(_f32c(gkl)), _ptr(_f32c(gsq)), _ptr(sdh), _ptr(partial),
+            n_partial, _ptr(dW), _ptr(db), _stream())
+        return dW, db, None, None, None, None, None, None, None, None, None
+
+
+def multvae_encode(Wq_t, bq, s, batch, state, seed, training, keep_prob=0.5, keep=None, keep_off=None, eps=None):
+    """-> z [B, 64], kl [1], sum of squares of (Wq_t, bq) [1], h = [mu | logvar] [B, 128], the eps used [B, 64]."""
+    return _MultVAEEncode.apply(Wq_t, bq, s, batch, state, seed, bool(training), keep_prob, keep, keep_off, eps)
+
+
+class _MultVAEDecode(torch.autograd.Function):
+    """(z [B, 64], Wp [I, 64], bp [I]) -> neg_ll [1], sum ||Wp||^2 + ||bp||^2 [1], lse [B] (Model/MultVAE.py:98-105,
+    :155-156), the logits recomputed tile by tile in the forward and in both backward passes."""
+
+    @staticmethod
+    def forward(ctx, z, Wp, bp, s, batch):
+        users, slot_ptr, perm = batch
+        _need_cuda(z, Wp, bp, users)
+        z, Wp, bp = _dense_f32(z, "z"), _dense_f32(Wp, "Wp"), _dense_f32(bp, "bp")
+        B, I, dev = users.numel(), s.num_item, z.device
+        if Wp.shape != (I, MULTVAE_LATENT) or z.shape != (B, MULTVAE_LATENT) or bp.shape != (I,):
+            raise ValueError(f"multvae: decoder shapes z {tuple(z.shape)}, Wp {tuple(Wp.shape)}, bp {tuple(bp.shape)}; "
+                             f"the kernels tile a latent width of {MULTVAE_LATENT}")
+        lib = _lib.load()
+        splits = int(lib.chaorec_multvae_decode_splits(B, I))
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        pm, ps, lse, lse2, cnt, nll, neg_ll, sq = f(splits, B), f(splits, B), f(B), f(2, B), f(B), f(B), f(1), f(1)
+        lib.chaorec_multvae_decode_fwd_f32(_ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(z), _ptr(Wp), _ptr(bp),
+                                           I, _ptr(pm), _ptr(ps), splits, _ptr(lse), _ptr(lse2), _ptr(cnt), _ptr(nll), _ptr(neg_ll),
+                                           _stream())
+        _multvae_sumsq((Wp, bp), sq)
+        ctx.save_for_backward(z, Wp, bp, lse2, cnt)
+        ctx.s, ctx.batch, ctx.splits = s, batch, splits
+        ctx.mark_non_differentiable(lse)
+        return neg_ll, sq, lse
+
+    @staticmethod
+    def backward(ctx, gnll, gsq, _glse):
+        z, Wp, bp, lse2, cnt = ctx.saved_tensors
+        s, (users, slot_ptr, perm) = ctx.s, ctx.batch
+        B, I, dev = users.numel(), s.num_item, z.device
+        dzp = torch.empty((ctx.splits, B, MULTVAE_LATENT), dtype=torch.float32, device=dev)
+        dz, dW, db = torch.empty_like(z), torch.empty_like(Wp), torch.empty_like(bp)
+        _lib.load().chaorec_multvae_decode_bwd_f32(
+            _ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(s.item_ptr), _ptr(s.item_users), _ptr(slot_ptr),
+            _ptr(perm), _ptr(z), _ptr(Wp), _ptr(bp), I, _ptr(lse2), _ptr(cnt), _ptr(_f32c(gnll)), _ptr(_f32c(gsq)), _ptr(dzp),
+            ctx.splits, _ptr(dz), _ptr(dW), _ptr(db), _stream())
+        return dz, dW, db, None, None
+
+
+def multvae_decode(z, Wp, bp, s, batch):
+    """-> neg_ll [1], sum of squares of (Wp, bp) [1], lse [B]."""
+    return _MultVAEDecode.apply(z, Wp, bp, s, batch)

@@ -218,6 +218,13 @@ class FusedAdam(torch.optim.Optimizer):
             self._step_dev = torch.zeros(1, dtype=torch.int32, device=live[0].device)
         for p in live:
             st = self.state[p]
+            if not st and not p.is_contiguous():
+                # a dense parameter in another element order (MultVAE's encoder weight is the transposed view of a
+                # row-major [I, 128] buffer): moments in the SAME order, so the flat update below pairs equal elements
+                st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                if st["exp_avg"].stride() != p.stride():
+                    raise ValueError("FusedAdam: a non-contiguous parameter must be dense (a permuted view of a buffer)")
+                continue
             if not st:
                 run = [q for q in live if not self.state[q] and q.dtype == p.dtype and q.is_contiguous()]
                 run = _adjacent_run(p, run)
@@ -296,7 +303,10 @@ class FusedAdam(torch.optim.Optimizer):
             i = 0
             while i < len(live):
                 p = live[i]
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                if p.is_contiguous():
+                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                else:           # (see _ensure_state: the gradient in the parameter's own element order)
+                    g = p.grad if p.grad.stride() == p.stride() else torch.empty_like(p).copy_(p.grad)
                 st = self.state[p]
                 n, j = p.numel(), i + 1
                 # extend over parameters whose data, gradient and moments all continue where this one ends
@@ -304,7 +314,7 @@ class FusedAdam(torch.optim.Optimizer):
                     q = live[j]
                     gq, sq = q.grad, self.state[q]
                     esz = p.element_size()
-                    if not (q.is_contiguous() and gq.is_contiguous() and q.dtype == p.dtype
+                    if not (p.is_contiguous() and q.is_contiguous() and gq.is_contiguous() and q.dtype == p.dtype
                             and q.data_ptr() == p.data_ptr() + n * esz and gq.data_ptr() == g.data_ptr() + n * esz
                             and sq["exp_avg"].data_ptr() == st["exp_avg"].data_ptr() + n * esz
                             and sq["exp_avg_sq"].data_ptr() == st["exp_avg_sq"].data_ptr() + n * esz):

@@ -887,6 +887,62 @@ int chaorec_dgcf_dcor_bwd_f32(const int64_t *sorted_idx, const int64_t *perm, in
                               const float *grad_out, const void *ws, float *grad_rows, float *grad_table,
                               int64_t n_table_rows, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MultVAE (Model/MultVAE.py) -- csrc/multvae.hip.  Additive to ABI 16: new names only, no existing prototype changed.
+ * Layouts: Wq_t [I, 128] row-major (layers_q.0.weight [128, I] transposed), bq [128], Wp [I, 64], bp [I], z [B, 64],
+ * h = [mu | logvar] [B, 128].  The latent width is 64 (p_dims = [64], :38).  hist = (rowptr int64 [U + 1], col int32 LOCAL
+ * item ids) is the user-history CSR; (item_ptr int64 [I + 1], item_users int32, item_pos int32 = the entry's place in its
+ * user's history row) its item-major transpose; (slot_ptr int64 [U + 1], perm int64 [B]) a stable sort of the batch's users:
+ * user u sits in samples perm[slot_ptr[u] .. slot_ptr[u + 1]).  state int64 [2] = {update_count, the count this step reads}.
+ * Every gradient scale (gnll, gkl, gsq) is a device scalar.  No atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------------------- */
+/* state[1] = state[0]; state[0] += 1; anneal[0] = min(cap, state[1] / total) (:145-148, :162; total <= 0: cap). */
+int chaorec_multvae_tick(int64_t *state, float *anneal, float anneal_cap, int64_t total_anneal_steps, void *stream);
+
+/* out[0] (+)= sum x^2 (torch.norm(p, 2) ** 2 of :127-136), two passes in a fixed order; partial [n_partial <= 4096]. */
+int chaorec_multvae_sumsq_f32(const float *x, int64_t n, float *partial, int64_t n_partial, float *out, int32_t accumulate,
+                              void *stream);
+
+/* q_graph + the reparametrisation (:75-93, :113-114) for the B samples users[b], no [B, I] input:
+ *   h_b = bq + s_b sum_{j : keep_bj} Wq_t[hist(u_b)_j, :],  s_b = 1 / max(sqrt(n_b), 1e-12) (/ keep_prob when training),
+ *   z = mu + eps exp(logvar / 2),  klrow[b] = 0.5 sum(-logvar + exp(logvar) + mu^2 - 1),  kl[0] = mean_b klrow.
+ * keep (uint8, sample 0's row, then sample 1's, ... with keep_off [B] the rows' starts) and eps_in [B, 64] are GIVEN draws;
+ * NULL: the counter RNG (seed, state[1], sample, entry / column).  eps_out [B, 64] = the eps used. */
+int chaorec_multvae_encode_fwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                   const float *Wq_t, const float *bq, const uint8_t *keep, const int64_t *keep_off,
+                                   const float *eps_in, const int64_t *state, uint64_t seed, int32_t training,
+                                   float keep_prob, float *h, float *z, float *eps_out, float *klrow, float *kl,
+                                   void *stream);
+/* Its backward from gz [B, 64], gkl [1] and gsq [1] (the gradient of the loss w.r.t. sum ||p||^2):
+ *   dWq_t[i, :] = sum_{b, keep_bi} s_b dh_b + 2 gsq Wq_t[i, :]  (every row of Wq_t is written),  dbq = sum_b dh_b + 2 gsq bq.
+ * sdh [B, 128] and partial [n_partial >= ceil(B / 64), 128] are scratch. */
+int chaorec_multvae_encode_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, int64_t I,
+                                   const int64_t *item_ptr, const int32_t *item_users, const int32_t *item_pos,
+                                   const int64_t *slot_ptr, const int64_t *perm, const float *Wq_t, const float *bq,
+                                   const uint8_t *keep, const int64_t *keep_off, const int64_t *state, uint64_t seed,
+                                   int32_t training, float keep_prob, const float *h, const float *eps, const float *gz,
+                                   const float *gkl, const float *gsq, float *sdh, float *partial, int64_t n_partial,
+                                   float *dWq_t, float *dbq, void *stream);
+
+/* The item splits of the sample-owned decoder passes (the first dimension of pm / ps / dzp). */
+int64_t chaorec_multvae_decode_splits(int64_t B, int64_t I);
+/* p_graph + log_softmax + the multinomial likelihood (:98-105, :155-156) with no [B, I] buffer:
+ *   lse_b = logsumexp_i (z_b . Wp[i] + bp[i]),  nll_b = n_b lse_b - sum_{i in hist(u_b)} logit_bi,  neg_ll[0] = mean_b nll_b;
+ * cnt [B] = n_b;  lse2 [2, B] = (the row maximum M, log of the sum rescaled by it): the backward forms exp((logit - M) - L),
+ * near values subtracted first as log_softmax does.  pm, ps [splits, B]: scratch. */
+int chaorec_multvae_decode_fwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                   const float *z, const float *Wp, const float *bp, int64_t I, float *pm, float *ps,
+                                   int64_t splits, float *lse, float *lse2, float *cnt, float *nll, float *neg_ll,
+                                   void *stream);
+/* Its backward with P_bi = gnll n_b exp(logit_bi - lse_b) / B and X the multi-hot batch:
+ *   dz = P Wp - gnll X Wp / B,  dWp = P^T z - gnll X^T z / B + 2 gsq Wp,  dbp = sum_b P - gnll sum_b x / B + 2 gsq bp.
+ * dzp [splits, B, 64]: scratch. */
+int chaorec_multvae_decode_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                   const int64_t *item_ptr, const int32_t *item_users, const int64_t *slot_ptr,
+                                   const int64_t *perm, const float *z, const float *Wp, const float *bp, int64_t I,
+                                   const float *lse2, const float *cnt, const float *gnll, const float *gsq, float *dzp,
+                                   int64_t splits, float *dz, float *dWp, float *dbp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
