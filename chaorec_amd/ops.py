@@ -971,6 +971,9 @@ _MOVED = {
         "dgcf_forward_raw", "_DGCFForward", "dgcf_forward", "_DGCFCor", "dgcf_cor_loss",
         "MULTVAE_LATENT", "MultVAEStructure", "multvae_tick", "_MultVAEEncode", "multvae_encode", "_MultVAEDecode",
         "multvae_decode",
+        "MACRID_D", "MACRID_K", "MACRID_H", "MACRID_STAGING_BYTES", "macrid_check_shape", "macrid_tick", "macrid_normal",
+        "_MacridConcept", "macrid_concept", "_MacridEncode", "macrid_encode", "macrid_split", "_MacridMix", "macrid_mix",
+        "macrid_range_users", "macrid_scores", "macrid_topk",
     ),
 }
 

@@ -664,3 +664,217 @@ class _MultVAEDecode(torch.autograd.Function):
 def multvae_decode(z, Wp, bp, s, batch):
     """-> neg_ll [1], sum of squares of (Wp, bp) [1], lse [B]."""
     return _MultVAEDecode.apply(z, Wp, bp, s, batch)
+
+
+# --------------------------------------------------------------------------------------------
+# MacridVAE (csrc/macridvae.hip): per-concept history-row encoder, mixture likelihood without [B, I] / [B, K, I]
+# --------------------------------------------------------------------------------------------
+MACRID_D, MACRID_K, MACRID_H = 64, 10, 600      # dim_E, kfac, hidden width the kernels tile (Model/MacridVAE.py:27-28)
+MACRID_STAGING_BYTES = 512 << 20                # CHAOREC_MACRID_STAGING_BYTES: one ranking range's [users, I] fp32 scores
+
+
+def macrid_check_shape(D, K=MACRID_K, H=MACRID_H):
+    if (int(D), int(K), int(H)) != (MACRID_D, MACRID_K, MACRID_H):
+        raise ValueError(f"MacridVAE: dim_E={D}, kfac={K}, hidden={H}; the kernels tile dim_E={MACRID_D}, kfac={MACRID_K}, "
+                         f"hidden={MACRID_H}")
+
+
+def macrid_tick(state, anneal, cap, total_steps):
+    """state[0] += 1, state[1] = state[0], anneal[0] = min(cap, state[0] / total): incremented BEFORE it is read."""
+    _need_cuda(state, anneal)
+    _lib.load().chaorec_macrid_tick(_ptr(state), _ptr(anneal), float(cap), int(total_steps), _stream())
+
+
+def macrid_normal(shape, state, seed, std, device):
+    """std * N(0, 1) of `shape` from the counter RNG (seed, state[1], element)."""
+    _need_cuda(state)
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    _lib.load().chaorec_macrid_normal_f32(_ptr(out), out.numel(), _ptr(state), int(seed), float(std), _stream())
+    return out
+
+
+def _mc_f32(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"macrid: {what} must be a contiguous float32 tensor")
+    return t
+
+
+class _MacridConcept(torch.autograd.Function):
+    """(item_embedding [I, D], k_embedding [K, D]) -> items [I, D], cates [I, K] (Model/MacridVAE.py:76-77, :86-94)."""
+
+    @staticmethod
+    def forward(ctx, E, Kemb, tau, gumbel, state, seed, training):
+        _need_cuda(E, Kemb, gumbel, state)
+        E, Kemb = _mc_f32(E, "item_embedding"), _mc_f32(Kemb, "k_embedding")
+        I, D = E.shape
+        K = Kemb.shape[0]
+        macrid_check_shape(D, K)
+        if gumbel is not None:
+            gumbel = _mc_f32(gumbel, "gumbel")
+            if gumbel.shape != (I, K):
+                raise ValueError("macrid: gumbel must be [I, K]")
+        items, cates = torch.empty_like(E), torch.empty((I, K), dtype=torch.float32, device=E.device)
+        _lib.load().chaorec_macrid_concept_fwd_f32(_ptr(E), _ptr(Kemb), I, D, K, float(tau), _ptr(gumbel), _ptr(state), int(seed),
+                                                   int(training), _ptr(items), _ptr(cates), _stream())
+        ctx.save_for_backward(E, Kemb, cates)
+        ctx.tau = float(tau)
+        return items, cates
+
+    @staticmethod
+    def backward(ctx, d_items, d_cates):
+        E, Kemb, cates = ctx.saved_tensors
+        I, D = E.shape
+        K = Kemb.shape[0]
+        n_partial = (I + 63) // 64
+        partial = torch.empty((n_partial, K, D), dtype=torch.float32, device=E.device)
+        dE, dK = torch.empty_like(E), torch.empty_like(Kemb)
+        _lib.load().chaorec_macrid_concept_bwd_f32(_ptr(E), _ptr(Kemb), I, D, K, ctx.tau, _ptr(cates), _ptr(_f32c(d_items)),
+                                                   _ptr(_f32c(d_cates)), _ptr(partial), n_partial, _ptr(dE), _ptr(dK), _stream())
+        return dE, dK, None, None, None, None, None
+
+
+def macrid_concept(E, Kemb, tau, state, seed, training, gumbel=None):
+    """-> items = normalize(E) [I, D], cates = softmax(items . normalize(Kemb)^T / tau (+ Gumbel noise in training)) [I, K]."""
+    return _MacridConcept.apply(E, Kemb, tau, gumbel, state, seed, bool(training))
+
+
+class _MacridEncode(torch.autograd.Function):
+    """(W1_t [I, 600], b1 [600], cates [I, K]) -> a [B, K, 600] (Model/MacridVAE.py:82-83, :101-105 up to the first Linear)."""
+
+    @staticmethod
+    def forward(ctx, W1_t, b1, cates, s, batch, state, seed, training, keep_prob, keep, keep_off):
+        users, slot_ptr, perm = batch
+        _need_cuda(W1_t, b1, cates, users, s.rowptr, state, keep, keep_off)
+        W1_t, b1, cates = _mc_f32(W1_t, "W1_t"), _mc_f32(b1, "b1"), _mc_f32(cates, "cates")
+        B, dev, K, H = users.numel(), W1_t.device, cates.shape[1], W1_t.shape[1]
+        macrid_check_shape(MACRID_D, K, H)
+        if W1_t.shape[0] != s.num_item or cates.shape[0] != s.num_item:
+            raise ValueError(f"macrid: W1_t {tuple(W1_t.shape)}, cates {tuple(cates.shape)} for {s.num_item} items")
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        a = torch.empty((B, K, H), dtype=torch.float32, device=dev)
+        srow = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.load().chaorec_macrid_encode_fwd_f32(_ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(W1_t), _ptr(b1),
+                                                  _ptr(cates), K, H, _ptr(keep), _ptr(keep_off), _ptr(state), int(seed), int(training),
+                                                  float(keep_prob), _ptr(a), _ptr(srow), _stream())
+        ctx.save_for_backward(W1_t, cates, srow)
+        ctx.s, ctx.batch, ctx.state, ctx.draw = s, batch, state, (int(seed), int(training), float(keep_prob), keep, keep_off)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        W1_t, cates, srow = ctx.saved_tensors
+        s, (users, slot_ptr, perm) = ctx.s, ctx.batch
+        seed, training, keep_prob, keep, keep_off = ctx.draw
+        B, dev, K, H = users.numel(), W1_t.device, cates.shape[1], W1_t.shape[1]
+        n_partial = (B * K + 63) // 64
+        partial = torch.empty((n_partial, H), dtype=torch.float32, device=dev)
+        dW, db, dc = torch.empty_like(W1_t), torch.empty(H, dtype=torch.float32, device=dev), torch.empty_like(cates)
+        _lib.load().chaorec_macrid_encode_bwd_f32(
+            B, s.num_item, _ptr(s.item_ptr), _ptr(s.item_users), _ptr(s.item_pos), _ptr(slot_ptr), _ptr(perm), _ptr(W1_t), _ptr(cates),
+            K, H, _ptr(keep), _ptr(keep_off), _ptr(ctx.state), seed, training, keep_prob, _ptr(srow), _ptr(_f32c(da)), _ptr(partial),
+            n_partial, _ptr(dW), _ptr(db), _ptr(dc), _stream())
+        return dW, db, dc, None, None, None, None, None, None, None, None
+
+
+def macrid_encode(W1_t, b1, cates, s, batch, state, seed, training, keep_prob=0.5, keep=None, keep_off=None):
+    """-> a [B, K, 600]: b1 + s_b sum over the kept history entries of cates[i, k] W1_t[i, :]."""
+    return _MacridEncode.apply(W1_t, b1, cates, s, batch, state, seed, bool(training), keep_prob, keep, keep_off)
+
+
+class _MacridSplit(torch.autograd.Function):
+    """h [n, 2 D] -> (h[:, :D], h[:, D:]) as contiguous tensors; the backward is one concatenation."""
+
+    @staticmethod
+    def forward(ctx, h):
+        D = h.shape[1] // 2
+        return h[:, :D].contiguous(), h[:, D:].contiguous()
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        return torch.cat((g1, g2), 1)
+
+
+def macrid_split(h):
+    return _MacridSplit.apply(h)
+
+
+class _MacridMix(torch.autograd.Function):
+    """(zh [B, K, D], items [I, D], cates [I, K]) -> ce [1], lse [B] (Model/MacridVAE.py:119-126, :150): the logits
+    recomputed tile by tile in the forward and in both backward passes."""
+
+    @staticmethod
+    def forward(ctx, zh, items, cates, s, batch, tau):
+        users, slot_ptr, perm = batch
+        _need_cuda(zh, items, cates, users)
+        zh, items, cates = _mc_f32(zh, "zh"), _mc_f32(items, "items"), _mc_f32(cates, "cates")
+        B, I, dev = users.numel(), s.num_item, zh.device
+        K, D = cates.shape[1], items.shape[1]
+        macrid_check_shape(D, K)
+        if zh.shape != (B, K, D) or items.shape[0] != I or cates.shape[0] != I:
+            raise ValueError(f"macrid: zh {tuple(zh.shape)}, items {tuple(items.shape)}, cates {tuple(cates.shape)}")
+        lib = _lib.load()
+        splits = int(lib.chaorec_macrid_mix_splits(B, I))
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        ps, lse, coef, nll, ce = f(splits, K, B), f(B), f(B), f(B), f(1)
+        lib.chaorec_macrid_mix_fwd_f32(_ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(zh), _ptr(items), _ptr(cates),
+                                       I, D, K, float(tau), _ptr(ps), splits, _ptr(lse), _ptr(coef), _ptr(nll), _ptr(ce), _stream())
+        ctx.save_for_backward(zh, items, cates, coef)
+        ctx.s, ctx.batch, ctx.splits, ctx.tau = s, batch, splits, float(tau)
+        ctx.mark_non_differentiable(lse)
+        return ce, lse
+
+    @staticmethod
+    def backward(ctx, gce, _glse):
+        zh, items, cates, coef = ctx.saved_tensors
+        s, (users, slot_ptr, perm) = ctx.s, ctx.batch
+        B, I, dev = users.numel(), s.num_item, zh.device
+        K, D = cates.shape[1], items.shape[1]
+        dzp = torch.empty((ctx.splits, B, K, D), dtype=torch.float32, device=dev)
+        dz, di, dc = torch.empty_like(zh), torch.empty_like(items), torch.empty_like(cates)
+        _lib.load().chaorec_macrid_mix_bwd_f32(
+            _ptr(users), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(s.item_ptr), _ptr(s.item_users), _ptr(slot_ptr), _ptr(perm),
+            _ptr(zh), _ptr(items), _ptr(cates), I, D, K, ctx.tau, _ptr(coef), _ptr(_f32c(gce)), _ptr(dzp), ctx.splits, _ptr(dz),
+            _ptr(di), _ptr(dc), _stream())
+        return dz, di, dc, None, None, None
+
+
+def macrid_mix(zh, items, cates, s, batch, tau):
+    """-> ce [1] = mean_b (n_b log sum_i p_bi - sum_{i in hist} log p_bi), lse [B]."""
+    return _MacridMix.apply(zh, items, cates, s, batch, tau)
+
+
+def macrid_range_users(num_item):
+    """How many users one ranking range may stage under the cap."""
+    return max(1, MACRID_STAGING_BYTES // (int(num_item) * 4))
+
+
+def macrid_scores(zh, items, cates, tau, user_begin, hist, mask_value, out=None):
+    """log p_ui of the users user_begin .. user_begin + n (zh [n, K, D]) -> [n, I] fp32, their history entries = mask_value."""
+    _need_cuda(zh, items, cates, hist[0], hist[1])
+    zh, items, cates = _mc_f32(zh, "zh"), _mc_f32(items, "items"), _mc_f32(cates, "cates")
+    n, K, D = zh.shape
+    I = items.shape[0]
+    macrid_check_shape(D, K)
+    if n > macrid_range_users(I):
+        raise ValueError(f"macrid: {n} users x {I} items exceed the staging cap of {MACRID_STAGING_BYTES} bytes; rank in ranges")
+    if hist[0].dtype != torch.int64 or hist[1].dtype != torch.int64:
+        raise ValueError("macrid: the history CSR must be int64")
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.float32, device=zh.device)
+    _lib.load().chaorec_macrid_scores_f32(_ptr(zh), n, _ptr(items), _ptr(cates), I, D, K, float(tau), int(user_begin), _ptr(hist[0]),
+                                          _ptr(hist[1]), float(mask_value), _ptr(out), out.numel() * 4, _stream())
+    return out
+
+
+def macrid_topk(scores, topk, id_offset=0):
+    """Exact top-k per row of scores [n, I], ties to the lowest index -> (int64 [n, topk] ids + id_offset, fp32 [n, topk])."""
+    _need_cuda(scores)
+    scores = _mc_f32(scores, "scores")
+    n, I = scores.shape
+    if not 1 <= int(topk) <= min(64, I):
+        raise ValueError(f"macrid: topk={topk} (1 .. min(64, I={I}))")
+    idx = torch.empty((n, int(topk)), dtype=torch.int64, device=scores.device)
+    val = torch.empty((n, int(topk)), dtype=torch.float32, device=scores.device)
+    _lib.load().chaorec_macrid_topk_f32(_ptr(scores), n, I, int(topk), int(id_offset), _ptr(idx), _ptr(val), _stream())
+    return idx, val

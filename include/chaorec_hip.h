@@ -943,6 +943,83 @@ int chaorec_multvae_decode_bwd_f32(const int64_t *users, int64_t B, int64_t U, c
                                    const float *lse2, const float *cnt, const float *gnll, const float *gsq, float *dzp,
                                    int64_t splits, float *dz, float *dWp, float *dbp, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MacridVAE (Model/MacridVAE.py) -- csrc/macridvae.hip.  Additive to ABI 16: new names only.
+ * D = dim_E = 64, K = kfac = 10, H = 600 are what the kernels tile (any other value: CHAOREC_E_INVALID).  Layouts:
+ * item_emb [I, D], k_emb [K, D], items [I, D] (normalised rows), cates [I, K], W1_t [I, H] row-major (encoder.0.weight
+ * [H, I] transposed), a [B, K, H], zh [B, K, D] (the normalised z of every (sample, concept)).  hist, the item-major
+ * transpose, (slot_ptr, perm) and the keep / keep_off flags: as for MultVAE above.  state int64 [2] = {update, the count
+ * the step's draws are keyed by}.  No [B, I] or [B, K, I] buffer, no atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------------------- */
+/* The largest [users, I] fp32 staging one chaorec_macrid_scores_f32 call may fill: the caller ranks users in ranges. */
+#define CHAOREC_MACRID_STAGING_BYTES 536870912
+/* CHAOREC_OK if the kernels tile (D, K, H). */
+int chaorec_macrid_check_shape(int32_t D, int32_t K, int32_t H);
+/* state[0] += 1; state[1] = state[0]; anneal[0] = min(cap, state[0] / total): incremented BEFORE it is read (:135-137). */
+int chaorec_macrid_tick(int64_t *state, float *anneal, float anneal_cap, int64_t total_anneal_steps, void *stream);
+/* out[e] = std * N(0, 1), e < n, from the counter RNG (seed, state[1], e): reparameterize's epsilon (:69). */
+int chaorec_macrid_normal_f32(float *out, int64_t n, const int64_t *state, uint64_t seed, float std, void *stream);
+
+/* Concept weights (:76-77, :86-94) in one pass over the item rows: items = normalize(item_emb),
+ * cates = softmax(items . normalize(k_emb)^T / tau + g), g = the GIVEN Gumbel noise [I, K] or, NULL, -log(Exp(1)) from the
+ * counter RNG (seed, state[1], item, k); training == 0: no noise. */
+int chaorec_macrid_concept_fwd_f32(const float *item_emb, const float *k_emb, int64_t I, int32_t D, int32_t K, float tau,
+                                   const float *gumbel, const int64_t *state, uint64_t seed, int32_t training, float *items,
+                                   float *cates, void *stream);
+/* Its backward from d_items [I, D] and d_cates [I, K]: d_item_emb [I, D], d_k_emb [K, D] (a fixed-order sum over items
+ * through partial [n_partial >= ceil(I / 64), K, D]). */
+int chaorec_macrid_concept_bwd_f32(const float *item_emb, const float *k_emb, int64_t I, int32_t D, int32_t K, float tau,
+                                   const float *cates, const float *d_items, const float *d_cates, float *partial,
+                                   int64_t n_partial, float *d_item_emb, float *d_k_emb, void *stream);
+
+/* The encoder's first layer for all K concepts (:82-83, :101-105), no [B, I] input:
+ *   a[b, k, :] = b1 + s_b sum_{j : keep_bj} cates[hist(u_b)_j, k] W1_t[hist(u_b)_j, :],  s_b = 1 / max(sqrt(n_b), 1e-12)
+ * (/ keep_prob when training); a row of W1_t is read once per (sample, entry).  srow [B] = s_b.  keep / keep_off: GIVEN
+ * flags; NULL: the counter RNG (seed, state[1], sample, entry).  Evaluation: training = 0, users = a range. */
+int chaorec_macrid_encode_fwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                  const float *W1_t, const float *b1, const float *cates, int32_t K, int32_t H,
+                                  const uint8_t *keep, const int64_t *keep_off, const int64_t *state, uint64_t seed,
+                                  int32_t training, float keep_prob, float *a, float *srow, void *stream);
+/* Its backward from da [B, K, H]:  dW1_t[i, :] = sum_{b, keep_bi} s_b sum_k cates[i, k] da_bk (every row is written),
+ * d_cates[i, k] = sum_{b, keep_bi} s_b W1_t[i, :] . da_bk,  db1 = sum_{b, k} da_bk through partial
+ * [n_partial >= ceil(B K / 64), H]. */
+int chaorec_macrid_encode_bwd_f32(int64_t B, int64_t I, const int64_t *item_ptr, const int32_t *item_users,
+                                  const int32_t *item_pos, const int64_t *slot_ptr, const int64_t *perm, const float *W1_t,
+                                  const float *cates, int32_t K, int32_t H, const uint8_t *keep, const int64_t *keep_off,
+                                  const int64_t *state, uint64_t seed, int32_t training, float keep_prob, const float *srow,
+                                  const float *da, float *partial, int64_t n_partial, float *dW1_t, float *db1, float *d_cates,
+                                  void *stream);
+
+/* The item splits of the sample-owned likelihood passes (the first dimension of ps / dzp). */
+int64_t chaorec_macrid_mix_splits(int64_t B, int64_t I);
+/* The mixture likelihood (:119-126, :150) with p_bi = sum_k cates[i, k] exp(zh_bk . items_i / tau):
+ *   lse_b = log sum_i p_bi,  nll_b = n_b lse_b - sum_{i in hist(u_b)} log p_bi,  ce[0] = mean_b nll_b;
+ * coef [B] = n_b / (B sum_i p_bi) is what the backward reads.  |logit| <= 1 / tau, so no running maximum is kept.
+ * ps [splits, K, B]: scratch. */
+int chaorec_macrid_mix_fwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                               const float *zh, const float *items, const float *cates, int64_t I, int32_t D, int32_t K,
+                               float tau, float *ps, int64_t splits, float *lse, float *coef, float *nll, float *ce,
+                               void *stream);
+/* Its backward, gce [1] = d loss / d ce, w_bi = gce (n_b p_bi / sum_i p_bi - x_bi) / B, r_bik = exp(l_bik) / p_bi:
+ *   d_zh_bk = sum_i w_bi cates_ik r_bik items_i / tau,  d_items_i = sum_{b,k} w_bi cates_ik r_bik zh_bk / tau,
+ *   d_cates_ik = sum_b w_bi r_bik.   dzp [splits, B, K, D]: scratch. */
+int chaorec_macrid_mix_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                               const int64_t *item_ptr, const int32_t *item_users, const int64_t *slot_ptr,
+                               const int64_t *perm, const float *zh, const float *items, const float *cates, int64_t I,
+                               int32_t D, int32_t K, float tau, const float *coef, const float *gce, float *dzp,
+                               int64_t splits, float *d_zh, float *d_items, float *d_cates, void *stream);
+
+/* gene_ranklist's scores (:176-182) for the users user_begin .. user_begin + n_users: scores[u - user_begin, i] =
+ * log p_ui, history entries (hist_rowptr int64 [U + 1], hist_col int64 LOCAL item ids) = mask_value.  n_users I 4 bytes
+ * must not exceed CHAOREC_MACRID_STAGING_BYTES: the [U, I] matrix never exists whole. */
+int chaorec_macrid_scores_f32(const float *zh, int64_t n_users, const float *items, const float *cates, int64_t I, int32_t D,
+                              int32_t K, float tau, int64_t user_begin, const int64_t *hist_rowptr, const int64_t *hist_col,
+                              float mask_value, float *scores, size_t scores_bytes, void *stream);
+/* Exact top-k of every row of scores [n_rows, I] (1 <= topk <= 64, topk <= I), ties to the lowest index (torch.topk's
+ * values, :185): idx [n_rows, topk] = column + id_offset, val [n_rows, topk]. */
+int chaorec_macrid_topk_f32(const float *scores, int64_t n_rows, int64_t I, int32_t topk, int64_t id_offset, int64_t *idx,
+                            float *val, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
