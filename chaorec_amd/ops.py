@@ -974,6 +974,9 @@ _MOVED = {
         "MACRID_D", "MACRID_K", "MACRID_H", "MACRID_STAGING_BYTES", "macrid_check_shape", "macrid_tick", "macrid_normal",
         "_MacridConcept", "macrid_concept", "_MacridEncode", "macrid_encode", "macrid_split", "_MacridMix", "macrid_mix",
         "macrid_range_users", "macrid_scores", "macrid_topk",
+        "DUALVAE_K", "DUALVAE_A", "DUALVAE_H", "DUALVAE_STAGING_BYTES", "dualvae_check_shape", "dualvae_tick", "_DualVAEEncode",
+        "dualvae_encode", "_DualVAEDense", "dualvae_dense", "dualvae_writeback", "dualvae_range_users", "dualvae_scores",
+        "_DualVAELinear", "dualvae_linear", "_DualVAELoss", "dualvae_loss",
     ),
 }
 

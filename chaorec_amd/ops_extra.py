@@ -878,3 +878,211 @@ def macrid_topk(scores, topk, id_offset=0):
     val = torch.empty((n, int(topk)), dtype=torch.float32, device=scores.device)
     _lib.load().chaorec_macrid_topk_f32(_ptr(scores), n, I, int(topk), int(id_offset), _ptr(idx), _ptr(val), _stream())
     return idx, val
+
+
+# --------------------------------------------------------------------------------------------
+# DualVAE (csrc/dualvae.hip): two-sided aspect encoder, Poisson likelihood and neighbourhood term without [B, U] / [B, I]
+# --------------------------------------------------------------------------------------------
+DUALVAE_K, DUALVAE_A, DUALVAE_H = 25, 5, 20     # latent width, aspects, hidden width the kernels tile (Model/DualVAE.py:37-49)
+DUALVAE_STAGING_BYTES = 512 << 20               # CHAOREC_DUALVAE_STAGING_BYTES: one ranking range's [users, I] fp32 scores
+
+
+def dualvae_check_shape(k, a=DUALVAE_A, hidden=DUALVAE_H):
+    if (int(k), int(a), int(hidden)) != (DUALVAE_K, DUALVAE_A, DUALVAE_H):
+        raise ValueError(f"DualVAE: k={k}, a={a}, hidden={hidden}; the kernels tile k={DUALVAE_K}, a={DUALVAE_A}, "
+                         f"hidden={DUALVAE_H}")
+
+
+def dualvae_tick(state):
+    """state[0] += 1, state[1] = state[0]: the step counter the device-drawn epsilon is keyed by."""
+    _need_cuda(state)
+    _lib.load().chaorec_dualvae_tick(_ptr(state), _stream())
+
+
+def _dv_f32(t, what, shape=None):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"dualvae: {what} must be a contiguous float32 tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"dualvae: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+class _DualVAEEncode(torch.autograd.Function):
+    """(We_t [N, 20], bias [20], w [N, 5]) -> pre [B, 5, 20] = bias + sum over the sample's row of w[n, a] We_t[n, :]."""
+
+    @staticmethod
+    def forward(ctx, We_t, bias, w, s, batch):
+        ids, slot_ptr, perm = batch
+        _need_cuda(We_t, bias, w, ids, s.rowptr)
+        N = s.num_item
+        We_t, bias, w = _dv_f32(We_t, "We_t", (N, DUALVAE_H)), _dv_f32(bias, "bias", (DUALVAE_H,)), _dv_f32(w, "w", (N, DUALVAE_A))
+        B = ids.numel()
+        pre = torch.empty((B, DUALVAE_A, DUALVAE_H), dtype=torch.float32, device=We_t.device)
+        _lib.load().chaorec_dualvae_encode_fwd_f32(_ptr(ids), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), N, _ptr(We_t), _ptr(bias),
+                                                   _ptr(w), _ptr(pre), _stream())
+        ctx.save_for_backward(We_t, w)
+        ctx.s, ctx.batch = s, batch
+        return pre
+
+    @staticmethod
+    def backward(ctx, dpre):
+        We_t, w = ctx.saved_tensors
+        s, (ids, slot_ptr, perm) = ctx.s, ctx.batch
+        B, N = ids.numel(), s.num_item
+        dpre = _f32c(dpre)
+        dW, dw = torch.empty_like(We_t), torch.empty_like(w)
+        _lib.load().chaorec_dualvae_encode_bwd_f32(B, N, _ptr(s.item_ptr), _ptr(s.item_users), _ptr(slot_ptr), _ptr(perm), _ptr(We_t),
+                                                   _ptr(w), _ptr(dpre), _ptr(dW), _ptr(dw), _stream())
+        db = col_sum(dpre.view(B * DUALVAE_A, DUALVAE_H))      # (a fixed-order sum over the B * 5 rows)
+        return dW, db, dw, None, None
+
+
+def dualvae_encode(We_t, bias, w, s, batch):
+    """-> pre [B, 5, 20]; s: the MultVAEStructure of the SAMPLE side (rows = samples, columns = table rows)."""
+    return _DualVAEEncode.apply(We_t, bias, w, s, batch)
+
+
+class _DualVAEDense(torch.autograd.Function):
+    """(z [B, 5, 25], zh [B, 5, 20], th [N, 5, 20], w [N, 5]; table [N, 5, 25] without gradient) -> sum_p [B], xlog [B],
+    nei [B, 5, 25]: the tiles s_bna recomputed in the forward and in both backward passes."""
+
+    @staticmethod
+    def forward(ctx, z, zh, th, w, table, s, batch):
+        ids, slot_ptr, perm = batch
+        _need_cuda(z, zh, th, w, table, ids)
+        B, N, dev = ids.numel(), s.num_item, z.device
+        z, zh = _dv_f32(z, "z", (B, DUALVAE_A, DUALVAE_K)), _dv_f32(zh, "zh", (B, DUALVAE_A, DUALVAE_H))
+        th, w = _dv_f32(th, "th", (N, DUALVAE_A, DUALVAE_H)), _dv_f32(w, "w", (N, DUALVAE_A))
+        table = _dv_f32(table, "table", (N, DUALVAE_A, DUALVAE_K))
+        lib = _lib.load()
+        splits = int(lib.chaorec_dualvae_splits(B, N))
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        psum, pnei = f(splits, DUALVAE_A, B), f(splits, B, DUALVAE_A, DUALVAE_K)
+        sum_p, xlog, nei = f(B), f(B), f(B, DUALVAE_A, DUALVAE_K)
+        lib.chaorec_dualvae_dense_fwd_f32(_ptr(ids), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(z), _ptr(zh), _ptr(table), _ptr(th),
+                                          _ptr(w), N, _ptr(psum), _ptr(pnei), splits, _ptr(sum_p), _ptr(xlog), _ptr(nei), _stream())
+        ctx.save_for_backward(z, zh, th, w, table)
+        ctx.s, ctx.batch, ctx.splits = s, batch, splits
+        return sum_p, xlog, nei
+
+    @staticmethod
+    def backward(ctx, g1, g2, gN):
+        z, zh, th, w, table = ctx.saved_tensors
+        s, (ids, slot_ptr, perm) = ctx.s, ctx.batch
+        B, N, dev = ids.numel(), s.num_item, z.device
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        dzp, dzhp = f(ctx.splits, B, DUALVAE_A, DUALVAE_K), f(ctx.splits, B, DUALVAE_A, DUALVAE_H)
+        dz, dzh, dth, dw = torch.empty_like(z), torch.empty_like(zh), torch.empty_like(th), torch.empty_like(w)
+        _lib.load().chaorec_dualvae_dense_bwd_f32(
+            _ptr(ids), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), _ptr(s.item_ptr), _ptr(s.item_users), _ptr(slot_ptr), _ptr(perm),
+            _ptr(z), _ptr(zh), _ptr(table), _ptr(th), _ptr(w), N, _ptr(_f32c(g1)), _ptr(_f32c(g2)), _ptr(_f32c(gN)), _ptr(dzp),
+            _ptr(dzhp), ctx.splits, _ptr(dz), _ptr(dzh), _ptr(dth), _ptr(dw), _stream())
+        return dz, dzh, dth, dw, None, None, None
+
+
+def dualvae_dense(z, zh, th, w, table, s, batch):
+    """-> sum_p [B] = sum_n p_bn, xlog [B] = sum_{n in row(b)} log(p_bn + 1e-10), nei [B, 5, 25].  `table` must stay as it
+    is until the backward has run (the caller passes a snapshot where the table is written in between)."""
+    return _DualVAEDense.apply(z, zh, th, w, table, s, batch)
+
+
+def dualvae_writeback(batch, num_rows, z, mu, table, mu_table):
+    """table[ids] = z, mu_table[ids] = mu in place; where an id repeats in the batch the highest position wins."""
+    ids, slot_ptr, perm = batch
+    _need_cuda(ids, z, mu, table, mu_table)
+    B = ids.numel()
+    z, mu = _dv_f32(z, "z", (B, DUALVAE_A, DUALVAE_K)), _dv_f32(mu, "mu", (B, DUALVAE_A, DUALVAE_K))
+    _dv_f32(table, "table", (num_rows, DUALVAE_A, DUALVAE_K))
+    _dv_f32(mu_table, "mu_table", (num_rows, DUALVAE_A, DUALVAE_K))
+    _lib.load().chaorec_dualvae_writeback_f32(_ptr(ids), B, int(num_rows), _ptr(slot_ptr), _ptr(perm), _ptr(z), _ptr(mu), _ptr(table),
+                                              _ptr(mu_table), _stream())
+
+
+def dualvae_range_users(num_item):
+    """How many users one ranking range may stage under the cap."""
+    return max(1, DUALVAE_STAGING_BYTES // (int(num_item) * 4))
+
+
+def dualvae_scores(z, zh, table, th, w, user_begin, hist, mask_value, out=None):
+    """sum_a w[i, a] sigmoid(z_ua . table_ia + tanh(zh_ua . th_ia)) of the users user_begin .. user_begin + n -> [n, I] fp32,
+    their history entries = mask_value."""
+    _need_cuda(z, zh, table, th, w, hist[0], hist[1])
+    n, I = z.shape[0], table.shape[0]
+    z, zh = _dv_f32(z, "z", (n, DUALVAE_A, DUALVAE_K)), _dv_f32(zh, "zh", (n, DUALVAE_A, DUALVAE_H))
+    table, th = _dv_f32(table, "table", (I, DUALVAE_A, DUALVAE_K)), _dv_f32(th, "th", (I, DUALVAE_A, DUALVAE_H))
+    w = _dv_f32(w, "w", (I, DUALVAE_A))
+    if n > dualvae_range_users(I):
+        raise ValueError(f"dualvae: {n} users x {I} items exceed the staging cap of {DUALVAE_STAGING_BYTES} bytes; rank in ranges")
+    if hist[0].dtype != torch.int64 or hist[1].dtype != torch.int64:
+        raise ValueError("dualvae: the history CSR must be int64")
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.float32, device=z.device)
+    _lib.load().chaorec_dualvae_scores_f32(_ptr(z), _ptr(zh), n, _ptr(table), _ptr(th), _ptr(w), I, int(user_begin), _ptr(hist[0]),
+                                           _ptr(hist[1]), float(mask_value), _ptr(out), out.numel() * 4, _stream())
+    return out
+
+
+class _DualVAELinear(torch.autograd.Function):
+    """y = x W^T + b for the small Linears (W [M, N], M <= 32, N <= 31): the forward and the input gradient are the f32
+    GEMM's, the weight and bias gradients are summed in double over the rows and rounded once."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _need_cuda(x, weight, bias)
+        x = _f32c(x)
+        y = gemm_raw(x, weight, transB=True, bias=bias)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gy = _f32c(gy)
+        R, (M, N) = x.shape[0], weight.shape
+        lib = _lib.load()
+        nbytes = lib.chaorec_dualvae_linear_bwd_workspace_bytes(R, M)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        gw, gb = torch.empty_like(weight), torch.empty(M, dtype=torch.float32, device=x.device)
+        lib.chaorec_dualvae_linear_bwd_f32(_ptr(gy), _ptr(x), R, M, N, _ptr(gw), _ptr(gb), _ptr(ws), nbytes, _stream())
+        gx = gemm_raw(gy, weight) if ctx.needs_input_grad[0] else None
+        return gx, gw, gb
+
+
+def dualvae_linear(x, weight, bias):
+    """nn.Linear for x [R, N] and a small weight [M, N] (see _DualVAELinear)."""
+    return _DualVAELinear.apply(x, weight.contiguous(), bias)
+
+
+class _DualVAELoss(torch.autograd.Function):
+    """(mu, std_pre [B * 5, 25], xlog [B], sum_p [B], cl []) -> [3] = (kl_weight kl - ll + ssl_reg cl, kl, ll) from double sums,
+    each rounded once; std = sigmoid(std_pre), the KL's elements are evaluated in double.  The gradient of element 0 only."""
+
+    @staticmethod
+    def forward(ctx, mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg):
+        _need_cuda(mu, std_pre, xlog, sum_p, cl)
+        mu, std_pre, xlog, sum_p, cl = _f32c(mu), _f32c(std_pre), _f32c(xlog), _f32c(sum_p), _f32c(cl)
+        B = xlog.numel()
+        if mu.shape != std_pre.shape or mu.numel() != B * DUALVAE_A * DUALVAE_K or sum_p.numel() != B:
+            raise ValueError(f"dualvae: mu {tuple(mu.shape)}, std_pre {tuple(std_pre.shape)} for {B} samples")
+        out = torch.empty(3, dtype=torch.float32, device=xlog.device)
+        ws = torch.empty(64, dtype=torch.float64, device=xlog.device)
+        _lib.load().chaorec_dualvae_loss_f32(_ptr(mu), _ptr(std_pre), mu.numel(), _ptr(xlog), _ptr(sum_p), B, _ptr(cl), float(kl_weight),
+                                             float(ssl_reg), _ptr(out), _ptr(ws), ws.numel() * 8, _stream())
+        ctx.save_for_backward(mu, std_pre)
+        ctx.B, ctx.c = B, (float(kl_weight), float(ssl_reg))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mu, std_pre = ctx.saved_tensors
+        g0 = g[0]
+        gB = (g0 / ctx.B).expand(ctx.B)
+        gk = g0 * (ctx.c[0] / (DUALVAE_A * ctx.B))
+        std = torch.sigmoid(std_pre)
+        # d/d mu = mu;  d/d std_pre of -0.5 (2 log std - std^2) = -(1 - std)(1 - std^2)
+        return gk * mu, gk * ((std - 1.0) * (1.0 - std * std)), -gB, gB, g0 * ctx.c[1], None, None
+
+
+def dualvae_loss(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg):
+    """-> [3]: one side's loss (Model/DualVAE.py:274), kl and ll."""
+    return _DualVAELoss.apply(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg)

@@ -1020,6 +1020,68 @@ int chaorec_macrid_scores_f32(const float *zh, int64_t n_users, const float *ite
 int chaorec_macrid_topk_f32(const float *scores, int64_t n_rows, int64_t I, int32_t topk, int64_t id_offset, int64_t *idx,
                             float *val, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * DualVAE (Model/DualVAE.py) -- csrc/dualvae.hip.  Additive to ABI 16: new names only.
+ * k = 25, a = 5, hidden = 20 are what the kernels tile.  One family serves both sides: a SAMPLE is a batch row (ids [B],
+ * each in [0, S)), the TABLE is the other side's table [N, 5, 25] (theta or beta).  (rowptr int64 [S + 1], col int32) is
+ * the samples' CSR over table rows, (tptr int64 [N + 1], tcol int32) its transpose, (slot_ptr [S + 1], perm [B]) the
+ * batch's stable sort as for MultVAE above.  Layouts: z [B, 5, 25], zh = tanh(decoder(z)) [B, 5, 20],
+ * th = tanh(decoder(table)) [N, 5, 20], w [N, 5] the aspect weights, We_t [N, 20] the encoder's first weight row-major
+ * per table row.  s_bna = sigmoid(z_ba . T_na + tanh(zh_ba . th_na)), p_bn = sum_a w_na s_bna.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* The largest [users, I] fp32 staging one chaorec_dualvae_scores_f32 call may fill: the caller ranks users in ranges. */
+#define CHAOREC_DUALVAE_STAGING_BYTES 536870912
+/* CHAOREC_OK if the kernels tile (k, a, hidden). */
+int chaorec_dualvae_check_shape(int32_t k, int32_t a, int32_t hidden);
+/* state[0] += 1; state[1] = state[0]: the step counter the device-drawn epsilon is keyed by. */
+int chaorec_dualvae_tick(int64_t *state, void *stream);
+/* pre[b, a, :] = bias + sum_{n in row(ids[b])} w[n, a] We_t[n, :]  -> [B, 5, 20] (:195, :236 up to the first Linear). */
+int chaorec_dualvae_encode_fwd_f32(const int64_t *ids, int64_t B, int64_t S, const int64_t *rowptr, const int32_t *col, int64_t N,
+                                   const float *We_t, const float *bias, const float *w, float *pre, void *stream);
+/* Its backward from dpre [B, 5, 20]: dWe_t [N, 20] and the sparse part of dw [N, 5], one owner per table row (every row
+ * is written). */
+int chaorec_dualvae_encode_bwd_f32(int64_t B, int64_t N, const int64_t *tptr, const int32_t *tcol, const int64_t *slot_ptr,
+                                   const int64_t *perm, const float *We_t, const float *w, const float *dpre, float *dWe_t,
+                                   float *dw, void *stream);
+/* How many table splits the dense passes use for (B, N): psum is [splits, 5, B], pnei / dzp [splits, B, 5, 25], dzhp
+ * [splits, B, 5, 20]. */
+int64_t chaorec_dualvae_splits(int64_t B, int64_t N);
+/* sum_p[b] = sum_n p_bn, xlog[b] = sum_{n in row(b)} log(p_bn + 1e-10), nei[b, a, :] = sum_n w_na s_bna T_na; no [B, N]
+ * buffer: the tiles are recomputed on the f32 MFMA pipe, the splits added in ascending order. */
+int chaorec_dualvae_dense_fwd_f32(const int64_t *ids, int64_t B, int64_t S, const int64_t *rowptr, const int32_t *col,
+                                  const float *z, const float *zh, const float *table, const float *th, const float *w, int64_t N,
+                                  float *psum, float *pnei, int64_t splits, float *sum_p, float *xlog, float *nei, void *stream);
+/* Its backward from g1 [B] = d / d sum_p, g2 [B] = d / d xlog, gN [B, 5, 25] = d / d nei: dz [B, 5, 25], dzh [B, 5, 20],
+ * dth [N, 5, 20], dw [N, 5] (the table itself carries no gradient). */
+int chaorec_dualvae_dense_bwd_f32(const int64_t *ids, int64_t B, int64_t S, const int64_t *rowptr, const int32_t *col,
+                                  const int64_t *tptr, const int32_t *tcol, const int64_t *slot_ptr, const int64_t *perm,
+                                  const float *z, const float *zh, const float *table, const float *th, const float *w, int64_t N,
+                                  const float *g1, const float *g2, const float *gN, float *dzp, float *dzhp, int64_t splits,
+                                  float *dz, float *dzh, float *dth, float *dw, void *stream);
+/* The small Linears' backward over R rows (gy [R, M], x [R, N], M <= 32, N <= 31): gw [M, N] = gy^T x, gb [M] = column sums
+ * of gy, accumulated in double (the products are exact) and rounded once.  workspace: 8-byte aligned,
+ * chaorec_dualvae_linear_bwd_workspace_bytes(R, M). */
+size_t chaorec_dualvae_linear_bwd_workspace_bytes(int64_t R, int32_t M);
+int chaorec_dualvae_linear_bwd_f32(const float *gy, const float *x, int64_t R, int32_t M, int32_t N, float *gw, float *gb,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+/* One side's scalars from double sums, each rounded once: out[0] = kl_weight kl - ll + ssl_reg cl[0] (:274),
+ * out[1] = kl = sum over the n_kl = B 5 25 elements of -0.5 (1 + 2 log std - mu^2 - std^2) / (5 B) with std = sigmoid(std_pre)
+ * evaluated in double (:197-198, :216), out[2] = ll = (sum xlog - sum sum_p) / B.  workspace: 8-byte aligned, >= 512 bytes. */
+int chaorec_dualvae_loss_f32(const float *mu, const float *std_pre, int64_t n_kl, const float *xlog, const float *sum_p, int64_t B,
+                             const float *cl, float kl_weight, float ssl_reg, float *out, void *workspace, size_t workspace_bytes,
+                             void *stream);
+/* table[ids[b]] = z[b], mu_table[ids[b]] = mu[b] (:289-290, :300-301); where an id repeats, the highest batch position
+ * wins. */
+int chaorec_dualvae_writeback_f32(const int64_t *ids, int64_t B, int64_t S, const int64_t *slot_ptr, const int64_t *perm,
+                                  const float *z, const float *mu, float *table, float *mu_table, void *stream);
+/* gene_ranklist's scores (:314-327) for the users user_begin .. user_begin + n_users (z [n_users, 5, 25] their mu_theta
+ * rows, zh their decoded rows): scores[u - user_begin, i] = sum_a w[i, a] s_uia with w AS GIVEN, history entries
+ * (hist_rowptr int64 [U + 1], hist_col int64 LOCAL item ids) = mask_value.  n_users I 4 bytes must not exceed
+ * CHAOREC_DUALVAE_STAGING_BYTES. */
+int chaorec_dualvae_scores_f32(const float *z, const float *zh, int64_t n_users, const float *table, const float *th,
+                               const float *w, int64_t I, int64_t user_begin, const int64_t *hist_rowptr, const int64_t *hist_col,
+                               float mask_value, float *scores, size_t scores_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
