@@ -13,10 +13,9 @@
 // g2 part is sparse and is an owner walk that recomputes the A aspects of one (sample, table row).
 // No atomics: partials are added in a fixed order and every output element has one owner; two runs give the same bits.
 #include "common.h"
+#include "vae_common.h"
 
 namespace chaorec {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int DV_K = 25;          // latent width (Model/DualVAE.py:37)
 constexpr int DV_A = 5;           // aspects (:38)
@@ -24,19 +23,9 @@ constexpr int DV_H = 20;          // encoder and decoder hidden width (:48-49)
 constexpr int DV_KS = 13;         // MFMA k-steps over K padded to 26
 constexpr int DV_HS = 10;         // MFMA k-steps over H
 constexpr int DV_AK = DV_A * DV_K, DV_AH = DV_A * DV_H;
-constexpr int DV_SB = 128;        // samples per workgroup (4 waves x 32)
-constexpr int DV_TI = 128;        // table rows per tile of the sample-owned passes
-constexpr int DV_TW = 64;         // table rows per workgroup of the table-owned passes
 constexpr float DV_EPS = 1e-10f;  // (:15)
 
-__device__ __forceinline__ int dv_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 __device__ __forceinline__ float dv_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ f32x16 dv_zero() {
-  f32x16 v;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) v[q] = 0.f;
-  return v;
-}
 
 // the step counter the device-drawn epsilon is keyed by: state[0] += 1, state[1] = state[0]
 __global__ void dv_tick_kernel(int64_t *state) {
@@ -58,39 +47,13 @@ __global__ __launch_bounds__(128) void dv_encode_fwd_kernel(const int64_t *__res
   if (t >= DV_AH) return;
   const int a = t / DV_H, c = t % DV_H;
   const int64_t b = blockIdx.x, id = ids[b];
-  const bool ok = id >= 0 && id < S;
-  const int64_t beg = ok ? rowptr[id] : 0, n_e = ok ? rowptr[id + 1] - beg : 0;
+  const auto [beg, n_e] = vae_hist_row(rowptr, id, S);
   float acc = 0.f;
   for (int64_t j = 0; j < n_e; ++j) {
     const int64_t n = col[beg + j];
     acc += w[n * DV_A + a] * We_t[n * DV_H + c];
   }
   pre[b * DV_AH + t] = bias[c] + acc;
-}
-
-// table row n's samples: its entries of the transposed CSR (ascending), per entry the sample slots
-// perm[slot_ptr[id] .. slot_ptr[id + 1]) (ascending sample number: a stable sort of the batch); the whole wave calls
-// f(slot) for each, in that order
-template <class F>
-__device__ __forceinline__ void dv_walk(int64_t n, const int64_t *__restrict__ tptr, const int32_t *__restrict__ tcol,
-                                        const int64_t *__restrict__ slot_ptr, const int64_t *__restrict__ perm, int lane, F f) {
-  const int64_t beg = tptr[n], end = tptr[n + 1];
-  for (int64_t e0 = beg; e0 < end; e0 += 64) {
-    const int64_t e = e0 + lane;
-    int64_t lo = 0, hi = 0;
-    if (e < end) {
-      const int64_t id = tcol[e];
-      lo = slot_ptr[id];
-      hi = slot_ptr[id + 1];
-    }
-    unsigned long long mask = __ballot(hi > lo);
-    while (mask) {
-      const int src = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int64_t lo_s = __shfl(lo, src, 64), hi_s = __shfl(hi, src, 64);
-      for (int64_t q = lo_s; q < hi_s; ++q) f(perm[q]);
-    }
-  }
 }
 
 // dWe_t[n, c] = sum_{slots of n} sum_a w[n, a] dpre[slot, a, c]   (lanes 0 .. 19)
@@ -111,7 +74,7 @@ __global__ __launch_bounds__(256) void dv_encode_bwd_kernel(int64_t N, const int
 #pragma unroll
   for (int c = 0; c < DV_H; ++c) wrow[c] = We_t[n * DV_H + c];
   float acc = 0.f;
-  dv_walk(n, tptr, tcol, slot_ptr, perm, lane, [&](int64_t slot) {
+  vae_item_walk(n, tptr, tcol, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
     const float *g = dpre + slot * DV_AH;
     if (colw) {
       float v = 0.f;
@@ -143,15 +106,15 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
                                                       float *__restrict__ psum, float *__restrict__ pnei,
                                                       const float *__restrict__ g1, const float *__restrict__ gN,
                                                       float *__restrict__ dzp, float *__restrict__ dzhp) {
-  constexpr int LD = DV_TI + 1;
+  constexpr int LD = VAE_TI + 1;
   __shared__ float Ts[DV_K + 1][LD];      // [k][table row]
   __shared__ float Hs[DV_H + 1][LD];      // [h][table row]
-  __shared__ float ws[DV_TI];             // w[n, a] (0 past the end: the column adds nothing)
+  __shared__ float ws[VAE_TI];             // w[n, a] (0 past the end: the column adds nothing)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
   const int a = blockIdx.z;
-  const int64_t b = (int64_t)blockIdx.x * DV_SB + wave * 32 + r;
+  const int64_t b = (int64_t)blockIdx.x * VAE_SB + wave * 32 + r;
   const bool live = b < B;
-  const int64_t n_tiles = (N + DV_TI - 1) / DV_TI;
+  const int64_t n_tiles = (N + VAE_TI - 1) / VAE_TI;
   const int64_t t_beg = (int64_t)blockIdx.y * tiles_per_split, t_end = min(n_tiles, t_beg + tiles_per_split);
   const int rk = r < DV_K ? r : DV_K, rh = r < DV_H ? r : DV_H;
 
@@ -166,29 +129,29 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
   for (int s = 0; s < DV_HS; ++s) bh[s] = live ? zh[(b * DV_A + a) * DV_H + 2 * s + h] : 0.f;
   const float my_g1 = BWD && live ? g1[b] : 0.f;
   float ssum = 0.f;
-  f32x16 o1 = dv_zero(), o2 = dv_zero();      // nei | dz, dzh
+  f32x16 o1 = vae_zero(), o2 = vae_zero();      // nei | dz, dzh
 
   if (t < LD) {
     Ts[DV_K][t] = 0.f;
     Hs[DV_H][t] = 0.f;
   }
   for (int64_t tile = t_beg; tile < t_end; ++tile) {
-    const int64_t n0 = tile * DV_TI;
+    const int64_t n0 = tile * VAE_TI;
     __syncthreads();
-    for (int e = t; e < DV_TI * DV_K; e += 256) {
+    for (int e = t; e < VAE_TI * DV_K; e += 256) {
       const int n = e / DV_K, k = e % DV_K;
       Ts[k][n] = (n0 + n < N) ? T[((n0 + n) * DV_A + a) * DV_K + k] : 0.f;
     }
-    for (int e = t; e < DV_TI * DV_H; e += 256) {
+    for (int e = t; e < VAE_TI * DV_H; e += 256) {
       const int n = e / DV_H, k = e % DV_H;
       Hs[k][n] = (n0 + n < N) ? th[((n0 + n) * DV_A + a) * DV_H + k] : 0.f;
     }
-    if (t < DV_TI) ws[t] = (n0 + t < N) ? w[(n0 + t) * DV_A + a] : 0.f;
+    if (t < VAE_TI) ws[t] = (n0 + t < N) ? w[(n0 + t) * DV_A + a] : 0.f;
     __syncthreads();
 
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
-      f32x16 ad = dv_zero(), am = dv_zero();
+      f32x16 ad = vae_zero(), am = vae_zero();
 #pragma unroll
       for (int s = 0; s < DV_KS; ++s) ad = __builtin_amdgcn_mfma_f32_32x32x2f32(Ts[2 * s + h][32 * jt + r], bz[s], ad, 0, 0, 0);
 #pragma unroll
@@ -196,18 +159,18 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
       if (!BWD) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int n = 32 * jt + dv_row(q, h);
+          const int n = 32 * jt + vae_row(q, h);
           const float v = ws[n] * dv_sigmoid(ad[q] + tanhf(am[q]));
           ssum += v;
           o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Ts[rk][n], v, o1, 0, 0, 0);
         }
       } else {
-        f32x16 an = dv_zero();
+        f32x16 an = vae_zero();
 #pragma unroll
         for (int s = 0; s < DV_KS; ++s) an = __builtin_amdgcn_mfma_f32_32x32x2f32(Ts[2 * s + h][32 * jt + r], bn[s], an, 0, 0, 0);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int n = 32 * jt + dv_row(q, h);
+          const int n = 32 * jt + vae_row(q, h);
           const float tm = tanhf(am[q]), sg = dv_sigmoid(ad[q] + tm);
           const float dl = ws[n] * (my_g1 + an[q]) * (sg * (1.0f - sg));
           const float dm = dl * (1.0f - tm * tm);
@@ -218,7 +181,7 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
     }
   }
 
-  // o1 / o2: row = dv_row(reg, h) (the k or h index), column = the lane's sample
+  // o1 / o2: row = vae_row(reg, h) (the k or h index), column = the lane's sample
   if (!BWD) {
     const float s2 = __shfl_xor(ssum, 32, 64);     // the two half-waves saw different table rows of the same sample: half 0 first
     if (live && h == 0) psum[((int64_t)blockIdx.y * DV_A + a) * B + b] = ssum + s2;
@@ -226,15 +189,15 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
       float *out = pnei + (((int64_t)blockIdx.y * B + b) * DV_A + a) * DV_K;
 #pragma unroll
       for (int q = 0; q < 16; ++q)
-        if (dv_row(q, h) < DV_K) out[dv_row(q, h)] = o1[q];
+        if (vae_row(q, h) < DV_K) out[vae_row(q, h)] = o1[q];
     }
   } else if (live) {
     float *out = dzp + (((int64_t)blockIdx.y * B + b) * DV_A + a) * DV_K;
     float *outh = dzhp + (((int64_t)blockIdx.y * B + b) * DV_A + a) * DV_H;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      if (dv_row(q, h) < DV_K) out[dv_row(q, h)] = o1[q];
-      if (dv_row(q, h) < DV_H) outh[dv_row(q, h)] = o2[q];
+      if (vae_row(q, h) < DV_K) out[vae_row(q, h)] = o1[q];
+      if (vae_row(q, h) < DV_H) outh[vae_row(q, h)] = o2[q];
     }
   }
 }
@@ -286,8 +249,7 @@ __global__ __launch_bounds__(64) void dv_fwd_finish_kernel(const int64_t *__rest
   float zk[DV_A], hk[DV_A];
   dv_load_row(z, zh, b, lane, zk, hk);
   const int64_t id = ids[b];
-  const bool ok = id >= 0 && id < S;
-  const int64_t beg = ok ? rowptr[id] : 0, n_e = ok ? rowptr[id + 1] - beg : 0;
+  const auto [beg, n_e] = vae_hist_row(rowptr, id, S);
   double part = 0.0;
   for (int64_t j = 0; j < n_e; ++j) {
     const int64_t n = col[beg + j];
@@ -323,8 +285,7 @@ __global__ __launch_bounds__(64) void dv_bwd_finish_kernel(const int64_t *__rest
       if (lane < DV_H) vh[a] += dzhp[((s * B + b) * DV_A + a) * DV_H + lane];
     }
   const int64_t id = ids[b];
-  const bool ok = id >= 0 && id < S;
-  const int64_t beg = ok ? rowptr[id] : 0, n_e = ok ? rowptr[id + 1] - beg : 0;
+  const auto [beg, n_e] = vae_hist_row(rowptr, id, S);
   const float g = g2[b];
   for (int64_t j = 0; j < n_e; ++j) {
     const int64_t n = col[beg + j];
@@ -359,60 +320,60 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
                                                        const float *__restrict__ w, int64_t B, int64_t N,
                                                        const float *__restrict__ g1, const float *__restrict__ gN,
                                                        float *__restrict__ dth, float *__restrict__ dw, float *__restrict__ scores) {
-  constexpr int LW = DV_TW + 1, LZ = DV_K + 2, LH = DV_H + 1;
+  constexpr int LW = VAE_TW + 1, LZ = DV_K + 2, LH = DV_H + 1;
   __shared__ float Ws[DV_K + 1][LW];      // [k][table row], row 25 zero
   __shared__ float Hs[DV_H][LW];          // [h][table row]
-  __shared__ float Zs[DV_SB][LZ];         // [sample][k], column 25 zero
-  __shared__ float Gs[SCORES ? 1 : DV_SB][LZ];
-  __shared__ float ZHs[DV_SB][LH];        // [sample][h], column 20 zero
-  __shared__ float g1s[DV_SB];
-  __shared__ float wcol[DV_TW];
-  __shared__ float bsum[4][DV_TW];
+  __shared__ float Zs[VAE_SB][LZ];         // [sample][k], column 25 zero
+  __shared__ float Gs[SCORES ? 1 : VAE_SB][LZ];
+  __shared__ float ZHs[VAE_SB][LH];        // [sample][h], column 20 zero
+  __shared__ float g1s[VAE_SB];
+  __shared__ float wcol[VAE_TW];
+  __shared__ float bsum[4][VAE_TW];
   float (*Rs)[33] = reinterpret_cast<float (*)[33]>(&Zs[0][0]);   // [table row][h]: the waves' sums, once Zs is done with
-  static_assert(DV_TW * 33 <= DV_SB * LZ, "the reduction buffer lives in Zs");
+  static_assert(VAE_TW * 33 <= VAE_SB * LZ, "the reduction buffer lives in Zs");
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-  const int64_t n0 = (int64_t)blockIdx.x * DV_TW;
+  const int64_t n0 = (int64_t)blockIdx.x * VAE_TW;
   const int rh = r < DV_H ? r : DV_H;
-  f32x16 acc2[2] = {dv_zero(), dv_zero()};      // d th | the scores
-  if (t < DV_TW) {
+  f32x16 acc2[2] = {vae_zero(), vae_zero()};      // d th | the scores
+  if (t < VAE_TW) {
 #pragma unroll
     for (int wv = 0; wv < 4; ++wv) bsum[wv][t] = 0.f;
   }
 
   const int a_beg = SCORES ? 0 : (int)blockIdx.y, a_end = SCORES ? DV_A : a_beg + 1;
-  const int64_t s_beg = SCORES ? (int64_t)blockIdx.y * DV_SB : 0, s_end = SCORES ? min(B, s_beg + DV_SB) : B;
+  const int64_t s_beg = SCORES ? (int64_t)blockIdx.y * VAE_SB : 0, s_end = SCORES ? min(B, s_beg + VAE_SB) : B;
   for (int a = a_beg; a < a_end; ++a) {
     __syncthreads();
-    for (int e = t; e < DV_TW * DV_K; e += 256) {
+    for (int e = t; e < VAE_TW * DV_K; e += 256) {
       const int n = e / DV_K, k = e % DV_K;
       Ws[k][n] = (n0 + n < N) ? T[((n0 + n) * DV_A + a) * DV_K + k] : 0.f;
     }
-    for (int e = t; e < DV_TW * DV_H; e += 256) {
+    for (int e = t; e < VAE_TW * DV_H; e += 256) {
       const int n = e / DV_H, k = e % DV_H;
       Hs[k][n] = (n0 + n < N) ? th[((n0 + n) * DV_A + a) * DV_H + k] : 0.f;
     }
-    if (t < DV_TW) {
+    if (t < VAE_TW) {
       Ws[DV_K][t] = 0.f;
       wcol[t] = (n0 + t < N) ? w[(n0 + t) * DV_A + a] : 0.f;
     }
-    for (int64_t s0 = s_beg; s0 < s_end; s0 += DV_SB) {
+    for (int64_t s0 = s_beg; s0 < s_end; s0 += VAE_SB) {
       __syncthreads();
-      for (int e = t; e < DV_SB * (DV_K + 1); e += 256) {
+      for (int e = t; e < VAE_SB * (DV_K + 1); e += 256) {
         const int row = e / (DV_K + 1), k = e % (DV_K + 1);
         const bool in = s0 + row < B && k < DV_K;
         Zs[row][k] = in ? z[((s0 + row) * DV_A + a) * DV_K + k] : 0.f;
         if (!SCORES) Gs[row][k] = in ? gN[((s0 + row) * DV_A + a) * DV_K + k] : 0.f;
       }
-      for (int e = t; e < DV_SB * (DV_H + 1); e += 256) {
+      for (int e = t; e < VAE_SB * (DV_H + 1); e += 256) {
         const int row = e / (DV_H + 1), k = e % (DV_H + 1);
         ZHs[row][k] = (s0 + row < B && k < DV_H) ? zh[((s0 + row) * DV_A + a) * DV_H + k] : 0.f;
       }
-      if (!SCORES && t < DV_SB) g1s[t] = (s0 + t < B) ? g1[s0 + t] : 0.f;      // a sample past the end: q = 0
+      if (!SCORES && t < VAE_SB) g1s[t] = (s0 + t < B) ? g1[s0 + t] : 0.f;      // a sample past the end: q = 0
       __syncthreads();
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt) {
         const float wl = wcol[32 * jt + r];
-        f32x16 ad = dv_zero(), am = dv_zero();
+        f32x16 ad = vae_zero(), am = vae_zero();
 #pragma unroll
         for (int s = 0; s < DV_KS; ++s)
           ad = __builtin_amdgcn_mfma_f32_32x32x2f32(Zs[wave * 32 + r][2 * s + h], Ws[2 * s + h][32 * jt + r], ad, 0, 0, 0);
@@ -423,14 +384,14 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
 #pragma unroll
           for (int q = 0; q < 16; ++q) acc2[jt][q] += wl * dv_sigmoid(ad[q] + tanhf(am[q]));
         } else {
-          f32x16 an = dv_zero();
+          f32x16 an = vae_zero();
 #pragma unroll
           for (int s = 0; s < DV_KS; ++s)
             an = __builtin_amdgcn_mfma_f32_32x32x2f32(Gs[wave * 32 + r][2 * s + h], Ws[2 * s + h][32 * jt + r], an, 0, 0, 0);
           float bk = 0.f;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const int sm = wave * 32 + dv_row(q, h);
+            const int sm = wave * 32 + vae_row(q, h);
             const float tm = tanhf(am[q]), sg = dv_sigmoid(ad[q] + tm);
             const float qq = g1s[sm] + an[q];
             bk += sg * qq;
@@ -450,14 +411,14 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
       const int64_t n = n0 + 32 * jt + r;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int64_t row = s_beg + wave * 32 + dv_row(q, h);
+        const int64_t row = s_beg + wave * 32 + vae_row(q, h);
         if (row < B && n < N) scores[row * N + n] = acc2[jt][q];
       }
     }
     return;
   }
 
-  // waves 0..3 in order; acc2[jt]: row = table row 32 jt + dv_row(reg, h), column = h index r
+  // waves 0..3 in order; acc2[jt]: row = table row 32 jt + vae_row(reg, h), column = h index r
   const int a = a_beg;
   for (int wv = 0; wv < 4; ++wv) {
     __syncthreads();
@@ -466,17 +427,17 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
       for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          float *dst = &Rs[32 * jt + dv_row(q, h)][r];
+          float *dst = &Rs[32 * jt + vae_row(q, h)][r];
           *dst = (wv ? *dst : 0.f) + acc2[jt][q];
         }
     }
   }
   __syncthreads();
-  for (int e = t; e < DV_TW * DV_H; e += 256) {
+  for (int e = t; e < VAE_TW * DV_H; e += 256) {
     const int n = e / DV_H, k = e % DV_H;
     if (n0 + n < N) dth[((n0 + n) * DV_A + a) * DV_H + k] = Rs[n][k];
   }
-  if (t < DV_TW && n0 + t < N) dw[(n0 + t) * DV_A + a] = ((bsum[0][t] + bsum[1][t]) + bsum[2][t]) + bsum[3][t];
+  if (t < VAE_TW && n0 + t < N) dw[(n0 + t) * DV_A + a] = ((bsum[0][t] + bsum[1][t]) + bsum[2][t]) + bsum[3][t];
 }
 
 // the sparse q = g2_b / (p_bn + EPS) of table row n's samples, ADDED to what the dense pass wrote (one owner per row):
@@ -495,7 +456,7 @@ __global__ __launch_bounds__(256) void dv_table_sparse_kernel(int64_t N, const i
 #pragma unroll
   for (int a = 0; a < DV_A; ++a) vh[a] = vw[a] = 0.f;
   bool any = false;
-  dv_walk(n, tptr, tcol, slot_ptr, perm, lane, [&](int64_t slot) {
+  vae_item_walk(n, tptr, tcol, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
     float zk[DV_A], hk[DV_A], s[DV_A], tm[DV_A], wa[DV_A];
     dv_load_row(z, zh, slot, lane, zk, hk);
     const float p = dv_pair(zk, hk, tk, thk, w + n * DV_A, s, tm, wa);
@@ -529,18 +490,6 @@ __global__ __launch_bounds__(128) void dv_writeback_kernel(const int64_t *__rest
   if (t < DV_AK) {
     table[id * DV_AK + t] = z[b * DV_AK + t];
     mu_table[id * DV_AK + t] = mu[b * DV_AK + t];
-  }
-}
-
-// scores[u - u0, i] = mask for the history entries of users u0 .. u1 (Model/DualVAE.py:325-327): one wave per user
-__global__ __launch_bounds__(256) void dv_mask_kernel(float *__restrict__ scores, int64_t u0, int64_t u1, int64_t I,
-                                                      const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, float mask) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = u0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= u1) return;
-  for (int64_t e = rowptr[u] + lane; e < rowptr[u + 1]; e += 64) {
-    const int64_t i = col[e];
-    if (i >= 0 && i < I) scores[(u - u0) * I + i] = mask;
   }
 }
 
@@ -628,18 +577,6 @@ __global__ __launch_bounds__(256) void dv_loss_kernel(const double *__restrict__
   }
 }
 
-static void dv_plan(int64_t B, int64_t N, int64_t &splits, int64_t &tiles_per_split) {
-  const int64_t n_tiles = (N + DV_TI - 1) / DV_TI, sblocks = (B + DV_SB - 1) / DV_SB;
-  int64_t want = (1024 + sblocks * DV_A - 1) / (sblocks * DV_A);      // ~4 workgroups per CU over (sample blocks, a, splits)
-  if (want > 64) want = 64;
-  if (want > n_tiles) want = n_tiles;
-  if (want < 1) want = 1;
-  tiles_per_split = (n_tiles + want - 1) / want;
-  if (tiles_per_split < 1) tiles_per_split = 1;
-  splits = (n_tiles + tiles_per_split - 1) / tiles_per_split;
-  if (splits < 1) splits = 1;
-}
-
 static int dv_shape(const char *what, int32_t k, int32_t a, int32_t hidden) {
   if (k != DV_K || a != DV_A || hidden != DV_H)
     return fail(CHAOREC_E_INVALID, "%s: k=%d a=%d hidden=%d, the kernels tile k=%d a=%d hidden=%d", what, (int)k, (int)a, (int)hidden,
@@ -654,7 +591,7 @@ using namespace chaorec;
 extern "C" int64_t chaorec_dualvae_splits(int64_t B, int64_t N) {
   if (B <= 0 || N <= 0) return 1;
   int64_t s, tp;
-  dv_plan(B, N, s, tp);
+  vae_split_plan(B, N, DV_A, s, tp);
   return s;
 }
 
@@ -694,10 +631,10 @@ extern "C" int chaorec_dualvae_dense_fwd_f32(const int64_t *ids, int64_t B, int6
     return fail(CHAOREC_E_INVALID, "dualvae_dense_fwd: NULL argument");
   if (B <= 0 || S <= 0 || N <= 0) return fail(CHAOREC_E_INVALID, "dualvae_dense_fwd: B=%lld S=%lld N=%lld", (long long)B, (long long)S, (long long)N);
   int64_t s, tp;
-  dv_plan(B, N, s, tp);
+  vae_split_plan(B, N, DV_A, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "dualvae_dense_fwd: splits %lld, chaorec_dualvae_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((B + DV_SB - 1) / DV_SB), (unsigned)s, DV_A);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s, DV_A);
   hipLaunchKernelGGL((dv_rows_kernel<false>), grid, dim3(256), 0, st, z, zh, table, th, w, B, N, tp, psum, pnei, (const float *)nullptr,
                      (const float *)nullptr, (float *)nullptr, (float *)nullptr);
   int rc = check_launch("dv_rows_kernel<fwd>");
@@ -717,10 +654,10 @@ extern "C" int chaorec_dualvae_dense_bwd_f32(const int64_t *ids, int64_t B, int6
     return fail(CHAOREC_E_INVALID, "dualvae_dense_bwd: NULL argument");
   if (B <= 0 || S <= 0 || N <= 0) return fail(CHAOREC_E_INVALID, "dualvae_dense_bwd: B=%lld S=%lld N=%lld", (long long)B, (long long)S, (long long)N);
   int64_t s, tp;
-  dv_plan(B, N, s, tp);
+  vae_split_plan(B, N, DV_A, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "dualvae_dense_bwd: splits %lld, chaorec_dualvae_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((B + DV_SB - 1) / DV_SB), (unsigned)s, DV_A);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s, DV_A);
   hipLaunchKernelGGL((dv_rows_kernel<true>), grid, dim3(256), 0, st, z, zh, table, th, w, B, N, tp, (float *)nullptr, (float *)nullptr, g1, gN,
                      dzp, dzhp);
   int rc = check_launch("dv_rows_kernel<bwd>");
@@ -729,7 +666,7 @@ extern "C" int chaorec_dualvae_dense_bwd_f32(const int64_t *ids, int64_t B, int6
                      (const float *)dzp, (const float *)dzhp, s, dz, dzh);
   rc = check_launch("dv_bwd_finish_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL((dv_table_kernel<false>), dim3((unsigned)((N + DV_TW - 1) / DV_TW), DV_A), dim3(256), 0, st, z, zh, table, th, w, B, N,
+  hipLaunchKernelGGL((dv_table_kernel<false>), dim3((unsigned)((N + VAE_TW - 1) / VAE_TW), DV_A), dim3(256), 0, st, z, zh, table, th, w, B, N,
                      g1, gN, dth, dw, (float *)nullptr);
   rc = check_launch("dv_table_kernel<grad>");
   if (rc) return rc;
@@ -755,16 +692,16 @@ extern "C" int chaorec_dualvae_scores_f32(const float *z, const float *zh, int64
   const size_t need = (size_t)n_users * (size_t)I * sizeof(float);
   if (scores_bytes < need || need > (size_t)CHAOREC_DUALVAE_STAGING_BYTES)
     return fail(CHAOREC_E_WORKSPACE, "dualvae_scores: staging of %zu bytes (given %zu, cap %zu)", need, scores_bytes, (size_t)CHAOREC_DUALVAE_STAGING_BYTES);
-  const int64_t sblocks = (n_users + DV_SB - 1) / DV_SB;
+  const int64_t sblocks = (n_users + VAE_SB - 1) / VAE_SB;
   if (sblocks > 65535) return fail(CHAOREC_E_INVALID, "dualvae_scores: %lld users in one range", (long long)n_users);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((dv_table_kernel<true>), dim3((unsigned)((I + DV_TW - 1) / DV_TW), (unsigned)sblocks), dim3(256), 0, st, z, zh, table, th,
+  hipLaunchKernelGGL((dv_table_kernel<true>), dim3((unsigned)((I + VAE_TW - 1) / VAE_TW), (unsigned)sblocks), dim3(256), 0, st, z, zh, table, th,
                      w, n_users, I, (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, scores);
   int rc = check_launch("dv_table_kernel<scores>");
   if (rc) return rc;
-  hipLaunchKernelGGL(dv_mask_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, scores, user_begin, user_begin + n_users, I,
+  hipLaunchKernelGGL(vae_mask_kernel<>, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, scores, user_begin, user_begin + n_users, I,
                      hist_rowptr, hist_col, mask_value);
-  return check_launch("dv_mask_kernel");
+  return check_launch("vae_mask_kernel");
 }
 
 extern "C" size_t chaorec_dualvae_linear_bwd_workspace_bytes(int64_t R, int32_t M) {

@@ -15,41 +15,20 @@
 // d cates) loops over all rows; the sparse x_bi terms are owner walks that recompute the K logits of one (sample, item).
 // No atomics, no memset: partials are added in a fixed order; two runs give the same bits.
 #include "common.h"
+#include "vae_common.h"
 
 namespace chaorec {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MC_D = 64;          // dim_E the kernels tile
 constexpr int MC_K = 10;          // kfac (Model/MacridVAE.py:27)
 constexpr int MC_H = 600;         // encoder hidden width (:28)
 constexpr int MC_H4 = MC_H / 4;
-constexpr int MC_SB = 128;        // rows per workgroup (4 waves x 32)
-constexpr int MC_TI = 128;        // items per tile of the sample-owned passes
-constexpr int MC_TW = 64;         // items per workgroup of the item-owned pass
+static_assert(MC_D == VAE_D, "the staging helpers move rows of dim_E floats");
 constexpr uint64_t MC_SALT_KEEP = 0x6D61637269643031ull, MC_SALT_GUMBEL = 0x6D61637269643032ull, MC_SALT_EPS = 0x6D61637269643033ull;
 
-__device__ __forceinline__ int mc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-// counter RNG (seed, step, a, b) -> uniform STRICTLY inside (0, 1): 23 bits + 0.5 is exact in fp32 (log(-log(u)) is finite)
-__device__ __forceinline__ uint64_t mc_key(uint64_t seed, uint64_t step, uint64_t salt) { return mix64(mix64(seed ^ salt) + step); }
-__device__ __forceinline__ float mc_uniform(uint64_t key, uint64_t a, uint64_t b) {
-  const uint64_t r = mix64(key ^ mix64((a << 32) ^ b));
-  return ((float)(r >> 41) + 0.5f) * (1.0f / 8388608.0f);
-}
-
-struct McKeep {   // is entry j of sample b's history row kept?  given flags (parity tests) or the counter RNG
-  const uint8_t *keep;
-  const int64_t *keep_off;
-  uint64_t key;
-  float keep_prob;
-  int training;
-  __device__ __forceinline__ bool operator()(int64_t b, int64_t j) const {
-    if (!training) return true;
-    if (keep) return keep[keep_off[b] + j] != 0;
-    return mc_uniform(key, (uint64_t)b, (uint64_t)j) < keep_prob;
-  }
-};
+// the uniform keeps 23 bits here (MultVAE's keeps 24): the streams the goldens were drawn from
+constexpr int MC_BITS = 23;
+using McKeep = VaeKeep<MC_BITS>;
 
 // Model/MacridVAE.py:135-137: `update` is incremented BEFORE the anneal is read.  state[0] = update, state[1] = the
 // count this step's draws are keyed by (the same number).
@@ -58,31 +37,7 @@ __global__ void mc_tick_kernel(int64_t *state, float *anneal, float cap, int64_t
   const int64_t c = state[0] + 1;
   state[0] = c;
   state[1] = c;
-  const double a = total > 0 ? (double)c / (double)total : (double)cap;
-  anneal[0] = (float)(a < (double)cap ? a : (double)cap);
-}
-
-__global__ __launch_bounds__(256) void mc_sum_kernel(const float *__restrict__ in, int64_t n, float scale, float *__restrict__ out) {
-  __shared__ double red[256];
-  double v = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) v += (double)in[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(red[0] * (double)scale);
-}
-
-// eps[e] = std * N(0, 1) keyed (seed, state[1], e): Box-Muller
-__global__ __launch_bounds__(256) void mc_normal_kernel(float *__restrict__ out, int64_t n, uint64_t seed, const int64_t *__restrict__ state,
-                                                        float std) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const uint64_t key = mc_key(seed, (uint64_t)state[1], MC_SALT_EPS);
-  const float u1 = mc_uniform(key, (uint64_t)e, 0), u2 = mc_uniform(key, (uint64_t)e, 1);
-  out[e] = std * (sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2));
+  anneal[0] = vae_anneal(c, total, cap);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -112,13 +67,13 @@ __global__ __launch_bounds__(256) void mc_concept_fwd_kernel(const float *__rest
   const float x = E[i * MC_D + lane];
   const float it = x / fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);
   items[i * MC_D + lane] = it;
-  const uint64_t key = training && !gumbel_in ? mc_key(seed, (uint64_t)state[1], MC_SALT_GUMBEL) : 0;
+  const uint64_t key = training && !gumbel_in ? vae_key(seed, (uint64_t)state[1], MC_SALT_GUMBEL) : 0;
   float l[MC_K], m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < MC_K; ++k) {
     l[k] = wave_sum(it * cs[k][lane]) * inv_tau;
     if (training)      // g = -log(Exp(1)) (F.gumbel_softmax, tau = 1): Exp(1) = -log(u)
-      l[k] += gumbel_in ? gumbel_in[i * MC_K + k] : -logf(-logf(mc_uniform(key, (uint64_t)i, (uint64_t)k)));
+      l[k] += gumbel_in ? gumbel_in[i * MC_K + k] : -logf(-logf(vae_uniform<MC_BITS>(key, (uint64_t)i, (uint64_t)k)));
     m = fmaxf(m, l[k]);
   }
   float sum = 0.f;
@@ -206,10 +161,8 @@ __global__ __launch_bounds__(192) void mc_encode_fwd_kernel(
   const bool active = t < MC_H4;
   const int c4 = 4 * (active ? t : 0);
   const int64_t b = blockIdx.x;
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
-  if (kf.training && !kf.keep) kf.key = mc_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
+  if (kf.training && !kf.keep) kf.key = vae_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
   float4 acc[MC_K];
 #pragma unroll
   for (int k = 0; k < MC_K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -226,9 +179,7 @@ __global__ __launch_bounds__(192) void mc_encode_fwd_kernel(
       acc[k].w += c * w.w;
     }
   }
-  // F.normalize's 1 / max(|x|, 1e-12) of a multi-hot row with n ones, times dropout's 1 / (1 - p) in training
-  float sc = 1.0f / fmaxf(sqrtf((float)n), 1e-12f);
-  if (kf.training) sc = sc / kf.keep_prob;
+  const float sc = vae_row_scale(n, kf.training, kf.keep_prob);
   if (t == 0) srow[b] = sc;
   if (!active) return;
   const float4 bias = *reinterpret_cast<const float4 *>(b1 + c4);
@@ -236,34 +187,6 @@ __global__ __launch_bounds__(192) void mc_encode_fwd_kernel(
   for (int k = 0; k < MC_K; ++k)
     *reinterpret_cast<float4 *>(a + (b * MC_K + k) * MC_H + c4) =
         make_float4(bias.x + sc * acc[k].x, bias.y + sc * acc[k].y, bias.z + sc * acc[k].z, bias.w + sc * acc[k].w);
-}
-
-// item i's users (item-major CSR, ascending), per user the sample slots perm[slot_ptr[u] .. slot_ptr[u + 1]) (ascending
-// sample number: a stable sort of the batch); the whole wave calls f(slot, pos) for each, in that order
-template <class F>
-__device__ __forceinline__ void mc_item_walk(int64_t i, const int64_t *__restrict__ item_ptr, const int32_t *__restrict__ item_users,
-                                             const int32_t *__restrict__ item_pos, const int64_t *__restrict__ slot_ptr,
-                                             const int64_t *__restrict__ perm, int lane, F f) {
-  const int64_t beg = item_ptr[i], end = item_ptr[i + 1];
-  for (int64_t e0 = beg; e0 < end; e0 += 64) {
-    const int64_t e = e0 + lane;
-    int64_t lo = 0, hi = 0;
-    int pos = 0;
-    if (e < end) {
-      const int64_t u = item_users[e];
-      lo = slot_ptr[u];
-      hi = slot_ptr[u + 1];
-      pos = item_pos ? item_pos[e] : 0;
-    }
-    unsigned long long mask = __ballot(hi > lo);
-    while (mask) {
-      const int src = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int64_t lo_s = __shfl(lo, src, 64), hi_s = __shfl(hi, src, 64);
-      const int pos_s = __shfl(pos, src, 64);
-      for (int64_t q = lo_s; q < hi_s; ++q) f(perm[q], pos_s);
-    }
-  }
 }
 
 // dW1_t[i, :] = sum_{b, keep_bi} s_b sum_k c_ik da_bk;  dcates[i, k] = sum_{b, keep_bi} s_b W1_t[i, :] . da_bk.
@@ -278,7 +201,7 @@ __global__ __launch_bounds__(192) void mc_encode_dw_kernel(
   const bool active = t < MC_H4;
   const int c4 = 4 * (active ? t : 0);
   const int64_t i = blockIdx.x;
-  if (kf.training && !kf.keep) kf.key = mc_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
+  if (kf.training && !kf.keep) kf.key = vae_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
   float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
   if (active) w = *reinterpret_cast<const float4 *>(W1_t + i * MC_H + c4);
   float c[MC_K], dc[MC_K];
@@ -288,7 +211,7 @@ __global__ __launch_bounds__(192) void mc_encode_dw_kernel(
     dc[k] = 0.f;
   }
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  mc_item_walk(i, item_ptr, item_users, item_pos, slot_ptr, perm, lane, [&](int64_t slot, int pos) {
+  vae_item_walk(i, item_ptr, item_users, item_pos, slot_ptr, perm, lane, [&](int64_t slot, int pos) {
     if (kf(slot, pos) && active) {
       const float s = srow[slot];
       float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -351,14 +274,14 @@ __global__ __launch_bounds__(256) void mc_rows_kernel(const float *__restrict__ 
                                                       const float *__restrict__ cates, int64_t B, int64_t I, int64_t tiles_per_split,
                                                       float inv_tau, float *__restrict__ ps, const float *__restrict__ coef,
                                                       const float *__restrict__ gce, float *__restrict__ dzp) {
-  constexpr int LD = MC_TI + 1;
+  constexpr int LD = VAE_TI + 1;
   __shared__ float Ws[MC_D][LD];      // [d][item]
-  __shared__ float cs[MC_TI];         // c_ik of the tile (0 past the end: the column adds nothing)
+  __shared__ float cs[VAE_TI];         // c_ik of the tile (0 past the end: the column adds nothing)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
   const int k = blockIdx.z;
-  const int64_t b = (int64_t)blockIdx.x * MC_SB + wave * 32 + r;
+  const int64_t b = (int64_t)blockIdx.x * VAE_SB + wave * 32 + r;
   const bool live = b < B;
-  const int64_t n_tiles = (I + MC_TI - 1) / MC_TI;
+  const int64_t n_tiles = (I + VAE_TI - 1) / VAE_TI;
   const int64_t t_beg = (int64_t)blockIdx.y * tiles_per_split, t_end = min(n_tiles, t_beg + tiles_per_split);
 
   float bf[MC_D / 2];
@@ -366,45 +289,30 @@ __global__ __launch_bounds__(256) void mc_rows_kernel(const float *__restrict__ 
   for (int s = 0; s < MC_D / 2; ++s) bf[s] = live ? zh[(b * MC_K + k) * MC_D + 2 * s + h] : 0.f;
   float ssum = 0.f;
   const float my_coef = WITH_DZ ? (live ? gce[0] * coef[b] : 0.f) : 0.f;
-  f32x16 dz[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dz[j][q] = 0.f;
+  f32x16 dz[2] = {vae_zero(), vae_zero()};
 
   for (int64_t tile = t_beg; tile < t_end; ++tile) {
-    const int64_t i0 = tile * MC_TI;
+    const int64_t i0 = tile * VAE_TI;
     __syncthreads();
-#pragma unroll
-    for (int p = 0; p < MC_TI * MC_D / 4 / 256; ++p) {
-      const int v = t + p * 256, item = v >> 4, k4 = (v & 15) * 4;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i0 + item < I) x = *reinterpret_cast<const float4 *>(items + (i0 + item) * MC_D + k4);
-      Ws[k4 + 0][item] = x.x;
-      Ws[k4 + 1][item] = x.y;
-      Ws[k4 + 2][item] = x.z;
-      Ws[k4 + 3][item] = x.w;
-    }
-    if (t < MC_TI) cs[t] = (i0 + t < I) ? cates[(i0 + t) * MC_K + k] : 0.f;
+    vae_stage_transposed<VAE_TI>(Ws, items, i0, I, t);
+    if (t < VAE_TI) cs[t] = (i0 + t < I) ? cates[(i0 + t) * MC_K + k] : 0.f;
     __syncthreads();
 
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
-      f32x16 acc;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+      f32x16 acc = vae_zero();
 #pragma unroll
       for (int s = 0; s < MC_D / 2; ++s)
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[2 * s + h][32 * jt + r], bf[s], acc, 0, 0, 0);
       if (!WITH_DZ) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) ssum += cs[32 * jt + mc_row(q, h)] * expf(acc[q] * inv_tau);      // |l| <= 10: no maximum
+        for (int q = 0; q < 16; ++q) ssum += cs[32 * jt + vae_row(q, h)] * expf(acc[q] * inv_tau);      // |l| <= 10: no maximum
       } else {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = my_coef * (cs[32 * jt + mc_row(q, h)] * expf(acc[q] * inv_tau));
+        for (int q = 0; q < 16; ++q) acc[q] = my_coef * (cs[32 * jt + vae_row(q, h)] * expf(acc[q] * inv_tau));
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int item = 32 * jt + mc_row(q, h);
+          const int item = 32 * jt + vae_row(q, h);
 #pragma unroll
           for (int j = 0; j < 2; ++j)
             dz[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[32 * j + r][item], acc[q], dz[j], 0, 0, 0);
@@ -417,13 +325,7 @@ __global__ __launch_bounds__(256) void mc_rows_kernel(const float *__restrict__ 
     const float s2 = __shfl_xor(ssum, 32, 64);     // the two half-waves saw different items of the same row: half 0 first
     if (live && h == 0) ps[((int64_t)blockIdx.y * MC_K + k) * B + b] = ssum + s2;
   } else if (live) {
-    float *out = dzp + (((int64_t)blockIdx.y * B + b) * MC_K + k) * MC_D;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4 *>(out + 32 * j + 8 * g + 4 * h) =
-            make_float4(dz[j][4 * g + 0], dz[j][4 * g + 1], dz[j][4 * g + 2], dz[j][4 * g + 3]);
+    vae_store_dz(dzp + (((int64_t)blockIdx.y * B + b) * MC_K + k) * MC_D, dz, h);
   }
 }
 
@@ -454,9 +356,7 @@ __global__ __launch_bounds__(64) void mc_lse_finish_kernel(
   float zk[MC_K];
 #pragma unroll
   for (int k = 0; k < MC_K; ++k) zk[k] = zh[(b * MC_K + k) * MC_D + lane];
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   double part = 0.0;
   for (int64_t j = 0; j < n; ++j) {
     const int64_t i = col[beg + j];
@@ -488,9 +388,7 @@ __global__ __launch_bounds__(64) void mc_dz_finish_kernel(
   for (int sp = 0; sp < splits; ++sp)
 #pragma unroll
     for (int k = 0; k < MC_K; ++k) v[k] += dzp[(((int64_t)sp * B + b) * MC_K + k) * MC_D + lane];
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   const float gB = gce[0] / (float)B;
   for (int64_t j = 0; j < n; ++j) {
     const int64_t i = col[beg + j];
@@ -519,66 +417,36 @@ __global__ __launch_bounds__(256) void mc_items_kernel(
     const int32_t *__restrict__ item_users, const int64_t *__restrict__ slot_ptr, const int64_t *__restrict__ perm,
     float *__restrict__ d_items, float *__restrict__ d_cates, float *__restrict__ scores) {
   constexpr int LD = MC_D + 1;
-  __shared__ float Ws[MC_D][MC_TW + 1];    // [d][item]
-  __shared__ float Zs[MC_SB][LD];          // [row][d] of the concept in flight
+  __shared__ float Ws[MC_D][VAE_TW + 1];    // [d][item]
+  __shared__ float Zs[VAE_SB][LD];          // [row][d] of the concept in flight
   float (*Rs)[LD] = reinterpret_cast<float (*)[LD]>(&Zs[0][0]);   // [item][d]: the waves' sums, once Zs is done with
-  __shared__ float coefs[MC_SB];
-  __shared__ float Cs[MC_K][MC_TW];
-  __shared__ float bsum[SCORES ? 1 : 4][SCORES ? 1 : MC_K][SCORES ? 1 : MC_TW];
+  __shared__ float coefs[VAE_SB];
+  __shared__ float Cs[MC_K][VAE_TW];
+  __shared__ float bsum[SCORES ? 1 : 4][SCORES ? 1 : MC_K][SCORES ? 1 : VAE_TW];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-  const int64_t i0 = (int64_t)blockIdx.x * MC_TW;
-#pragma unroll
-  for (int p = 0; p < MC_TW * MC_D / 4 / 256; ++p) {
-    const int v = t + p * 256, item = v >> 4, k4 = (v & 15) * 4;
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i0 + item < I) x = *reinterpret_cast<const float4 *>(items + (i0 + item) * MC_D + k4);
-    Ws[k4 + 0][item] = x.x;
-    Ws[k4 + 1][item] = x.y;
-    Ws[k4 + 2][item] = x.z;
-    Ws[k4 + 3][item] = x.w;
-  }
-  for (int e = t; e < MC_K * MC_TW; e += 256) {
-    const int k = e / MC_TW, item = e % MC_TW;
+  const int64_t i0 = (int64_t)blockIdx.x * VAE_TW;
+  vae_stage_transposed<VAE_TW>(Ws, items, i0, I, t);
+  for (int e = t; e < MC_K * VAE_TW; e += 256) {
+    const int k = e / VAE_TW, item = e % VAE_TW;
     Cs[k][item] = (i0 + item < I) ? cates[(i0 + item) * MC_K + k] : 0.f;
     if (!SCORES)
 #pragma unroll
       for (int w = 0; w < 4; ++w) bsum[w][k][item] = 0.f;
   }
   const float g = SCORES ? 0.f : gce[0];
-  f32x16 dw[2][2];
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) dw[jt][j][q] = 0.f;
+  f32x16 dw[2][2] = {{vae_zero(), vae_zero()}, {vae_zero(), vae_zero()}};
 
-  for (int64_t s0 = 0; s0 < B; s0 += MC_SB) {
-    f32x16 pr[2];
-#pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) pr[jt][q] = 0.f;
+  for (int64_t s0 = 0; s0 < B; s0 += VAE_SB) {
+    f32x16 pr[2] = {vae_zero(), vae_zero()};
     for (int k = 0; k < MC_K; ++k) {
       __syncthreads();
-#pragma unroll
-      for (int p = 0; p < MC_SB * MC_D / 4 / 256; ++p) {
-        const int v = t + p * 256, row = v >> 4, k4 = (v & 15) * 4;
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (s0 + row < B) x = *reinterpret_cast<const float4 *>(zh + ((s0 + row) * MC_K + k) * MC_D + k4);
-        Zs[row][k4 + 0] = x.x;
-        Zs[row][k4 + 1] = x.y;
-        Zs[row][k4 + 2] = x.z;
-        Zs[row][k4 + 3] = x.w;
-      }
-      if (!SCORES && k == 0 && t < MC_SB) coefs[t] = (s0 + t < B) ? g * coef[s0 + t] : 0.f;     // a row past the end: P = 0
+      vae_stage_rows(Zs, zh + k * MC_D, MC_K * MC_D, s0, B, t);
+      if (!SCORES && k == 0 && t < VAE_SB) coefs[t] = (s0 + t < B) ? g * coef[s0 + t] : 0.f;     // a row past the end: P = 0
       __syncthreads();
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt) {
         const float cl = Cs[k][32 * jt + r];
-        f32x16 acc;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+        f32x16 acc = vae_zero();
 #pragma unroll
         for (int s = 0; s < MC_D / 2; ++s)
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Zs[wave * 32 + r][2 * s + h], Ws[2 * s + h][32 * jt + r], acc, 0, 0, 0);
@@ -589,13 +457,13 @@ __global__ __launch_bounds__(256) void mc_items_kernel(
           float bk = 0.f;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const float ce = coefs[wave * 32 + mc_row(q, h)] * expf(acc[q] * inv_tau);
+            const float ce = coefs[wave * 32 + vae_row(q, h)] * expf(acc[q] * inv_tau);
             bk += ce;
             acc[q] = ce * cl;
           }
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            const int sm = wave * 32 + mc_row(q, h);
+            const int sm = wave * 32 + vae_row(q, h);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
               dw[jt][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[q], Zs[sm][32 * j + r], dw[jt][j], 0, 0, 0);
@@ -611,7 +479,7 @@ __global__ __launch_bounds__(256) void mc_items_kernel(
         const int64_t i = i0 + 32 * jt + r;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int64_t row = s0 + wave * 32 + mc_row(q, h);
+          const int64_t row = s0 + wave * 32 + vae_row(q, h);
           if (row < B && i < I) scores[row * I + i] = logf(pr[jt][q]);
         }
       }
@@ -619,31 +487,16 @@ __global__ __launch_bounds__(256) void mc_items_kernel(
   }
   if (SCORES) return;
 
-  // waves 0..3 in order; dw[jt][j]: row = item 32 jt + mc_row(reg, h), col = d = 32 j + r
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            float *dst = &Rs[32 * jt + mc_row(q, h)][32 * j + r];
-            *dst = (w ? *dst : 0.f) + dw[jt][j][q];
-          }
-    }
-  }
-  __syncthreads();
+  vae_reduce_waves(Rs, dw, wave, r, h);
   const float gB = g / (float)B;
-  for (int it = wave; it < MC_TW; it += 4) {
+  for (int it = wave; it < VAE_TW; it += 4) {
     const int64_t i = i0 + it;
     if (i >= I) break;
     const float itv = items[i * MC_D + lane];
     float xz = 0.f, hk[MC_K];
 #pragma unroll
     for (int k = 0; k < MC_K; ++k) hk[k] = 0.f;
-    mc_item_walk(i, item_ptr, item_users, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
+    vae_item_walk(i, item_ptr, item_users, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
       float zk[MC_K], e[MC_K], c[MC_K];
 #pragma unroll
       for (int k = 0; k < MC_K; ++k) zk[k] = zh[(slot * MC_K + k) * MC_D + lane];
@@ -663,18 +516,6 @@ __global__ __launch_bounds__(256) void mc_items_kernel(
     for (int k = 0; k < MC_K; ++k)
       if (lane == k) mine = (((bsum[0][k][it] + bsum[1][k][it]) + bsum[2][k][it]) + bsum[3][k][it]) - gB * hk[k];
     if (lane < MC_K) d_cates[i * MC_K + lane] = mine;
-  }
-}
-
-// scores[u - u0, i] = mask for the history entries of users u0 .. u1 (Model/MacridVAE.py:180-182): one wave per user
-__global__ __launch_bounds__(256) void mc_mask_kernel(float *__restrict__ scores, int64_t u0, int64_t u1, int64_t I,
-                                                      const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, float mask) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = u0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= u1) return;
-  for (int64_t e = rowptr[u] + lane; e < rowptr[u + 1]; e += 64) {
-    const int64_t i = col[e];
-    if (i >= 0 && i < I) scores[(u - u0) * I + i] = mask;
   }
 }
 
@@ -775,18 +616,6 @@ __global__ __launch_bounds__(256) void mc_topk_kernel(const float *__restrict__ 
   }
 }
 
-static void mc_plan(int64_t B, int64_t I, int64_t &splits, int64_t &tiles_per_split) {
-  const int64_t n_tiles = (I + MC_TI - 1) / MC_TI, sblocks = (B + MC_SB - 1) / MC_SB;
-  int64_t want = (1024 + sblocks * MC_K - 1) / (sblocks * MC_K);      // ~4 workgroups per CU over (sample blocks, k, splits)
-  if (want > 64) want = 64;
-  if (want > n_tiles) want = n_tiles;
-  if (want < 1) want = 1;
-  tiles_per_split = (n_tiles + want - 1) / want;
-  if (tiles_per_split < 1) tiles_per_split = 1;
-  splits = (n_tiles + tiles_per_split - 1) / tiles_per_split;
-  if (splits < 1) splits = 1;
-}
-
 static int mc_shape(const char *what, int32_t D, int32_t K, int32_t H) {
   if (D != MC_D || K != MC_K || H != MC_H)
     return fail(CHAOREC_E_INVALID, "%s: D=%d K=%d H=%d, the kernels tile D=%d K=%d H=%d", what, (int)D, (int)K, (int)H, MC_D, MC_K, MC_H);
@@ -800,7 +629,7 @@ using namespace chaorec;
 extern "C" int64_t chaorec_macrid_mix_splits(int64_t B, int64_t I) {
   if (B <= 0 || I <= 0) return 1;
   int64_t s, tp;
-  mc_plan(B, I, s, tp);
+  vae_split_plan(B, I, MC_K, s, tp);
   return s;
 }
 
@@ -815,8 +644,9 @@ extern "C" int chaorec_macrid_tick(int64_t *state, float *anneal, float anneal_c
 extern "C" int chaorec_macrid_normal_f32(float *out, int64_t n, const int64_t *state, uint64_t seed, float std, void *stream) {
   if (!out || !state) return fail(CHAOREC_E_INVALID, "macrid_normal: NULL argument");
   if (n <= 0) return fail(CHAOREC_E_INVALID, "macrid_normal: n=%lld", (long long)n);
-  hipLaunchKernelGGL(mc_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n, seed, state, std);
-  return check_launch("mc_normal_kernel");
+  hipLaunchKernelGGL((vae_normal_kernel<MC_BITS, MC_SALT_EPS>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n,
+                     seed, state, std);
+  return check_launch("vae_normal_kernel");
 }
 
 extern "C" int chaorec_macrid_concept_fwd_f32(const float *item_emb, const float *k_emb, int64_t I, int32_t D, int32_t K, float tau,
@@ -905,11 +735,11 @@ extern "C" int chaorec_macrid_mix_fwd_f32(const int64_t *users, int64_t B, int64
   if (rc) return rc;
   if (B <= 0 || U <= 0 || I <= 0 || !(tau > 0.f)) return fail(CHAOREC_E_INVALID, "macrid_mix_fwd: B=%lld U=%lld I=%lld tau=%g", (long long)B, (long long)U, (long long)I, tau);
   int64_t s, tp;
-  mc_plan(B, I, s, tp);
+  vae_split_plan(B, I, MC_K, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "macrid_mix_fwd: splits %lld, chaorec_macrid_mix_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
   const float inv_tau = (float)(1.0 / (double)tau);
-  const dim3 grid((unsigned)((B + MC_SB - 1) / MC_SB), (unsigned)s, MC_K);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s, MC_K);
   hipLaunchKernelGGL((mc_rows_kernel<false>), grid, dim3(256), 0, st, zh, items, cates, B, I, tp, inv_tau, ps, (const float *)nullptr,
                      (const float *)nullptr, (float *)nullptr);
   rc = check_launch("mc_rows_kernel<lse>");
@@ -918,8 +748,8 @@ extern "C" int chaorec_macrid_mix_fwd_f32(const int64_t *users, int64_t B, int64
                      (const float *)ps, s * MC_K, lse, coef, nll);
   rc = check_launch("mc_lse_finish_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(mc_sum_kernel, dim3(1), dim3(256), 0, st, (const float *)nll, B, 1.0f / (float)B, ce);
-  return check_launch("mc_sum_kernel");
+  hipLaunchKernelGGL(vae_sum_kernel<>, dim3(1), dim3(256), 0, st, (const float *)nll, B, 1.0f / (float)B, ce, 0);
+  return check_launch("vae_sum_kernel");
 }
 
 extern "C" int chaorec_macrid_mix_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
@@ -934,11 +764,11 @@ extern "C" int chaorec_macrid_mix_bwd_f32(const int64_t *users, int64_t B, int64
   if (rc) return rc;
   if (B <= 0 || U <= 0 || I <= 0 || !(tau > 0.f)) return fail(CHAOREC_E_INVALID, "macrid_mix_bwd: B=%lld U=%lld I=%lld tau=%g", (long long)B, (long long)U, (long long)I, tau);
   int64_t s, tp;
-  mc_plan(B, I, s, tp);
+  vae_split_plan(B, I, MC_K, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "macrid_mix_bwd: splits %lld, chaorec_macrid_mix_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
   const float inv_tau = (float)(1.0 / (double)tau);
-  const dim3 grid((unsigned)((B + MC_SB - 1) / MC_SB), (unsigned)s, MC_K);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s, MC_K);
   hipLaunchKernelGGL((mc_rows_kernel<true>), grid, dim3(256), 0, st, zh, items, cates, B, I, tp, inv_tau, (float *)nullptr, coef, gce, dzp);
   rc = check_launch("mc_rows_kernel<dz>");
   if (rc) return rc;
@@ -946,7 +776,7 @@ extern "C" int chaorec_macrid_mix_bwd_f32(const int64_t *users, int64_t B, int64
                      (const float *)dzp, (int)s, gce, d_zh);
   rc = check_launch("mc_dz_finish_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL((mc_items_kernel<false>), dim3((unsigned)((I + MC_TW - 1) / MC_TW)), dim3(256), 0, st, zh, items, cates, B, I, inv_tau,
+  hipLaunchKernelGGL((mc_items_kernel<false>), dim3((unsigned)((I + VAE_TW - 1) / VAE_TW)), dim3(256), 0, st, zh, items, cates, B, I, inv_tau,
                      coef, gce, item_ptr, item_users, slot_ptr, perm, d_items, d_cates, (float *)nullptr);
   return check_launch("mc_items_kernel<grad>");
 }
@@ -963,14 +793,14 @@ extern "C" int chaorec_macrid_scores_f32(const float *zh, int64_t n_users, const
   if (scores_bytes < need || need > (size_t)CHAOREC_MACRID_STAGING_BYTES)
     return fail(CHAOREC_E_WORKSPACE, "macrid_scores: staging of %zu bytes (given %zu, cap %zu)", need, scores_bytes, (size_t)CHAOREC_MACRID_STAGING_BYTES);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((mc_items_kernel<true>), dim3((unsigned)((I + MC_TW - 1) / MC_TW)), dim3(256), 0, st, zh, items, cates, n_users, I,
+  hipLaunchKernelGGL((mc_items_kernel<true>), dim3((unsigned)((I + VAE_TW - 1) / VAE_TW)), dim3(256), 0, st, zh, items, cates, n_users, I,
                      (float)(1.0 / (double)tau), (const float *)nullptr, (const float *)nullptr, (const int64_t *)nullptr,
                      (const int32_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, (float *)nullptr, (float *)nullptr, scores);
   rc = check_launch("mc_items_kernel<scores>");
   if (rc) return rc;
-  hipLaunchKernelGGL(mc_mask_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, scores, user_begin, user_begin + n_users, I,
+  hipLaunchKernelGGL(vae_mask_kernel<>, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, scores, user_begin, user_begin + n_users, I,
                      hist_rowptr, hist_col, mask_value);
-  return check_launch("mc_mask_kernel");
+  return check_launch("vae_mask_kernel");
 }
 
 extern "C" int chaorec_macrid_topk_f32(const float *scores, int64_t n_rows, int64_t I, int32_t topk, int64_t id_offset, int64_t *idx,

@@ -15,51 +15,18 @@
 // Layouts: Wq_t [I, 128] row-major (the reference's layers_q.0.weight [128, I] is its transposed view), Wp [I, 64],
 // z [B, 64], h = [mu | logvar] [B, 128].  The latent width is 64 whatever dim_E says (p_dims = [64], :38).
 #include "common.h"
+#include "vae_common.h"
 
 namespace chaorec {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int MV_D = 64;          // latent width
 constexpr int MV_H = 2 * MV_D;    // encoder output [mu | logvar]
-constexpr int MV_SB = 128;        // samples per workgroup (4 waves x 32)
-constexpr int MV_TI = 128;        // items per tile of the sample-owned passes
-constexpr int MV_TW = 64;         // items per workgroup of the item-owned pass
+static_assert(MV_D == VAE_D, "the staging helpers move rows of the latent width");
 constexpr uint64_t MV_SALT_KEEP = 0x6D756C7476616531ull, MV_SALT_EPS = 0x6D756C7476616532ull;
 
-// row of a 32x32 MFMA accumulator register (C/D layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
-__device__ __forceinline__ int mv_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-// counter RNG (seed, step, a, b) -> uniform in (0, 1): a draw depends on its counters only, so a replayed graph whose
-// step counter moved draws fresh values and the backward redraws the forward's
-__device__ __forceinline__ uint64_t mv_key(uint64_t seed, uint64_t step, uint64_t salt) { return mix64(mix64(seed ^ salt) + step); }
-__device__ __forceinline__ float mv_uniform(uint64_t key, uint64_t a, uint64_t b) {
-  const uint64_t r = mix64(key ^ mix64((a << 32) ^ b));
-  return ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ float mv_normal(uint64_t key, uint64_t a, uint64_t c) {   // Box-Muller
-  const float u1 = mv_uniform(key, a, 2 * c), u2 = mv_uniform(key, a, 2 * c + 1);
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
-
-// F.normalize's 1 / max(|x|, 1e-12) of a multi-hot row with n ones, times dropout's 1 / keep_prob in training
-__device__ __forceinline__ float mv_row_scale(int64_t n, int training, float keep_prob) {
-  const float s = 1.0f / fmaxf(sqrtf((float)n), 1e-12f);
-  return training ? s / keep_prob : s;
-}
-
-struct MvKeep {   // is entry j of sample b's history row kept?  given flags (parity tests) or the counter RNG
-  const uint8_t *keep;
-  const int64_t *keep_off;
-  uint64_t key;
-  float keep_prob;
-  int training;
-  __device__ __forceinline__ bool operator()(int64_t b, int64_t j) const {
-    if (!training) return true;
-    if (keep) return keep[keep_off[b] + j] != 0;
-    return mv_uniform(key, (uint64_t)b, (uint64_t)j) < keep_prob;
-  }
-};
+// the uniform keeps 24 bits here (MacridVAE's keeps 23): the streams the goldens were drawn from
+constexpr int MV_BITS = 24;
+using MvKeep = VaeKeep<MV_BITS>;
 
 // state[0] = update_count (Model/MultVAE.py:29,162), state[1] = the count this step reads; anneal of :145-148
 __global__ void mv_tick_kernel(int64_t *state, float *anneal, float cap, int64_t total) {
@@ -67,24 +34,7 @@ __global__ void mv_tick_kernel(int64_t *state, float *anneal, float cap, int64_t
   const int64_t c = state[0];
   state[1] = c;
   state[0] = c + 1;
-  const double a = total > 0 ? (double)c / (double)total : (double)cap;
-  anneal[0] = (float)(a < (double)cap ? a : (double)cap);
-}
-
-// out[0] = sum(in[0..n)) * scale, one workgroup, fixed order, summed in double (the result is one fp32 rounding away
-// from the exact sum of its fp32 terms: the loss parts are compared at a few ulp)
-__global__ __launch_bounds__(256) void mv_sum_kernel(const float *__restrict__ in, int64_t n, float scale, float *__restrict__ out,
-                                                     int accumulate) {
-  __shared__ double red[256];
-  double v = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) v += (double)in[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)((accumulate ? (double)out[0] : 0.0) + red[0] * (double)scale);
+  anneal[0] = vae_anneal(c, total, cap);
 }
 
 // partial[g] = sum of squares of chunk g (Model/MultVAE.py:127-136, torch.norm(p) ** 2 per parameter)
@@ -113,11 +63,9 @@ __global__ __launch_bounds__(256) void mv_encode_fwd_kernel(
   const int lane = threadIdx.x & 63, half = lane >> 5, c4 = (lane & 31) * 4;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   const uint64_t step = (uint64_t)state[1];
-  kf.key = mv_key(seed, step, MV_SALT_KEEP);
+  kf.key = vae_key(seed, step, MV_SALT_KEEP);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t j = half; j < n; j += 8) {      // four gathers in flight per half-wave
     float4 w[4];
@@ -136,19 +84,19 @@ __global__ __launch_bounds__(256) void mv_encode_fwd_kernel(
   acc.y += __shfl_xor(acc.y, 32, 64);
   acc.z += __shfl_xor(acc.z, 32, 64);
   acc.w += __shfl_xor(acc.w, 32, 64);
-  const float sc = mv_row_scale(n, kf.training, kf.keep_prob);
+  const float sc = vae_row_scale(n, kf.training, kf.keep_prob);
   const float4 bias = *reinterpret_cast<const float4 *>(bq + c4);
   float hv[4] = {bias.x + sc * acc.x, bias.y + sc * acc.y, bias.z + sc * acc.z, bias.w + sc * acc.w};
   if (half == 0) *reinterpret_cast<float4 *>(h_out + b * MV_H + c4) = make_float4(hv[0], hv[1], hv[2], hv[3]);
   // epilogue (Model/MultVAE.py:87-91, :113-114): lanes 0-15 hold mu, lanes 16-31 the logvar of the same columns
-  const uint64_t ekey = mv_key(seed, step, MV_SALT_EPS);
+  const uint64_t ekey = vae_key(seed, step, MV_SALT_EPS);
   double kl = 0.0;
   float zv[4], ev[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float lv = __shfl(hv[q], (lane & 15) + 16, 64), mu = hv[q];
     const int c = c4 + q;                              // (a column of z for lanes 0-15)
-    const float e = (lane < 16) ? (eps_in ? eps_in[b * MV_D + c] : mv_normal(ekey, (uint64_t)b, (uint64_t)c)) : 0.f;
+    const float e = (lane < 16) ? (eps_in ? eps_in[b * MV_D + c] : vae_normal<MV_BITS>(ekey, (uint64_t)b, (uint64_t)c)) : 0.f;
     ev[q] = e;
     zv[q] = mu + e * expf(0.5f * lv);
     kl += (double)(0.5f * (-lv + expf(lv) + mu * mu - 1.0f));
@@ -173,8 +121,7 @@ __global__ __launch_bounds__(MV_H) void mv_encode_dh_kernel(
   for (int q = 0; q < 64; ++q) {
     const int64_t b = (int64_t)blockIdx.x * 64 + q;
     if (b >= B) break;
-    const int64_t u = users[b];
-    const int64_t n = (u >= 0 && u < U) ? rowptr[u + 1] - rowptr[u] : 0;
+    const int64_t n = vae_hist_row(rowptr, users[b], U).n;
     const float hv = h[b * MV_H + c];
     float d;
     if (c < MV_D) {
@@ -183,7 +130,7 @@ __global__ __launch_bounds__(MV_H) void mv_encode_dh_kernel(
       const float e = eps[b * MV_D + c - MV_D];
       d = gz[b * MV_D + c - MV_D] * e * expf(0.5f * hv) * 0.5f + gk * 0.5f * (expf(hv) - 1.0f);
     }
-    sdh[b * MV_H + c] = mv_row_scale(n, training, keep_prob) * d;
+    sdh[b * MV_H + c] = vae_row_scale(n, training, keep_prob) * d;
     colsum += d;
   }
   partial[(int64_t)blockIdx.x * MV_H + c] = colsum;
@@ -198,35 +145,6 @@ __global__ __launch_bounds__(MV_H) void mv_encode_dbias_kernel(const float *__re
   dbq[c] = v + 2.0f * gsq[0] * bq[c];
 }
 
-// The owner walk both weight gradients share: item i's users (item-major CSR, ascending), per user the sample slots
-// perm[slot_ptr[u] .. slot_ptr[u + 1]) (ascending sample number: a stable sort of the batch).  64 lanes scan 64 users
-// at a time; the users that are in the batch are then taken one by one, in order, by the whole wave (f(slot, pos)).
-template <class F>
-__device__ __forceinline__ void mv_item_walk(int64_t i, const int64_t *__restrict__ item_ptr, const int32_t *__restrict__ item_users,
-                                             const int32_t *__restrict__ item_pos, const int64_t *__restrict__ slot_ptr,
-                                             const int64_t *__restrict__ perm, int lane, F f) {
-  const int64_t beg = item_ptr[i], end = item_ptr[i + 1];
-  for (int64_t e0 = beg; e0 < end; e0 += 64) {
-    const int64_t e = e0 + lane;
-    int64_t lo = 0, hi = 0;
-    int pos = 0;
-    if (e < end) {
-      const int64_t u = item_users[e];
-      lo = slot_ptr[u];
-      hi = slot_ptr[u + 1];
-      pos = item_pos ? item_pos[e] : 0;
-    }
-    unsigned long long mask = __ballot(hi > lo);
-    while (mask) {
-      const int src = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int64_t lo_s = __shfl(lo, src, 64), hi_s = __shfl(hi, src, 64);
-      const int pos_s = __shfl(pos, src, 64);
-      for (int64_t q = lo_s; q < hi_s; ++q) f(perm[q], pos_s);
-    }
-  }
-}
-
 // encoder backward, part 2: dWq_t[i, :] = sum over kept (sample, i) of sdh[sample] + 2 gsq Wq_t[i, :]; one wave per item
 __global__ __launch_bounds__(256) void mv_encode_dw_kernel(
     int64_t I, const int64_t *__restrict__ item_ptr, const int32_t *__restrict__ item_users, const int32_t *__restrict__ item_pos,
@@ -235,9 +153,9 @@ __global__ __launch_bounds__(256) void mv_encode_dw_kernel(
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= I) return;
-  kf.key = mv_key(seed, (uint64_t)state[1], MV_SALT_KEEP);
+  kf.key = vae_key(seed, (uint64_t)state[1], MV_SALT_KEEP);
   float2 acc = make_float2(0.f, 0.f);
-  mv_item_walk(i, item_ptr, item_users, item_pos, slot_ptr, perm, lane, [&](int64_t slot, int pos) {
+  vae_item_walk(i, item_ptr, item_users, item_pos, slot_ptr, perm, lane, [&](int64_t slot, int pos) {
     if (kf(slot, pos)) {
       const float2 g = *reinterpret_cast<const float2 *>(sdh + slot * MV_H + 2 * lane);
       acc.x += g.x;
@@ -261,13 +179,13 @@ __global__ __launch_bounds__(256) void mv_decode_rows_kernel(
     const float *__restrict__ z, const float *__restrict__ Wp, const float *__restrict__ bp, int64_t B, int64_t I,
     int64_t tiles_per_split, float *__restrict__ pm, float *__restrict__ ps, const float *__restrict__ lse2,
     const float *__restrict__ cnt, const float *__restrict__ gnll, float *__restrict__ dzp) {
-  constexpr int LD = MV_TI + 1;
+  constexpr int LD = VAE_TI + 1;
   __shared__ float Ws[MV_D][LD];      // [k][item]: A operand of the logits (k-major), A operand of dz^T (d-major)
-  __shared__ float bs[MV_TI];
+  __shared__ float bs[VAE_TI];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-  const int64_t b = (int64_t)blockIdx.x * MV_SB + wave * 32 + r;
+  const int64_t b = (int64_t)blockIdx.x * VAE_SB + wave * 32 + r;
   const bool live = b < B;
-  const int64_t n_tiles = (I + MV_TI - 1) / MV_TI;
+  const int64_t n_tiles = (I + VAE_TI - 1) / VAE_TI;
   const int64_t t_beg = (int64_t)blockIdx.y * tiles_per_split, t_end = min(n_tiles, t_beg + tiles_per_split);
 
   float bf[MV_D / 2];
@@ -279,38 +197,24 @@ __global__ __launch_bounds__(256) void mv_decode_rows_kernel(
   const float my_m = WITH_DZ ? (live ? lse2[b] : INFINITY) : 0.f;
   const float my_l = WITH_DZ ? (live ? lse2[B + b] : 0.f) : 0.f;
   const float my_coef = WITH_DZ ? (live ? gnll[0] * cnt[b] / (float)B : 0.f) : 0.f;
-  f32x16 dz[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dz[j][q] = 0.f;
+  f32x16 dz[2] = {vae_zero(), vae_zero()};
 
   for (int64_t tile = t_beg; tile < t_end; ++tile) {
-    const int64_t i0 = tile * MV_TI;
+    const int64_t i0 = tile * VAE_TI;
     __syncthreads();                      // the previous tile's readers are done
-#pragma unroll
-    for (int p = 0; p < MV_TI * MV_D / 4 / 256; ++p) {
-      const int v = t + p * 256, item = v >> 4, k4 = (v & 15) * 4;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i0 + item < I) x = *reinterpret_cast<const float4 *>(Wp + (i0 + item) * MV_D + k4);
-      Ws[k4 + 0][item] = x.x;
-      Ws[k4 + 1][item] = x.y;
-      Ws[k4 + 2][item] = x.z;
-      Ws[k4 + 3][item] = x.w;
-    }
-    if (t < MV_TI) bs[t] = (i0 + t < I) ? bp[i0 + t] : -INFINITY;      // a column past the end: logit -inf, P = 0
+    vae_stage_transposed<VAE_TI>(Ws, Wp, i0, I, t);
+    if (t < VAE_TI) bs[t] = (i0 + t < I) ? bp[i0 + t] : -INFINITY;      // a column past the end: logit -inf, P = 0
     __syncthreads();
 
     f32x16 acc[4];
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[jt][q] = 0.f;
+      acc[jt] = vae_zero();
 #pragma unroll
       for (int s = 0; s < MV_D / 2; ++s)
         acc[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[2 * s + h][32 * jt + r], bf[s], acc[jt], 0, 0, 0);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) acc[jt][q] = acc[jt][q] + bs[32 * jt + mv_row(q, h)];
+      for (int q = 0; q < 16; ++q) acc[jt][q] = acc[jt][q] + bs[32 * jt + vae_row(q, h)];
     }
     if (!WITH_DZ) {
       float tmax = -INFINITY;
@@ -335,7 +239,7 @@ __global__ __launch_bounds__(256) void mv_decode_rows_kernel(
         for (int q = 0; q < 16; ++q) acc[jt][q] = my_coef * expf((acc[jt][q] - my_m) - my_l);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int item = 32 * jt + mv_row(q, h);
+          const int item = 32 * jt + vae_row(q, h);
 #pragma unroll
           for (int j = 0; j < 2; ++j)
             dz[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[32 * j + r][item], acc[jt][q], dz[j], 0, 0, 0);
@@ -356,13 +260,7 @@ __global__ __launch_bounds__(256) void mv_decode_rows_kernel(
       ps[(int64_t)blockIdx.y * B + b] = S;
     }
   } else if (live) {
-    float *out = dzp + ((int64_t)blockIdx.y * B + b) * MV_D;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)     // registers 4g .. 4g+3: d = 32 j + 8 g + 4 h + (0..3)
-        *reinterpret_cast<float4 *>(out + 32 * j + 8 * g + 4 * h) =
-            make_float4(dz[j][4 * g + 0], dz[j][4 * g + 1], dz[j][4 * g + 2], dz[j][4 * g + 3]);
+    vae_store_dz(dzp + ((int64_t)blockIdx.y * B + b) * MV_D, dz, h);
   }
 }
 
@@ -392,9 +290,7 @@ __global__ __launch_bounds__(64) void mv_decode_lse_finish_kernel(
   const float S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
   const double l = (double)M + log((double)S);
   __syncthreads();
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   double part = 0.0;
   for (int64_t j = lane; j < n; j += 64) {
     const int64_t i = col[beg + j];
@@ -429,9 +325,7 @@ __global__ __launch_bounds__(64) void mv_decode_dz_finish_kernel(
   const int64_t b = blockIdx.x;
   float v = 0.f;
   for (int sp = 0; sp < splits; ++sp) v += dzp[((int64_t)sp * B + b) * MV_D + d];
-  const int64_t u = users[b];
-  const bool ok = u >= 0 && u < U;
-  const int64_t beg = ok ? rowptr[u] : 0, n = ok ? rowptr[u + 1] - beg : 0;
+  const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   float x = 0.f;
   for (int64_t j = 0; j < n; ++j) x += Wp[(int64_t)col[beg + j] * MV_D + d];
   dz[b * MV_D + d] = v - (gnll[0] / (float)B) * x;
@@ -449,48 +343,24 @@ __global__ __launch_bounds__(256) void mv_decode_dw_kernel(
     const int64_t *__restrict__ item_ptr, const int32_t *__restrict__ item_users, const int64_t *__restrict__ slot_ptr,
     const int64_t *__restrict__ perm, float *__restrict__ dWp, float *__restrict__ dbp) {
   constexpr int LD = MV_D + 1;
-  __shared__ float Ws[MV_D][MV_TW + 1];    // [k][item]
-  __shared__ float Zs[MV_SB][LD];          // [sample][k]
+  __shared__ float Ws[MV_D][VAE_TW + 1];    // [k][item]
+  __shared__ float Zs[VAE_SB][LD];          // [sample][k]
   float (*Rs)[LD] = reinterpret_cast<float (*)[LD]>(&Zs[0][0]);   // [item][d]: the waves' sums, once Zs is done with
-  __shared__ float lsem[MV_SB], lsel[MV_SB], coefs[MV_SB], bsum[4][MV_TW];
+  __shared__ float lsem[VAE_SB], lsel[VAE_SB], coefs[VAE_SB], bsum[4][VAE_TW];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-  const int64_t i0 = (int64_t)blockIdx.x * MV_TW;
+  const int64_t i0 = (int64_t)blockIdx.x * VAE_TW;
   const float g = gnll[0];
-#pragma unroll
-  for (int p = 0; p < MV_TW * MV_D / 4 / 256; ++p) {
-    const int v = t + p * 256, item = v >> 4, k4 = (v & 15) * 4;
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i0 + item < I) x = *reinterpret_cast<const float4 *>(Wp + (i0 + item) * MV_D + k4);
-    Ws[k4 + 0][item] = x.x;
-    Ws[k4 + 1][item] = x.y;
-    Ws[k4 + 2][item] = x.z;
-    Ws[k4 + 3][item] = x.w;
-  }
+  vae_stage_transposed<VAE_TW>(Ws, Wp, i0, I, t);
   float bias[2];
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt) bias[jt] = (i0 + 32 * jt + r < I) ? bp[i0 + 32 * jt + r] : -INFINITY;
-  f32x16 dw[2][2];
+  f32x16 dw[2][2] = {{vae_zero(), vae_zero()}, {vae_zero(), vae_zero()}};
   float bacc[2] = {0.f, 0.f};
-#pragma unroll
-  for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) dw[jt][j][q] = 0.f;
 
-  for (int64_t s0 = 0; s0 < B; s0 += MV_SB) {
+  for (int64_t s0 = 0; s0 < B; s0 += VAE_SB) {
     __syncthreads();
-#pragma unroll
-    for (int p = 0; p < MV_SB * MV_D / 4 / 256; ++p) {
-      const int v = t + p * 256, row = v >> 4, k4 = (v & 15) * 4;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (s0 + row < B) x = *reinterpret_cast<const float4 *>(z + (s0 + row) * MV_D + k4);
-      Zs[row][k4 + 0] = x.x;
-      Zs[row][k4 + 1] = x.y;
-      Zs[row][k4 + 2] = x.z;
-      Zs[row][k4 + 3] = x.w;
-    }
-    if (t < MV_SB) {
+    vae_stage_rows(Zs, z, MV_D, s0, B, t);
+    if (t < VAE_SB) {
       const bool live = s0 + t < B;
       lsem[t] = live ? lse2[s0 + t] : INFINITY;           // a sample past the end: P = 0 * exp(-inf) = 0
       lsel[t] = live ? lse2[B + s0 + t] : 0.f;
@@ -500,55 +370,40 @@ __global__ __launch_bounds__(256) void mv_decode_dw_kernel(
     f32x16 acc[2];
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[jt][q] = 0.f;
+      acc[jt] = vae_zero();
 #pragma unroll
       for (int s = 0; s < MV_D / 2; ++s)
         acc[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(Zs[wave * 32 + r][2 * s + h], Ws[2 * s + h][32 * jt + r], acc[jt], 0, 0, 0);
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int sm = wave * 32 + mv_row(q, h);
+        const int sm = wave * 32 + vae_row(q, h);
         const float p = coefs[sm] * expf(((acc[jt][q] + bias[jt]) - lsem[sm]) - lsel[sm]);
         acc[jt][q] = p;
         bacc[jt] += p;
       }
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int sm = wave * 32 + mv_row(q, h);
+        const int sm = wave * 32 + vae_row(q, h);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           dw[jt][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[jt][q], Zs[sm][32 * j + r], dw[jt][j], 0, 0, 0);
       }
     }
   }
-  // waves 0..3 in order; dw[jt][j]: row = item 32 jt + mv_row(reg, h), col = d = 32 j + r
+  // the column sums of P per wave (added at the end, waves 0..3 in order), then the waves' dw the same way
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt) bacc[jt] += __shfl_xor(bacc[jt], 32, 64);
   if (h == 0) {
     bsum[wave][r] = bacc[0];
     bsum[wave][32 + r] = bacc[1];
   }
-  for (int w = 0; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            float *dst = &Rs[32 * jt + mv_row(q, h)][32 * j + r];
-            *dst = (w ? *dst : 0.f) + dw[jt][j][q];
-          }
-    }
-  }
-  __syncthreads();
+  vae_reduce_waves(Rs, dw, wave, r, h);
   const float gB = g / (float)B, reg2 = 2.0f * gsq[0];
-  for (int it = wave; it < MV_TW; it += 4) {
+  for (int it = wave; it < VAE_TW; it += 4) {
     const int64_t i = i0 + it;
     if (i >= I) break;
     float xz = 0.f, hits = 0.f;
-    mv_item_walk(i, item_ptr, item_users, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
+    vae_item_walk(i, item_ptr, item_users, (const int32_t *)nullptr, slot_ptr, perm, lane, [&](int64_t slot, int) {
       xz += z[slot * MV_D + lane];
       hits += 1.0f;
     });
@@ -558,18 +413,6 @@ __global__ __launch_bounds__(256) void mv_decode_dw_kernel(
   }
 }
 
-static void mv_plan(int64_t B, int64_t I, int64_t &splits, int64_t &tiles_per_split) {
-  const int64_t n_tiles = (I + MV_TI - 1) / MV_TI, sblocks = (B + MV_SB - 1) / MV_SB;
-  int64_t want = (1024 + sblocks - 1) / sblocks;      // ~4 workgroups per CU
-  if (want > 64) want = 64;
-  if (want > n_tiles) want = n_tiles;
-  if (want < 1) want = 1;
-  tiles_per_split = (n_tiles + want - 1) / want;
-  if (tiles_per_split < 1) tiles_per_split = 1;
-  splits = (n_tiles + tiles_per_split - 1) / tiles_per_split;       // no empty split
-  if (splits < 1) splits = 1;
-}
-
 }  // namespace chaorec
 
 using namespace chaorec;
@@ -577,7 +420,7 @@ using namespace chaorec;
 extern "C" int64_t chaorec_multvae_decode_splits(int64_t B, int64_t I) {
   if (B <= 0 || I <= 0) return 1;
   int64_t s, tp;
-  mv_plan(B, I, s, tp);
+  vae_split_plan(B, I, 1, s, tp);
   return s;
 }
 
@@ -595,8 +438,8 @@ extern "C" int chaorec_multvae_sumsq_f32(const float *x, int64_t n, float *parti
   hipLaunchKernelGGL(mv_sumsq_kernel, dim3((unsigned)n_partial), dim3(256), 0, (hipStream_t)stream, x, n, chunk, partial);
   int rc = check_launch("mv_sumsq_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(mv_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)partial, n_partial, 1.0f, out, (int)accumulate);
-  return check_launch("mv_sum_kernel");
+  hipLaunchKernelGGL(vae_sum_kernel<>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)partial, n_partial, 1.0f, out, (int)accumulate);
+  return check_launch("vae_sum_kernel");
 }
 
 extern "C" int chaorec_multvae_encode_fwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
@@ -615,8 +458,8 @@ extern "C" int chaorec_multvae_encode_fwd_f32(const int64_t *users, int64_t B, i
                      seed, state, eps_in, h, z, eps_out, klrow);
   int rc = check_launch("mv_encode_fwd_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(mv_sum_kernel, dim3(1), dim3(256), 0, st, (const float *)klrow, B, 1.0f / (float)B, kl, 0);
-  return check_launch("mv_sum_kernel");
+  hipLaunchKernelGGL(vae_sum_kernel<>, dim3(1), dim3(256), 0, st, (const float *)klrow, B, 1.0f / (float)B, kl, 0);
+  return check_launch("vae_sum_kernel");
 }
 
 extern "C" int chaorec_multvae_encode_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, int64_t I,
@@ -654,10 +497,10 @@ extern "C" int chaorec_multvae_decode_fwd_f32(const int64_t *users, int64_t B, i
     return fail(CHAOREC_E_INVALID, "multvae_decode_fwd: NULL argument");
   if (B <= 0 || U <= 0 || I <= 0) return fail(CHAOREC_E_INVALID, "multvae_decode_fwd: B=%lld U=%lld I=%lld", (long long)B, (long long)U, (long long)I);
   int64_t s, tp;
-  mv_plan(B, I, s, tp);
+  vae_split_plan(B, I, 1, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "multvae_decode_fwd: splits %lld, chaorec_multvae_decode_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((B + MV_SB - 1) / MV_SB), (unsigned)s);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s);
   hipLaunchKernelGGL((mv_decode_rows_kernel<false>), grid, dim3(256), 0, st, z, Wp, bp, B, I, tp, pm, ps, (const float *)nullptr,
                      (const float *)nullptr, (const float *)nullptr, (float *)nullptr);
   int rc = check_launch("mv_decode_rows_kernel<lse>");
@@ -666,8 +509,8 @@ extern "C" int chaorec_multvae_decode_fwd_f32(const int64_t *users, int64_t B, i
                      (const float *)pm, (const float *)ps, (int)s, lse, lse2, cnt, nll);
   rc = check_launch("mv_decode_lse_finish_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(mv_sum_kernel, dim3(1), dim3(256), 0, st, (const float *)nll, B, 1.0f / (float)B, neg_ll, 0);
-  return check_launch("mv_sum_kernel");
+  hipLaunchKernelGGL(vae_sum_kernel<>, dim3(1), dim3(256), 0, st, (const float *)nll, B, 1.0f / (float)B, neg_ll, 0);
+  return check_launch("vae_sum_kernel");
 }
 
 extern "C" int chaorec_multvae_decode_bwd_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
@@ -680,10 +523,10 @@ extern "C" int chaorec_multvae_decode_bwd_f32(const int64_t *users, int64_t B, i
     return fail(CHAOREC_E_INVALID, "multvae_decode_bwd: NULL argument");
   if (B <= 0 || U <= 0 || I <= 0) return fail(CHAOREC_E_INVALID, "multvae_decode_bwd: B=%lld U=%lld I=%lld", (long long)B, (long long)U, (long long)I);
   int64_t s, tp;
-  mv_plan(B, I, s, tp);
+  vae_split_plan(B, I, 1, s, tp);
   if (splits != s) return fail(CHAOREC_E_WORKSPACE, "multvae_decode_bwd: splits %lld, chaorec_multvae_decode_splits says %lld", (long long)splits, (long long)s);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((B + MV_SB - 1) / MV_SB), (unsigned)s);
+  const dim3 grid((unsigned)((B + VAE_SB - 1) / VAE_SB), (unsigned)s);
   hipLaunchKernelGGL((mv_decode_rows_kernel<true>), grid, dim3(256), 0, st, z, Wp, bp, B, I, tp, (float *)nullptr, (float *)nullptr,
                      lse2, cnt, gnll, dzp);
   int rc = check_launch("mv_decode_rows_kernel<dz>");
@@ -692,7 +535,7 @@ extern "C" int chaorec_multvae_decode_bwd_f32(const int64_t *users, int64_t B, i
                      (int)s, gnll, dz);
   rc = check_launch("mv_decode_dz_finish_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(mv_decode_dw_kernel, dim3((unsigned)((I + MV_TW - 1) / MV_TW)), dim3(256), 0, st, z, Wp, bp, B, I, lse2, cnt, gnll,
+  hipLaunchKernelGGL(mv_decode_dw_kernel, dim3((unsigned)((I + VAE_TW - 1) / VAE_TW)), dim3(256), 0, st, z, Wp, bp, B, I, lse2, cnt, gnll,
                      gsq, item_ptr, item_users, slot_ptr, perm, dWp, dbp);
   return check_launch("mv_decode_dw_kernel");
 }

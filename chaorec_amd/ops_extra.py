@@ -515,13 +515,12 @@ def dgcf_cor_loss(table, idx, K):
 
 
 # --------------------------------------------------------------------------------------------
-# MultVAE (csrc/multvae.hip): history-row encoder, all-items multinomial likelihood without [B, I]
+# The autoencoders (csrc/multvae.hip, macridvae.hip, dualvae.hip over csrc/vae_common.h): what the three share
 # --------------------------------------------------------------------------------------------
-MULTVAE_LATENT = 64      # p_dims = [64] (Model/MultVAE.py:38): the width the kernels tile
-
-
+# MultVAEStructure has three users: MultVAE and MacridVAE walk the user-history CSR with it, DualVAE builds one per side
+# (rows = that side's samples, columns = the other side's table rows).  It keeps the name of its first user.
 class MultVAEStructure:
-    """What the MultVAE kernels walk: the user-history CSR (rowptr int64 [U + 1], col int32 local item ids, ascending)
+    """What the autoencoder kernels walk: the user-history CSR (rowptr int64 [U + 1], col int32 local item ids, ascending)
     and its item-major transpose with every entry's place in its user's row (graph.item_major_hist)."""
 
     def __init__(self, rowptr, col, num_item):
@@ -549,6 +548,24 @@ class MultVAEStructure:
         return (torch.cumsum(n, 0) - n).contiguous()
 
 
+def _vae_f32(model, t, what, shape=None):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{model}: {what} must be a contiguous float32 tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{model}: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _range_users(staging_bytes, num_item):
+    return max(1, staging_bytes // (int(num_item) * 4))
+
+
+# --------------------------------------------------------------------------------------------
+# MultVAE (csrc/multvae.hip): history-row encoder, all-items multinomial likelihood without [B, I]
+# --------------------------------------------------------------------------------------------
+MULTVAE_LATENT = 64      # p_dims = [64] (Model/MultVAE.py:38): the width the kernels tile
+
+
 def multvae_tick(state, anneal, cap, total_steps):
     """state[1] = state[0] (the update_count this step reads), state[0] += 1, anneal[0] = min(cap, state[1] / total)."""
     _need_cuda(state, anneal)
@@ -563,12 +580,6 @@ def _multvae_sumsq(tensors, out):
         lib.chaorec_multvae_sumsq_f32(_ptr(t), t.numel(), _ptr(partial), n_partial, _ptr(out), 1 if k else 0, _stream())
 
 
-def _dense_f32(t, what):
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"multvae: {what} must be a contiguous float32 tensor")
-    return t
-
-
 class _MultVAEEncode(torch.autograd.Function):
     """(Wq_t [I, 128], bq [128]) -> z [B, 64], kl [1], sum ||Wq||^2 + ||bq||^2 [1] (Model/MultVAE.py:75-93, :113-114)."""
 
@@ -576,12 +587,12 @@ class _MultVAEEncode(torch.autograd.Function):
     def forward(ctx, Wq_t, bq, s, batch, state, seed, training, keep_prob, keep, keep_off, eps):
         users, slot_ptr, perm = batch
         _need_cuda(Wq_t, bq, users, s.rowptr, state, keep, keep_off, eps)
-        Wq_t, bq = _dense_f32(Wq_t, "Wq_t"), _dense_f32(bq, "bq")
+        Wq_t, bq = _vae_f32("multvae", Wq_t, "Wq_t"), _vae_f32("multvae", bq, "bq")
         B, dev = users.numel(), Wq_t.device
         if Wq_t.shape != (s.num_item, 2 * MULTVAE_LATENT):
             raise ValueError(f"multvae: Wq_t is {tuple(Wq_t.shape)}, the kernels tile [{s.num_item}, {2 * MULTVAE_LATENT}]")
         if eps is not None:
-            eps = _dense_f32(eps, "eps")
+            eps = _vae_f32("multvae", eps, "eps")
             if eps.shape != (B, MULTVAE_LATENT):
                 raise ValueError("multvae: eps must be [B, 64]")
         if keep is not None:
@@ -629,7 +640,7 @@ class _MultVAEDecode(torch.autograd.Function):
     def forward(ctx, z, Wp, bp, s, batch):
         users, slot_ptr, perm = batch
         _need_cuda(z, Wp, bp, users)
-        z, Wp, bp = _dense_f32(z, "z"), _dense_f32(Wp, "Wp"), _dense_f32(bp, "bp")
+        z, Wp, bp = _vae_f32("multvae", z, "z"), _vae_f32("multvae", Wp, "Wp"), _vae_f32("multvae", bp, "bp")
         B, I, dev = users.numel(), s.num_item, z.device
         if Wp.shape != (I, MULTVAE_LATENT) or z.shape != (B, MULTVAE_LATENT) or bp.shape != (I,):
             raise ValueError(f"multvae: decoder shapes z {tuple(z.shape)}, Wp {tuple(Wp.shape)}, bp {tuple(bp.shape)}; "
@@ -693,24 +704,18 @@ def macrid_normal(shape, state, seed, std, device):
     return out
 
 
-def _mc_f32(t, what):
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"macrid: {what} must be a contiguous float32 tensor")
-    return t
-
-
 class _MacridConcept(torch.autograd.Function):
     """(item_embedding [I, D], k_embedding [K, D]) -> items [I, D], cates [I, K] (Model/MacridVAE.py:76-77, :86-94)."""
 
     @staticmethod
     def forward(ctx, E, Kemb, tau, gumbel, state, seed, training):
         _need_cuda(E, Kemb, gumbel, state)
-        E, Kemb = _mc_f32(E, "item_embedding"), _mc_f32(Kemb, "k_embedding")
+        E, Kemb = _vae_f32("macrid", E, "item_embedding"), _vae_f32("macrid", Kemb, "k_embedding")
         I, D = E.shape
         K = Kemb.shape[0]
         macrid_check_shape(D, K)
         if gumbel is not None:
-            gumbel = _mc_f32(gumbel, "gumbel")
+            gumbel = _vae_f32("macrid", gumbel, "gumbel")
             if gumbel.shape != (I, K):
                 raise ValueError("macrid: gumbel must be [I, K]")
         items, cates = torch.empty_like(E), torch.empty((I, K), dtype=torch.float32, device=E.device)
@@ -745,7 +750,7 @@ class _MacridEncode(torch.autograd.Function):
     def forward(ctx, W1_t, b1, cates, s, batch, state, seed, training, keep_prob, keep, keep_off):
         users, slot_ptr, perm = batch
         _need_cuda(W1_t, b1, cates, users, s.rowptr, state, keep, keep_off)
-        W1_t, b1, cates = _mc_f32(W1_t, "W1_t"), _mc_f32(b1, "b1"), _mc_f32(cates, "cates")
+        W1_t, b1, cates = _vae_f32("macrid", W1_t, "W1_t"), _vae_f32("macrid", b1, "b1"), _vae_f32("macrid", cates, "cates")
         B, dev, K, H = users.numel(), W1_t.device, cates.shape[1], W1_t.shape[1]
         macrid_check_shape(MACRID_D, K, H)
         if W1_t.shape[0] != s.num_item or cates.shape[0] != s.num_item:
@@ -807,7 +812,7 @@ class _MacridMix(torch.autograd.Function):
     def forward(ctx, zh, items, cates, s, batch, tau):
         users, slot_ptr, perm = batch
         _need_cuda(zh, items, cates, users)
-        zh, items, cates = _mc_f32(zh, "zh"), _mc_f32(items, "items"), _mc_f32(cates, "cates")
+        zh, items, cates = _vae_f32("macrid", zh, "zh"), _vae_f32("macrid", items, "items"), _vae_f32("macrid", cates, "cates")
         B, I, dev = users.numel(), s.num_item, zh.device
         K, D = cates.shape[1], items.shape[1]
         macrid_check_shape(D, K)
@@ -846,13 +851,13 @@ def macrid_mix(zh, items, cates, s, batch, tau):
 
 def macrid_range_users(num_item):
     """How many users one ranking range may stage under the cap."""
-    return max(1, MACRID_STAGING_BYTES // (int(num_item) * 4))
+    return _range_users(MACRID_STAGING_BYTES, num_item)
 
 
 def macrid_scores(zh, items, cates, tau, user_begin, hist, mask_value, out=None):
     """log p_ui of the users user_begin .. user_begin + n (zh [n, K, D]) -> [n, I] fp32, their history entries = mask_value."""
     _need_cuda(zh, items, cates, hist[0], hist[1])
-    zh, items, cates = _mc_f32(zh, "zh"), _mc_f32(items, "items"), _mc_f32(cates, "cates")
+    zh, items, cates = _vae_f32("macrid", zh, "zh"), _vae_f32("macrid", items, "items"), _vae_f32("macrid", cates, "cates")
     n, K, D = zh.shape
     I = items.shape[0]
     macrid_check_shape(D, K)
@@ -870,7 +875,7 @@ def macrid_scores(zh, items, cates, tau, user_begin, hist, mask_value, out=None)
 def macrid_topk(scores, topk, id_offset=0):
     """Exact top-k per row of scores [n, I], ties to the lowest index -> (int64 [n, topk] ids + id_offset, fp32 [n, topk])."""
     _need_cuda(scores)
-    scores = _mc_f32(scores, "scores")
+    scores = _vae_f32("macrid", scores, "scores")
     n, I = scores.shape
     if not 1 <= int(topk) <= min(64, I):
         raise ValueError(f"macrid: topk={topk} (1 .. min(64, I={I}))")
@@ -899,14 +904,6 @@ def dualvae_tick(state):
     _lib.load().chaorec_dualvae_tick(_ptr(state), _stream())
 
 
-def _dv_f32(t, what, shape=None):
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"dualvae: {what} must be a contiguous float32 tensor")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"dualvae: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
-    return t
-
-
 class _DualVAEEncode(torch.autograd.Function):
     """(We_t [N, 20], bias [20], w [N, 5]) -> pre [B, 5, 20] = bias + sum over the sample's row of w[n, a] We_t[n, :]."""
 
@@ -915,7 +912,8 @@ class _DualVAEEncode(torch.autograd.Function):
         ids, slot_ptr, perm = batch
         _need_cuda(We_t, bias, w, ids, s.rowptr)
         N = s.num_item
-        We_t, bias, w = _dv_f32(We_t, "We_t", (N, DUALVAE_H)), _dv_f32(bias, "bias", (DUALVAE_H,)), _dv_f32(w, "w", (N, DUALVAE_A))
+        We_t, bias = _vae_f32("dualvae", We_t, "We_t", (N, DUALVAE_H)), _vae_f32("dualvae", bias, "bias", (DUALVAE_H,))
+        w = _vae_f32("dualvae", w, "w", (N, DUALVAE_A))
         B = ids.numel()
         pre = torch.empty((B, DUALVAE_A, DUALVAE_H), dtype=torch.float32, device=We_t.device)
         _lib.load().chaorec_dualvae_encode_fwd_f32(_ptr(ids), B, s.num_user, _ptr(s.rowptr), _ptr(s.col), N, _ptr(We_t), _ptr(bias),
@@ -951,9 +949,9 @@ class _DualVAEDense(torch.autograd.Function):
         ids, slot_ptr, perm = batch
         _need_cuda(z, zh, th, w, table, ids)
         B, N, dev = ids.numel(), s.num_item, z.device
-        z, zh = _dv_f32(z, "z", (B, DUALVAE_A, DUALVAE_K)), _dv_f32(zh, "zh", (B, DUALVAE_A, DUALVAE_H))
-        th, w = _dv_f32(th, "th", (N, DUALVAE_A, DUALVAE_H)), _dv_f32(w, "w", (N, DUALVAE_A))
-        table = _dv_f32(table, "table", (N, DUALVAE_A, DUALVAE_K))
+        z, zh = _vae_f32("dualvae", z, "z", (B, DUALVAE_A, DUALVAE_K)), _vae_f32("dualvae", zh, "zh", (B, DUALVAE_A, DUALVAE_H))
+        th, w = _vae_f32("dualvae", th, "th", (N, DUALVAE_A, DUALVAE_H)), _vae_f32("dualvae", w, "w", (N, DUALVAE_A))
+        table = _vae_f32("dualvae", table, "table", (N, DUALVAE_A, DUALVAE_K))
         lib = _lib.load()
         splits = int(lib.chaorec_dualvae_splits(B, N))
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
@@ -991,16 +989,16 @@ def dualvae_writeback(batch, num_rows, z, mu, table, mu_table):
     ids, slot_ptr, perm = batch
     _need_cuda(ids, z, mu, table, mu_table)
     B = ids.numel()
-    z, mu = _dv_f32(z, "z", (B, DUALVAE_A, DUALVAE_K)), _dv_f32(mu, "mu", (B, DUALVAE_A, DUALVAE_K))
-    _dv_f32(table, "table", (num_rows, DUALVAE_A, DUALVAE_K))
-    _dv_f32(mu_table, "mu_table", (num_rows, DUALVAE_A, DUALVAE_K))
+    z, mu = _vae_f32("dualvae", z, "z", (B, DUALVAE_A, DUALVAE_K)), _vae_f32("dualvae", mu, "mu", (B, DUALVAE_A, DUALVAE_K))
+    _vae_f32("dualvae", table, "table", (num_rows, DUALVAE_A, DUALVAE_K))
+    _vae_f32("dualvae", mu_table, "mu_table", (num_rows, DUALVAE_A, DUALVAE_K))
     _lib.load().chaorec_dualvae_writeback_f32(_ptr(ids), B, int(num_rows), _ptr(slot_ptr), _ptr(perm), _ptr(z), _ptr(mu), _ptr(table),
                                               _ptr(mu_table), _stream())
 
 
 def dualvae_range_users(num_item):
     """How many users one ranking range may stage under the cap."""
-    return max(1, DUALVAE_STAGING_BYTES // (int(num_item) * 4))
+    return _range_users(DUALVAE_STAGING_BYTES, num_item)
 
 
 def dualvae_scores(z, zh, table, th, w, user_begin, hist, mask_value, out=None):
@@ -1008,9 +1006,9 @@ def dualvae_scores(z, zh, table, th, w, user_begin, hist, mask_value, out=None):
     their history entries = mask_value."""
     _need_cuda(z, zh, table, th, w, hist[0], hist[1])
     n, I = z.shape[0], table.shape[0]
-    z, zh = _dv_f32(z, "z", (n, DUALVAE_A, DUALVAE_K)), _dv_f32(zh, "zh", (n, DUALVAE_A, DUALVAE_H))
-    table, th = _dv_f32(table, "table", (I, DUALVAE_A, DUALVAE_K)), _dv_f32(th, "th", (I, DUALVAE_A, DUALVAE_H))
-    w = _dv_f32(w, "w", (I, DUALVAE_A))
+    z, zh = _vae_f32("dualvae", z, "z", (n, DUALVAE_A, DUALVAE_K)), _vae_f32("dualvae", zh, "zh", (n, DUALVAE_A, DUALVAE_H))
+    table, th = _vae_f32("dualvae", table, "table", (I, DUALVAE_A, DUALVAE_K)), _vae_f32("dualvae", th, "th", (I, DUALVAE_A, DUALVAE_H))
+    w = _vae_f32("dualvae", w, "w", (I, DUALVAE_A))
     if n > dualvae_range_users(I):
         raise ValueError(f"dualvae: {n} users x {I} items exceed the staging cap of {DUALVAE_STAGING_BYTES} bytes; rank in ranges")
     if hist[0].dtype != torch.int64 or hist[1].dtype != torch.int64:

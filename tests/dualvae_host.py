@@ -8,6 +8,8 @@ import os
 import numpy as np
 import torch
 
+from multvae_host import rel_dev, user_item_dict  # noqa: F401
+
 NAMES = ("user_preferences", "item_topics",
          "user_encoder.fc0.weight", "user_encoder.fc0.bias", "user_mu.weight", "user_mu.bias", "user_std.weight", "user_std.bias",
          "item_encoder.fc0.weight", "item_encoder.fc0.bias", "item_mu.weight", "item_mu.bias", "item_std.weight", "item_std.bias",
@@ -15,19 +17,6 @@ NAMES = ("user_preferences", "item_topics",
 A, K, H = 5, 25, 20
 EPS = 1e-10
 KL_WEIGHT, SSL_REG = 0.5, 0.01      # Model_YAML/DualVAE.yaml
-
-
-def rel_dev(x, ref):
-    """max |x - ref| relative to ref's largest element (the project's convention)."""
-    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float(np.abs(x - ref).max()) / max(float(np.abs(ref).max()), 1e-300)
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(int(u), []).append(int(i))
-    return d
 
 
 def dense_matrix(edges, U, I):
