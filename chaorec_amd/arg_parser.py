@@ -54,6 +54,7 @@ def build_parser():
     parser.add_argument('--no_graph', action='store_true',
                         help='eager launches instead of one captured hipGraph replay per training batch')
     parser.add_argument('--ii_topk', type=int, default=10, help='the number of item-item graph topk.')
+    parser.add_argument('--uu_topk', type=int, default=10, help='the number of user-user graph topk.')
     parser.add_argument('--lambda_coeff', type=float, default=0.9, help='the number of jump connection factor.')
     parser.add_argument('--seed', type=int, default=42, help='Number of seed')
     parser.add_argument('--num_workers', type=int, default=1, help='Workers number.')

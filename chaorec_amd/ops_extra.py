@@ -1084,3 +1084,176 @@ class _DualVAELoss(torch.autograd.Function):
 def dualvae_loss(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg):
     """-> [3]: one side's loss (Model/DualVAE.py:274), kl and ll."""
     return _DualVAELoss.apply(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg)
+
+
+# --------------------------------------------------------------------------------------------
+# The user-user co-occurrence graph (csrc/usergraph.hip): DRAGON's user_graph_dict built, sampled and aggregated on the device
+# --------------------------------------------------------------------------------------------
+USERGRAPH_TOPN = 200         # dualgnn-gen-u-u-matrix.py:92-103 keeps the 200 largest co-occurrence counts of a user
+USERGRAPH_MAX_N = 256        # what the build kernel's sorting network holds
+USERGRAPH_DIMS = (64, 128)   # the row widths the aggregation kernels are instantiated for
+
+
+def usergraph_max_users():
+    """The largest user count the usergraph entries accept (ids are 32-bit)."""
+    return int(_lib.load().chaorec_usergraph_max_users())
+
+
+def usergraph_tile_users(num_user, tile_users=0):
+    """How many user ids one LDS tile of the build covers."""
+    return int(_lib.load().chaorec_usergraph_tile_users(int(num_user), int(tile_users)))
+
+
+def _ug_i32(t, what, shape=None):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"usergraph: {what} must be a contiguous int32 tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"usergraph: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+class UserGraphStructure:
+    """nbr_idx / nbr_cnt int32 [U, N], nbr_len int32 [U] (each user's co-occurring users by count descending, id ascending)
+    and, once usergraph_sample() has run, the epoch's buffers: epoch_idx int32 [U, k], epoch_w fp32 [U, k] and the reverse
+    structure of the aggregation's backward (rev_ptr int64 [U + 1]; rev_slot int64, rev_u int32, rev_w fp32 [U k]: for every
+    user r the slots u k + j that name r, ascending).  The epoch buffers are allocated once per k and rewritten in place
+    by every later sample, so a captured step that holds their addresses reads the new epoch's graph at its next replay."""
+
+    def __init__(self, nbr_idx, nbr_cnt, nbr_len):
+        U, N = nbr_idx.shape
+        self.num_user, self.n = int(U), int(N)
+        self.nbr_idx, self.nbr_cnt = _ug_i32(nbr_idx, "nbr_idx"), _ug_i32(nbr_cnt, "nbr_cnt", (U, N))
+        self.nbr_len = _ug_i32(nbr_len, "nbr_len", (U,))
+        self.k = 0
+        self.epoch_idx = self.epoch_w = self.rev_ptr = self.rev_slot = self.rev_u = self.rev_w = self._ids = None
+
+    @classmethod
+    def from_dict(cls, user_graph_dict, num_user, n=USERGRAPH_TOPN, device="cpu"):
+        """The reference's user_graph_dict.npy ({user: [[ids], [counts]]}, Model/DRAGON.py:170) in the arrays' form."""
+        import numpy as np
+        idx, cnt = np.zeros((num_user, n), dtype=np.int32), np.zeros((num_user, n), dtype=np.int32)
+        length = np.zeros(num_user, dtype=np.int32)
+        for u in range(num_user):
+            ids, counts = user_graph_dict[u]
+            m = min(len(ids), n)
+            idx[u, :m], cnt[u, :m], length[u] = ids[:m], np.asarray(counts[:m]).astype(np.int32), m
+        return cls(torch.from_numpy(idx).to(device), torch.from_numpy(cnt).to(device), torch.from_numpy(length).to(device))
+
+    def to(self, device):
+        for name in ("nbr_idx", "nbr_cnt", "nbr_len", "epoch_idx", "epoch_w", "rev_ptr", "rev_slot", "rev_u", "rev_w", "_ids"):
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name).to(device))
+        return self
+
+    def _epoch_buffers(self, k):
+        if self.k != k:
+            U, dev = self.num_user, self.nbr_idx.device
+            self.k = int(k)
+            self.epoch_idx = torch.zeros((U, k), dtype=torch.int32, device=dev)
+            self.epoch_w = torch.zeros((U, k), dtype=torch.float32, device=dev)
+            self.rev_ptr = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+            self.rev_slot = torch.zeros(U * k, dtype=torch.int64, device=dev)
+            self.rev_u = torch.zeros(U * k, dtype=torch.int32, device=dev)
+            self.rev_w = torch.zeros(U * k, dtype=torch.float32, device=dev)
+            self._ids = torch.arange(U + 1, dtype=torch.int64, device=dev)
+
+    def set_epoch(self, epoch_idx, epoch_w):
+        """Install a GIVEN epoch graph ([U, k] ids and weights, e.g. the reference's own draw) and index it for the backward."""
+        U, k = epoch_idx.shape
+        if U != self.num_user or tuple(epoch_w.shape) != (U, k):
+            raise ValueError(f"usergraph: epoch graph {tuple(epoch_idx.shape)} / {tuple(epoch_w.shape)} for {self.num_user} users")
+        self._epoch_buffers(int(k))
+        self.epoch_idx.copy_(epoch_idx)
+        self.epoch_w.copy_(epoch_w)
+        self.index_epoch()
+
+    def index_epoch(self):
+        """The reverse structure of the current epoch_idx: torch's STABLE sort of the flattened slots by the user they name
+        (so a user's slots stay in ascending (u, j)), written into the buffers allocated with the epoch graph."""
+        flat = self.epoch_idx.view(-1).to(torch.int64)
+        named, perm = torch.sort(flat, stable=True)
+        self.rev_slot.copy_(perm)
+        self.rev_u.copy_(torch.div(perm, self.k, rounding_mode="floor"))
+        self.rev_w.copy_(self.epoch_w.view(-1)[perm])
+        self.rev_ptr.copy_(torch.searchsorted(named, self._ids))
+
+
+def usergraph_build(rowptr, col, num_item, n=USERGRAPH_TOPN, tile_users=0, out=None):
+    """The co-occurrence graph of the user-history CSR (rowptr int64 [U + 1], col int32 local item ids without repeats, on
+    the device) -> UserGraphStructure with N = n neighbours per user.  `out` = (nbr_idx, nbr_cnt, nbr_len) to fill."""
+    _need_cuda(rowptr, col)
+    if rowptr.dtype != torch.int64 or not rowptr.is_contiguous() or rowptr.dim() != 1:
+        raise ValueError("usergraph: rowptr must be a contiguous int64 vector")
+    col = _ug_i32(col, "col")
+    U, I, dev = int(rowptr.numel() - 1), int(num_item), rowptr.device
+    if not 1 <= int(n) <= USERGRAPH_MAX_N:
+        raise ValueError(f"usergraph: n = {n}, the build keeps 1 .. {USERGRAPH_MAX_N} neighbours")
+    if U < 1 or U > usergraph_max_users() or I < 1:
+        raise ValueError(f"usergraph: {U} users, {I} items (at most {usergraph_max_users()} users)")
+    # the item-major transpose (item -> ascending holders): a stable sort of the entries by item
+    counts = rowptr[1:] - rowptr[:-1]
+    rows = torch.repeat_interleave(torch.arange(U, dtype=torch.int32, device=dev), counts)
+    col64 = col.to(torch.int64)
+    item_users = rows[torch.sort(col64, stable=True)[1]].contiguous()
+    item_ptr = torch.zeros(I + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(col64, minlength=I)[:I], 0, out=item_ptr[1:])
+    if out is None:
+        out = (torch.empty((U, n), dtype=torch.int32, device=dev), torch.empty((U, n), dtype=torch.int32, device=dev),
+               torch.empty(U, dtype=torch.int32, device=dev))
+    nbr_idx, nbr_cnt, nbr_len = _ug_i32(out[0], "nbr_idx", (U, n)), _ug_i32(out[1], "nbr_cnt", (U, n)), _ug_i32(out[2], "nbr_len", (U,))
+    _need_cuda(nbr_idx, nbr_cnt, nbr_len)
+    _lib.load().chaorec_usergraph_build(_ptr(rowptr), _ptr(col), _ptr(item_ptr), _ptr(item_users), U, I, int(n), int(tile_users),
+                                        _ptr(nbr_idx), _ptr(nbr_cnt), _ptr(nbr_len), _stream())
+    return UserGraphStructure(nbr_idx, nbr_cnt, nbr_len)
+
+
+def usergraph_sample(s, k, seed, epoch):
+    """Model/DRAGON.py:231-270 on the device: fills s.epoch_idx / s.epoch_w [U, k] for (seed, epoch) and re-indexes them."""
+    _need_cuda(s.nbr_idx, s.nbr_cnt, s.nbr_len)
+    if not 1 <= int(k) <= s.n:
+        raise ValueError(f"usergraph: k = {k}, the structure holds {s.n} neighbours per user")
+    s._epoch_buffers(int(k))
+    _lib.load().chaorec_usergraph_sample(_ptr(s.nbr_idx), _ptr(s.nbr_cnt), _ptr(s.nbr_len), s.num_user, s.n, int(k),
+                                         int(seed) & (2**64 - 1), int(epoch) & (2**64 - 1), _ptr(s.epoch_idx), _ptr(s.epoch_w),
+                                         _stream())
+    s.index_epoch()
+    return s.epoch_idx, s.epoch_w
+
+
+class _UserGraphAggregate(torch.autograd.Function):
+    """(v [U, D], t [U, D], weight_u [U, 2(, 1)]) -> [U, 2 D] (Model/DRAGON.py:289-302): neither user_rep, nor
+    features[user_graph] [U, k, 2 D], nor h_u exists in memory, forward or backward."""
+
+    @staticmethod
+    def forward(ctx, v, t, weight_u, s):
+        _need_cuda(v, t, weight_u, s.epoch_idx)
+        if v.dim() != 2 or v.shape[1] not in USERGRAPH_DIMS:
+            raise ValueError(f"usergraph: v is {tuple(v.shape)}, the aggregation is built for D in {USERGRAPH_DIMS}")
+        U, D = s.num_user, int(v.shape[1])
+        v, t = _vae_f32("usergraph", v, "v", (U, D)), _vae_f32("usergraph", t, "t", (U, D))
+        weight_u = _vae_f32("usergraph", weight_u, "weight_u")
+        if weight_u.numel() != 2 * U or weight_u.shape[0] != U:
+            raise ValueError(f"usergraph: weight_u is {tuple(weight_u.shape)}, expected ({U}, 2)")
+        if s.k < 1:
+            raise ValueError("usergraph: no epoch graph yet (usergraph_sample / set_epoch)")
+        out = torch.empty((U, 2 * D), dtype=torch.float32, device=v.device)
+        _lib.load().chaorec_usergraph_aggregate_fwd_f32(_ptr(v), _ptr(t), _ptr(weight_u), _ptr(s.epoch_idx), _ptr(s.epoch_w), U, s.k, D,
+                                                        _ptr(out), _stream())
+        ctx.save_for_backward(v, t, weight_u)
+        ctx.s = s
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        v, t, weight_u = ctx.saved_tensors
+        s, (U, D) = ctx.s, v.shape
+        g = _f32c(g)
+        dv, dt, dw = torch.empty_like(v), torch.empty_like(t), torch.empty_like(weight_u)
+        _lib.load().chaorec_usergraph_aggregate_bwd_f32(_ptr(g), _ptr(v), _ptr(t), _ptr(weight_u), _ptr(s.rev_ptr), _ptr(s.rev_u),
+                                                        _ptr(s.rev_w), U, D, _ptr(dv), _ptr(dt), _ptr(dw), _stream())
+        return dv, dt, dw, None
+
+
+def usergraph_aggregate(v, t, weight_u, s):
+    """out[u] = x[u] + sum_j s.epoch_w[u, j] x[s.epoch_idx[u, j]], x[r] = (weight_u[r, 0] v[r], weight_u[r, 1] t[r])."""
+    return _UserGraphAggregate.apply(v, t, weight_u, s)

@@ -1082,6 +1082,42 @@ int chaorec_dualvae_scores_f32(const float *z, const float *zh, int64_t n_users,
                                const float *w, int64_t I, int64_t user_begin, const int64_t *hist_rowptr, const int64_t *hist_col,
                                float mask_value, float *scores, size_t scores_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The user-user co-occurrence graph (Model/DRAGON.py; DualGNN, COHESION and MHRec read the same user_graph_dict.npy) --
+ * csrc/usergraph.hip.  Additive to ABI 16: new names only.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* The largest U the entries below accept (user ids are 32-bit in every array): beyond it they return CHAOREC_E_INVALID. */
+int64_t chaorec_usergraph_max_users(void);
+/* How many user ids one LDS tile of chaorec_usergraph_build covers for (U, tile_users): min(U, 32768), capped by a
+ * positive tile_users. */
+int64_t chaorec_usergraph_tile_users(int64_t U, int32_t tile_users);
+/* dualgnn-gen-u-u-matrix.py:20-50 and :90-103 (the dense [U, U] co-occurrence matrix and its per-row torch.topk) without
+ * the matrix.  (hist_rowptr int64 [U + 1], hist_col int32 local item ids, no repeats) is the user-history CSR, (item_ptr
+ * int64 [I + 1], item_users int32) its item-major transpose.  Row u of nbr_idx / nbr_cnt [U, N]: the users v != u with
+ * c(u, v) = |items(u) & items(v)| > 0, by c descending then v ascending, cut at N <= 256; nbr_len[u] = how many; slots
+ * past it hold 0 / 0.  tile_users: 0 = the kernel's own tile, else a cap on it (the result does not depend on it). */
+int chaorec_usergraph_build(const int64_t *hist_rowptr, const int32_t *hist_col, const int64_t *item_ptr, const int32_t *item_users,
+                            int64_t U, int64_t I, int32_t N, int32_t tile_users, int32_t *nbr_idx, int32_t *nbr_cnt,
+                            int32_t *nbr_len, void *stream);
+/* Model/DRAGON.py:231-270 (topk_sample), k <= N: epoch_idx int32 [U, k], epoch_w fp32 [U, k] = softmax over the k slots'
+ * counts.  nbr_len >= k: the first k neighbours.  0 < nbr_len < k: slot j >= nbr_len copies slot r_j of the same row,
+ * r_j = ((mix64(seed ^ mix64(epoch ^ mix64(u << 32 | j))) >> 32) * j) >> 32 (:249-252, the urn over the grown list).
+ * nbr_len = 0: indices 0, weights 0 (:244-246). */
+int chaorec_usergraph_sample(const int32_t *nbr_idx, const int32_t *nbr_cnt, const int32_t *nbr_len, int64_t U, int32_t N, int32_t k,
+                             uint64_t seed, uint64_t epoch, int32_t *epoch_idx, float *epoch_w, void *stream);
+/* Model/DRAGON.py:289-302 in one pass: with x[r, :] = (weight_u[r, 0] v[r, :], weight_u[r, 1] t[r, :]) (v, t fp32 [U, D],
+ * weight_u [U, 2]), out[u, :] = x[u, :] + sum_j epoch_w[u, j] x[epoch_idx[u, j], :]  -> [U, 2 D]; the sum in ascending j,
+ * product and add rounded separately, the residual last.  D is 64 or 128. */
+int chaorec_usergraph_aggregate_fwd_f32(const float *v, const float *t, const float *weight_u, const int32_t *epoch_idx,
+                                        const float *epoch_w, int64_t U, int32_t k, int32_t D, float *out, void *stream);
+/* Its backward from g [U, 2 D].  (rev_ptr int64 [U + 1], rev_u int32, rev_w fp32): for every user r the slots (u, j) with
+ * epoch_idx[u, j] = r in ascending (u, j), as their u and their epoch_w.  gx[r] = g[r] + sum rev_w g[rev_u] in that order;
+ * dv[r] = weight_u[r, 0] gx[r, :D], dt[r] = weight_u[r, 1] gx[r, D:], dw[r] = (<gx[r, :D], v[r]>, <gx[r, D:], t[r]>).
+ * One owner per row, no atomics: the same bits every run. */
+int chaorec_usergraph_aggregate_bwd_f32(const float *g, const float *v, const float *t, const float *weight_u,
+                                        const int64_t *rev_ptr, const int32_t *rev_u, const float *rev_w, int64_t U, int32_t D,
+                                        float *dv, float *dt, float *dw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,149 @@
+"""The restatements of tests/dragon_host.py against the reference fixtures of tests/golden/gen_dragon.py (no GPU):
+the co-occurrence top-N against what the reference's own script wrote for baby, one DRAGON step against the reference class on
+the synthetic graph, the epoch sample's law against the epoch graph the reference's topk_sample drew; and the part of the
+model's surface that needs no device (the constructor's arguments, the methods)."""
+import inspect
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dragon_host as dh  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def baby_graph():
+    g = np.load(os.path.join(GOLDEN, "baby_interactions.npz"))
+    U, I = int(g["U"]), int(g["I"])
+    rowptr, col = dh.history_csr(g["train"], U)
+    return U, I, dh.cooccurrence(rowptr, col, U, I)
+
+
+def test_cooccurrence_reproduces_the_reference_script(baby_graph):
+    U, I, C = baby_graph
+    f = dh.load_fixture(GOLDEN, "dragon_usergraph_baby.npz")
+    assert int(f["U"]) == U and len(f["len"]) == U
+    idx, cnt, length = dh.topn(C)
+    assert np.array_equal(length, f["len"].astype(np.int32))                       # every user's neighbour count ...
+    off = np.concatenate(([0], np.cumsum(f["len"].astype(np.int64))))
+    mine = np.concatenate([cnt[u, :length[u]] for u in range(U)])
+    assert np.array_equal(mine, f["counts"].astype(np.int32))                      # ... and count sequence
+    assert (np.diff(C.indptr) > dh.TOPN).any(), "no user is cut at 200: the tie rule would go unchecked"
+    ioff = np.concatenate(([0], np.cumsum(f["len"][f["id_users"]].astype(np.int64))))
+    for n, u in enumerate(f["id_users"].astype(np.int64)):
+        ref_ids = f["ids"][ioff[n]:ioff[n + 1]]
+        ref_counts = f["counts"][off[u]:off[u + 1]]
+        assert dh.check_ids(u, ref_ids, ref_counts, C) is None, dh.check_ids(u, ref_ids, ref_counts, C)     # the reference's list
+        assert dh.check_ids(u, idx[u, :length[u]], cnt[u, :length[u]], C) is None                          # ... and ours
+
+
+def test_check_ids_rejects_wrong_lists(baby_graph):
+    U, I, C = baby_graph
+    idx, cnt, length = dh.topn(C)
+    u = int(np.argmax(np.diff(C.indptr) > dh.TOPN))
+    ids, counts = idx[u, :length[u]].copy(), cnt[u, :length[u]].copy()
+    assert dh.check_ids(u, ids[:-1], counts[:-1], C) is not None
+    swapped = ids.copy()
+    swapped[0] = (set(range(U)) - set(C.indices[C.indptr[u]:C.indptr[u + 1]].tolist()) - {u}).pop()     # not a neighbour at all
+    assert dh.check_ids(u, swapped, counts, C) is not None
+    doubled = ids.copy()
+    doubled[-1] = doubled[-2]
+    assert dh.check_ids(u, doubled, counts, C) is not None
+
+
+@pytest.fixture(scope="module")
+def small():
+    c = dh.small_case()
+    f = dh.load_fixture(GOLDEN, "dragon_small.npz")
+    w = dh.init_weights(c)
+    return c, f, w
+
+
+def test_init_replay_matches_the_reference(small):
+    c, f, w = small
+    assert tuple(w) != () and set(w) == set(dh.NAMES)
+    for k, n in enumerate(dh.NAMES):
+        assert np.array_equal(w[n].reshape(-1)[:f["w_probe"].shape[1]], f["w_probe"][k][:w[n].size]), n
+        assert abs(float(w[n].astype(np.float64).sum()) - f["w_sum"][k]) <= 1e-9 * max(1.0, abs(f["w_sum"][k])), n
+
+
+def test_step_reproduces_the_reference(small):
+    c, f, w = small
+    U, I = c["U"], c["I"]
+    out = dh.step(w, c["v_feat"], c["t_feat"], c["edges"], U, I, f["epoch_idx"], f["epoch_w"], c["users"], c["pos"] - U, c["neg"] - U,
+                  dh.REG_WEIGHT, dh.N_LAYERS, f["knn_v"], f["knn_t"], dh.MM_IMAGE_WEIGHT)
+    tight = 1.0 + 1e-6
+    assert dh.rel_dev(f["ref_result"], out["result"]) <= float(f["dev_result"]) * tight
+    for k in ("loss", "bpr", "reg"):
+        assert dh.rel_dev(float(f["ref_" + k]), out[k]) <= float(f["dev_" + k]) * tight, k
+    assert float(f["dev_loss"]) < 1e-4
+    for k, n in enumerate(dh.WITH_GRAD):
+        mine = out["grads"][n]
+        scale = float(np.abs(mine).max())
+        assert abs(scale - f["gscale"][k]) <= 1e-9 * scale
+        sub = mine[dh.GRAD_ROWS] if n.endswith("MLP.weight") else mine
+        assert np.abs(f[f"ref_grad_{k}"] - sub).max() <= float(f["dev_grads"][k]) * scale * tight, n
+
+
+def test_sample_law_matches_the_reference_draw(small):
+    """The epoch graph the reference's topk_sample drew obeys the law the restated sample follows: the first min(len, k)
+    slots are the neighbours in order, every later slot repeats an EARLIER slot of the same row, the weights are the softmax
+    of the slots' counts, a user without neighbours has indices 0 and weights 0."""
+    c, f, _ = small
+    U, I, k = c["U"], c["I"], dh.UU_TOPK
+    rowptr, col = dh.history_csr(c["edges"], U)
+    idx, cnt, length = dh.topn(dh.cooccurrence(rowptr, col, U, I))
+    e_idx, e_w = f["epoch_idx"].astype(np.int64), f["epoch_w"].astype(np.float64)
+    assert (length == 0).any() and ((length > 0) & (length < k)).any() and (length >= k).any()
+    count_of = [dict(zip(idx[u, :length[u]].tolist(), cnt[u, :length[u]].tolist())) for u in range(U)]
+    for u in range(U):
+        n = min(int(length[u]), k)
+        if n == 0:
+            assert not e_idx[u].any() and not e_w[u].any()
+            continue
+        assert np.array_equal(e_idx[u, :n], idx[u, :n])
+        for j in range(n, k):
+            assert e_idx[u, j] in e_idx[u, :j]
+        cs = np.array([count_of[u][int(i)] for i in e_idx[u]], dtype=np.float64)
+        sm = np.exp(cs - cs.max())
+        assert np.abs(e_w[u] - sm / sm.sum()).max() <= 4 * 2.0 ** -24
+    # the restated sample on the same structure: same first slots, same law, its own draws
+    m_idx, m_w, src, r = dh.sample(idx, cnt, length, k, 7, 0)
+    full = length >= k
+    assert np.array_equal(m_idx[full], e_idx[full]) and np.abs(m_w[full] - e_w[full]).max() <= 4 * 2.0 ** -24
+    for u in np.nonzero(~full & (length > 0))[0]:
+        for j in range(int(length[u]), k):
+            assert 0 <= r[u, j] < j and m_idx[u, j] == m_idx[u, r[u, j]]
+    assert np.allclose(m_w[length > 0].sum(1), 1.0, rtol=0, atol=1e-12) and not m_w[length == 0].any()
+    assert not np.array_equal(dh.sample(idx, cnt, length, k, 7, 1)[0], m_idx)        # another epoch, another padding
+
+
+def test_generator_is_uniform_enough():
+    """r_j = draw(seed, epoch, u, j, j) lies in [0, j) and every value turns up about equally often."""
+    u = np.arange(20000)
+    for j in (1, 2, 7, 199):
+        r = dh.draw(99, 5, u, j, j).astype(np.int64)
+        assert r.min() >= 0 and r.max() < j
+        share = np.bincount(r, minlength=j) / len(u)
+        assert np.abs(share - 1.0 / j).max() < 5 * np.sqrt((1.0 / j) / len(u))
+
+
+def test_model_surface():
+    from chaorec_amd import main, train_and_evaluate
+    from chaorec_amd.arg_parser import load_yaml_config, parse_args
+    from chaorec_amd.Model import DRAGON
+    args = [p for p in inspect.signature(DRAGON.__init__).parameters][1:]
+    assert args == ["num_user", "num_item", "edge_index", "user_item_dict", "v_feat", "t_feat", "dim_E", "feature_embedding",
+                    "reg_weight", "n_layers", "ii_topk", "uu_topk", "mm_image_weight", "aggr_mode", "device"]     # main.py:284
+    for name in ("forward", "loss", "pre_epoch_processing", "gene_ranklist", "topk_sample", "init_weight", "get_knn_adj_mat"):
+        assert callable(getattr(DRAGON, name)), name
+    assert "DRAGON" in train_and_evaluate.PRE_EPOCH
+    a = parse_args(["--Model", "DRAGON"])
+    assert (a.uu_topk, a.ii_topk) == (10, 10)
+    cfg = load_yaml_config("DRAGON")
+    assert cfg["uu_topk"] == [40] and cfg["ii_topk"] == [10] and cfg["lambda_coeff"] == [0.6] and cfg["reg_weight"] == [0.01]
+    assert "'DRAGON'" in inspect.getsource(main.build_model)
