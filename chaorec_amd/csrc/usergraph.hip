@@ -9,6 +9,8 @@
 //                          when a user has fewer, and the softmax of their counts.
 //  (c) ug_agg_fwd / _bwd   Model/DRAGON.py:289-302 (weight_u * [v_rep | t_rep], User_Graph_sample.forward, the residual)
 //                          and its gradient, one lane group per row, ordered and atomic-free.
+//  (d) dg_fuse_fwd / _bwd  Model/DualGNN.py:189-239: the same aggregation over the weighted SUM a v + b t, with the item rows
+//                          v + t in the same launch -- the whole result table [U + I, D] and its gradient.
 //
 // Key convention (the project's): (count << 32) | (0xFFFFFFFF - id), larger key first = count descending, id ascending.
 // A key of 0 is "no entry" (a count of 0 is never stored).
@@ -293,6 +295,89 @@ __global__ __launch_bounds__(UG_THREADS) void ug_agg_bwd_kernel(const float *__r
   if (ln.c == 0) dw[r * 2 + ln.which] = dot;
 }
 
+// ---- DualGNN (Model/DualGNN.py:189-239): the modality mix is a weighted SUM, x[r, :] = a_r v[r, :] + b_r t[r, :], a row of D floats
+// (DRAGON's is the concatenation above), and the item rows v + t are written by the same launch: one [U + I, D] table out.
+// A lane group of D / 4 lanes owns a row, one dwordx4 of v and one of t per lane.
+template <int D>
+struct DgLane {
+  const float *v, *t, *wu;
+  int c;
+  __device__ __forceinline__ DgLane(const float *v_, const float *t_, const float *wu_, int l) : v(v_), t(t_), wu(wu_), c(l * 4) {}
+  __device__ __forceinline__ float4 row(const float *p, int64_t r) const { return *reinterpret_cast<const float4 *>(p + r * D + c); }
+  __device__ __forceinline__ float4 x(int64_t r) const {
+    return add_rn4(mul_rn4(wu[r * 2], row(v, r)), mul_rn4(wu[r * 2 + 1], row(t, r)));
+  }
+};
+
+template <int D>
+__global__ __launch_bounds__(UG_THREADS) void dg_fuse_fwd_kernel(const float *__restrict__ v, const float *__restrict__ t,
+                                                                 const float *__restrict__ wu, const int32_t *__restrict__ idx,
+                                                                 const float *__restrict__ w, int64_t U, int64_t N, int k,
+                                                                 float *__restrict__ out) {
+  constexpr int LPR = D / 4;
+  const int64_t r = (int64_t)blockIdx.x * (UG_THREADS / LPR) + threadIdx.x / LPR;
+  if (r >= N) return;
+  const DgLane<D> ln(v, t, wu, threadIdx.x % LPR);
+  float4 *dst = reinterpret_cast<float4 *>(out + r * D + ln.c);
+  if (r >= U) {                                      // an item row: representation[U:] = v_rep + t_rep (:189, :231)
+    *dst = add_rn4(ln.row(v, r), ln.row(t, r));
+    return;
+  }
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int32_t *iu = idx + r * k;
+  const float *wr = w + r * k;
+#pragma unroll 4
+  for (int j = 0; j < k; ++j) {
+    const int64_t s = iu[j];
+    if (s < 0 || s >= U) continue;
+    acc = add_rn4(acc, mul_rn4(wr[j], ln.x(s)));
+  }
+  *dst = add_rn4(ln.x(r), acc);
+}
+
+// The owner of gradient row r < U walks the slots that name r as ug_agg_bwd_kernel does; an item row hands g on to both tables.
+template <int D>
+__global__ __launch_bounds__(UG_THREADS) void dg_fuse_bwd_kernel(const float *__restrict__ g, const float *__restrict__ v,
+                                                                 const float *__restrict__ t, const float *__restrict__ wu,
+                                                                 const int64_t *__restrict__ rev_ptr, const int32_t *__restrict__ rev_u,
+                                                                 const float *__restrict__ rev_w, int64_t U, int64_t N,
+                                                                 float *__restrict__ dv, float *__restrict__ dt, float *__restrict__ dw) {
+  constexpr int LPR = D / 4;
+  const int64_t r = (int64_t)blockIdx.x * (UG_THREADS / LPR) + threadIdx.x / LPR;
+  if (r >= N) return;                                // (whole lane groups leave: the shuffles below stay inside a group)
+  const DgLane<D> ln(v, t, wu, threadIdx.x % LPR);
+  const float4 gr = ln.row(g, r);
+  float4 *pv = reinterpret_cast<float4 *>(dv + r * D + ln.c), *pt = reinterpret_cast<float4 *>(dt + r * D + ln.c);
+  if (r >= U) {
+    *pv = gr;
+    *pt = gr;
+    return;
+  }
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int64_t end = rev_ptr[r + 1];
+#pragma unroll 4
+  for (int64_t e = rev_ptr[r]; e < end; ++e) {
+    const int64_t u = rev_u[e];
+    if (u < 0 || u >= U) continue;
+    acc = add_rn4(acc, mul_rn4(rev_w[e], ln.row(g, u)));
+  }
+  const float4 gx = add_rn4(gr, acc);
+  *pv = mul_rn4(wu[r * 2], gx);
+  *pt = mul_rn4(wu[r * 2 + 1], gx);
+  const float4 xv = ln.row(v, r), xt = ln.row(t, r);
+  float da = add_rn(add_rn(mul_rn(gx.x, xv.x), mul_rn(gx.y, xv.y)), add_rn(mul_rn(gx.z, xv.z), mul_rn(gx.w, xv.w)));
+  float db = add_rn(add_rn(mul_rn(gx.x, xt.x), mul_rn(gx.y, xt.y)), add_rn(mul_rn(gx.z, xt.z), mul_rn(gx.w, xt.w)));
+#pragma unroll
+  for (int off = LPR / 2; off > 0; off >>= 1) {      // within the row's D / 4 lanes, fixed order
+    da += __shfl_xor(da, off, 64);
+    db += __shfl_xor(db, off, 64);
+  }
+  if (ln.c == 0) {
+    dw[r * 2] = da;
+    dw[r * 2 + 1] = db;
+  }
+}
+
 static int ug_tile(int64_t U, int32_t tile_users) {
   int64_t tile = U < UG_MAX_TILE ? U : UG_MAX_TILE;
   if (tile_users > 0 && tile_users < tile) tile = tile_users;
@@ -364,4 +449,40 @@ extern "C" int chaorec_usergraph_aggregate_bwd_f32(const float *g, const float *
     hipLaunchKernelGGL(ug_agg_bwd_kernel<128>, dim3((unsigned)((U + 3) / 4)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, v, t, weight_u,
                        rev_ptr, rev_u, rev_w, U, dv, dt, dw);
   return check_launch("ug_agg_bwd_kernel");
+}
+
+static int dg_check(const char *what, int64_t U, int64_t N, int32_t k, int32_t D) {
+  if (U <= 0 || U > chaorec_usergraph_max_users() || N < U || N > 2 * chaorec_usergraph_max_users() || k < 1 || (D != 64 && D != 128))
+    return fail(CHAOREC_E_INVALID, "%s: U=%lld N=%lld k=%d D=%d (1 <= U <= N, k >= 1, D is 64 or 128)", what, (long long)U,
+                (long long)N, (int)k, (int)D);
+  return CHAOREC_OK;
+}
+
+extern "C" int chaorec_dualgnn_fuse_fwd_f32(const float *v, const float *t, const float *weight_u, const int32_t *epoch_idx,
+                                            const float *epoch_w, int64_t U, int64_t N, int32_t k, int32_t D, float *result,
+                                            void *stream) {
+  if (!v || !t || !weight_u || !epoch_idx || !epoch_w || !result) return fail(CHAOREC_E_INVALID, "dualgnn_fuse_fwd: NULL argument");
+  if (const int rc = dg_check("dualgnn_fuse_fwd", U, N, k, D)) return rc;
+  if (D == 64)
+    hipLaunchKernelGGL(dg_fuse_fwd_kernel<64>, dim3((unsigned)((N + 15) / 16)), dim3(UG_THREADS), 0, (hipStream_t)stream, v, t, weight_u,
+                       epoch_idx, epoch_w, U, N, (int)k, result);
+  else
+    hipLaunchKernelGGL(dg_fuse_fwd_kernel<128>, dim3((unsigned)((N + 7) / 8)), dim3(UG_THREADS), 0, (hipStream_t)stream, v, t, weight_u,
+                       epoch_idx, epoch_w, U, N, (int)k, result);
+  return check_launch("dg_fuse_fwd_kernel");
+}
+
+extern "C" int chaorec_dualgnn_fuse_bwd_f32(const float *g, const float *v, const float *t, const float *weight_u, const int64_t *rev_ptr,
+                                            const int32_t *rev_u, const float *rev_w, int64_t U, int64_t N, int32_t D, float *dv,
+                                            float *dt, float *dw, void *stream) {
+  if (!g || !v || !t || !weight_u || !rev_ptr || !rev_u || !rev_w || !dv || !dt || !dw)
+    return fail(CHAOREC_E_INVALID, "dualgnn_fuse_bwd: NULL argument");
+  if (const int rc = dg_check("dualgnn_fuse_bwd", U, N, 1, D)) return rc;
+  if (D == 64)
+    hipLaunchKernelGGL(dg_fuse_bwd_kernel<64>, dim3((unsigned)((N + 15) / 16)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, v, t, weight_u,
+                       rev_ptr, rev_u, rev_w, U, N, dv, dt, dw);
+  else
+    hipLaunchKernelGGL(dg_fuse_bwd_kernel<128>, dim3((unsigned)((N + 7) / 8)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, v, t, weight_u,
+                       rev_ptr, rev_u, rev_w, U, N, dv, dt, dw);
+  return check_launch("dg_fuse_bwd_kernel");
 }

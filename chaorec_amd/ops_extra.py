@@ -1087,7 +1087,8 @@ def dualvae_loss(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg):
 
 
 # --------------------------------------------------------------------------------------------
-# The user-user co-occurrence graph (csrc/usergraph.hip): DRAGON's user_graph_dict built, sampled and aggregated on the device
+# The user-user co-occurrence graph (csrc/usergraph.hip): DRAGON's user_graph_dict built, sampled and aggregated on the device;
+# DualGNN's fused node over the same structure
 # --------------------------------------------------------------------------------------------
 USERGRAPH_TOPN = 200         # dualgnn-gen-u-u-matrix.py:92-103 keeps the 200 largest co-occurrence counts of a user
 USERGRAPH_MAX_N = 256        # what the build kernel's sorting network holds
@@ -1257,3 +1258,45 @@ class _UserGraphAggregate(torch.autograd.Function):
 def usergraph_aggregate(v, t, weight_u, s):
     """out[u] = x[u] + sum_j s.epoch_w[u, j] x[s.epoch_idx[u, j]], x[r] = (weight_u[r, 0] v[r], weight_u[r, 1] t[r])."""
     return _UserGraphAggregate.apply(v, t, weight_u, s)
+
+
+class _DualGNNFuse(torch.autograd.Function):
+    """(v [N, D], t [N, D], weight_u [U, 2(, 1)]) -> result [N, D] (Model/DualGNN.py:189-239): none of user_rep,
+    features[user_graph] [U, k, D], h_u1 or representation exists in memory, forward or backward."""
+
+    @staticmethod
+    def forward(ctx, v, t, weight_u, s, num_user):
+        _need_cuda(v, t, weight_u, s.epoch_idx)
+        if v.dim() != 2 or v.shape[1] not in USERGRAPH_DIMS:
+            raise ValueError(f"dualgnn_fuse: v is {tuple(v.shape)}, the kernels are built for D in {USERGRAPH_DIMS}")
+        U, (N, D) = int(num_user), (int(v.shape[0]), int(v.shape[1]))
+        if U != s.num_user or N < U:
+            raise ValueError(f"dualgnn_fuse: {U} users, a table of {N} rows, a user graph of {s.num_user} users")
+        v, t = _vae_f32("dualgnn_fuse", v, "v", (N, D)), _vae_f32("dualgnn_fuse", t, "t", (N, D))
+        weight_u = _vae_f32("dualgnn_fuse", weight_u, "weight_u")
+        if tuple(weight_u.shape) not in ((U, 2), (U, 2, 1)):
+            raise ValueError(f"dualgnn_fuse: weight_u is {tuple(weight_u.shape)}, expected ({U}, 2) or ({U}, 2, 1)")
+        if s.k < 1:
+            raise ValueError("dualgnn_fuse: no epoch graph yet (usergraph_sample / set_epoch)")
+        out = torch.empty((N, D), dtype=torch.float32, device=v.device)
+        _lib.load().chaorec_dualgnn_fuse_fwd_f32(_ptr(v), _ptr(t), _ptr(weight_u), _ptr(s.epoch_idx), _ptr(s.epoch_w), U, N, s.k, D,
+                                                 _ptr(out), _stream())
+        ctx.save_for_backward(v, t, weight_u)
+        ctx.s, ctx.U = s, U
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        v, t, weight_u = ctx.saved_tensors
+        s, U, (N, D) = ctx.s, ctx.U, v.shape
+        g = _f32c(g)
+        dv, dt, dw = torch.empty_like(v), torch.empty_like(t), torch.empty_like(weight_u)   # every element is written
+        _lib.load().chaorec_dualgnn_fuse_bwd_f32(_ptr(g), _ptr(v), _ptr(t), _ptr(weight_u), _ptr(s.rev_ptr), _ptr(s.rev_u),
+                                                 _ptr(s.rev_w), U, N, D, _ptr(dv), _ptr(dt), _ptr(dw), _stream())
+        return dv, dt, dw, None, None
+
+
+def dualgnn_fuse(v, t, weight_u, s, num_user):
+    """result[u] = x[u] + sum_j s.epoch_w[u, j] x[s.epoch_idx[u, j]] with x[r] = weight_u[r, 0] v[r] + weight_u[r, 1] t[r] for
+    u < num_user, result[r] = v[r] + t[r] below: DualGNN's whole table from the two modality tables in one launch."""
+    return _DualGNNFuse.apply(v, t, weight_u, s, num_user)

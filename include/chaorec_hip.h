@@ -1118,6 +1118,21 @@ int chaorec_usergraph_aggregate_bwd_f32(const float *g, const float *v, const fl
                                         const int64_t *rev_ptr, const int32_t *rev_u, const float *rev_w, int64_t U, int32_t D,
                                         float *dv, float *dt, float *dw, void *stream);
 
+/* Model/DualGNN.py:189-239 in one pass over the whole result table of N = U + I rows (v, t fp32 [N, D], the two modality GCN
+ * outputs; weight_u [U, 2]).  With x[r, :] = weight_u[r, 0] v[r, :] + weight_u[r, 1] t[r, :] for r < U:
+ * result[u, :] = x[u, :] + sum_j epoch_w[u, j] x[epoch_idx[u, j], :] for u < U (ascending j, product and add rounded
+ * separately, the residual last; a slot whose index lies outside [0, U) is skipped), result[r, :] = v[r, :] + t[r, :] for
+ * r >= U.  N == U is legal.  D is 64 or 128. */
+int chaorec_dualgnn_fuse_fwd_f32(const float *v, const float *t, const float *weight_u, const int32_t *epoch_idx,
+                                 const float *epoch_w, int64_t U, int64_t N, int32_t k, int32_t D, float *result, void *stream);
+/* Its backward from g [N, D] over the reverse structure of chaorec_usergraph_aggregate_bwd_f32: for r < U
+ * gx[r] = g[r] + sum rev_w g[rev_u] in the list's order, dv[r] = weight_u[r, 0] gx[r], dt[r] = weight_u[r, 1] gx[r],
+ * dw[r] = (<gx[r], v[r]>, <gx[r], t[r]>); for r >= U dv[r] = dt[r] = g[r].  dv, dt [N, D] and dw [U, 2] are written in
+ * every element.  One owner per row, no atomics: the same bits every run. */
+int chaorec_dualgnn_fuse_bwd_f32(const float *g, const float *v, const float *t, const float *weight_u, const int64_t *rev_ptr,
+                                 const int32_t *rev_u, const float *rev_w, int64_t U, int64_t N, int32_t D, float *dv, float *dt,
+                                 float *dw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
