@@ -11,6 +11,9 @@
 //                          and its gradient, one lane group per row, ordered and atomic-free.
 //  (d) dg_fuse_fwd / _bwd  Model/DualGNN.py:189-239: the same aggregation over the weighted SUM a v + b t, with the item rows
 //                          v + t in the same launch -- the whole result table [U + I, D] and its gradient.
+//  (e) cf_fuse_fwd / cf_chunk / cf_rows   Model/COHESION.py:340-359: the aggregation over rows of three tables side by side
+//                          (id | v | t, 192 floats), the item rows plus their item-graph term -- and a backward whose long
+//                          reverse lists are cut into chunks summed by separate lane groups, the partials added in chunk order.
 //
 // Key convention (the project's): (count << 32) | (0xFFFFFFFF - id), larger key first = count descending, id ascending.
 // A key of 0 is "no entry" (a count of 0 is never stored).
@@ -378,6 +381,110 @@ __global__ __launch_bounds__(UG_THREADS) void dg_fuse_bwd_kernel(const float *__
   }
 }
 
+// ---- COHESION (Model/COHESION.py:340-359): x[r, :] = (idr[r, :] | v[r, :] | t[r, :]), a row of 3 x 64 floats that is never
+// concatenated in memory; the item rows take their item-graph term h = mm_adj^L x[U:] from three [I, 64] tables (or none).
+// A lane group of 16 lanes owns a row: the same four columns of each of the three tables, three dwordx4 per lane.
+constexpr int CF_D = 64;               // COHESION hard-codes dim_latent = 64
+constexpr int CF_W = 3 * CF_D;         // a row of result / g
+constexpr int CF_LIVE = 2 * CF_D;      // the columns of g that carry a gradient: the id third is detached (:321)
+
+__device__ __forceinline__ float4 cf_row(const float *p, int64_t r, int c) { return *reinterpret_cast<const float4 *>(p + r * CF_D + c); }
+
+__global__ __launch_bounds__(UG_THREADS) void cf_fuse_fwd_kernel(const float *__restrict__ idr, const float *__restrict__ v,
+                                                                 const float *__restrict__ t, const float *__restrict__ h_id,
+                                                                 const float *__restrict__ h_v, const float *__restrict__ h_t,
+                                                                 const int32_t *__restrict__ idx, const float *__restrict__ w, int64_t U,
+                                                                 int64_t N, int k, float *__restrict__ out) {
+  constexpr int LPR = CF_D / 4;
+  const int64_t r = (int64_t)blockIdx.x * (UG_THREADS / LPR) + threadIdx.x / LPR;
+  if (r >= N) return;
+  const int c = (threadIdx.x % LPR) * 4;
+  float4 *dst = reinterpret_cast<float4 *>(out + r * CF_W + c);
+  const float4 x0 = cf_row(idr, r, c), x1 = cf_row(v, r, c), x2 = cf_row(t, r, c);
+  if (r >= U) {                                      // an item row: item_rep + h_i (:348-355); no item graph: item_rep
+    const int64_t i = r - U;
+    const bool has = h_id != nullptr;
+    dst[0] = has ? add_rn4(x0, cf_row(h_id, i, c)) : x0;
+    dst[CF_D / 4] = has ? add_rn4(x1, cf_row(h_v, i, c)) : x1;
+    dst[2 * CF_D / 4] = has ? add_rn4(x2, cf_row(h_t, i, c)) : x2;
+    return;
+  }
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0;
+  const int32_t *iu = idx + r * k;
+  const float *wr = w + r * k;
+#pragma unroll 4
+  for (int j = 0; j < k; ++j) {
+    const int64_t s = iu[j];
+    if (s < 0 || s >= U) continue;
+    const float ws = wr[j];
+    a0 = add_rn4(a0, mul_rn4(ws, cf_row(idr, s, c)));
+    a1 = add_rn4(a1, mul_rn4(ws, cf_row(v, s, c)));
+    a2 = add_rn4(a2, mul_rn4(ws, cf_row(t, s, c)));
+  }
+  dst[0] = add_rn4(x0, a0);
+  dst[CF_D / 4] = add_rn4(x1, a1);
+  dst[2 * CF_D / 4] = add_rn4(x2, a2);
+}
+
+// Backward, first launch.  A lane group of 32 lanes owns one CHUNK of a reverse list -- entries [first, first + chunk) of
+// rev_u / rev_w, cut at the end of the row's list -- over the 128 live columns of g, one dwordx4 per lane:
+// part[c, :] = ((0 + w_1 g_1) + w_2 g_2) + ... in list order.  No list is longer than `chunk` for any lane group, so the
+// launch's time follows the bytes it moves, not the longest list (dg_fuse_bwd_kernel above walks that one alone).
+__global__ __launch_bounds__(UG_THREADS) void cf_chunk_kernel(const float *__restrict__ g, const int64_t *__restrict__ rev_ptr,
+                                                              const int32_t *__restrict__ rev_u, const float *__restrict__ rev_w,
+                                                              const int32_t *__restrict__ chunk_row, const int64_t *__restrict__ chunk_first,
+                                                              int64_t n_chunks, int64_t chunk, int64_t U, float *__restrict__ part) {
+  constexpr int LPC = CF_LIVE / 4;
+  const int64_t q = (int64_t)blockIdx.x * (UG_THREADS / LPC) + threadIdx.x / LPC;
+  if (q >= n_chunks) return;
+  const int c = (threadIdx.x % LPC) * 4;
+  const int64_t r = chunk_row[q];
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (r >= 0 && r < U) {
+    const int64_t first = chunk_first[q], row_end = rev_ptr[r + 1];
+    const int64_t end = (chunk > 0 && first + chunk < row_end) ? first + chunk : row_end;
+#pragma unroll 4
+    for (int64_t e = first < rev_ptr[r] ? rev_ptr[r] : first; e < end; ++e) {
+      const int64_t u = rev_u[e];
+      if (u < 0 || u >= U) continue;
+      acc = add_rn4(acc, mul_rn4(rev_w[e], *reinterpret_cast<const float4 *>(g + u * CF_W + CF_D + c)));
+    }
+  }
+  *reinterpret_cast<float4 *>(part + q * CF_LIVE + c) = acc;
+}
+
+// Backward, second launch.  A lane group of 32 lanes owns gradient row r: a user row adds its chunks' partials in chunk order,
+// S = ((p_0 + p_1) + p_2) + ..., then gx = g[r, 64:] + S; an item row hands g[r, 64:] on to the table and to its h term.
+// Columns 0 .. 63 of g are never read and nothing is written for them.
+__global__ __launch_bounds__(UG_THREADS) void cf_rows_kernel(const float *__restrict__ g, const float *__restrict__ part,
+                                                             const int64_t *__restrict__ row_chunk, int64_t n_chunks, int64_t U, int64_t N,
+                                                             float *__restrict__ dv, float *__restrict__ dt, float *__restrict__ dh_v,
+                                                             float *__restrict__ dh_t) {
+  constexpr int LPR = CF_LIVE / 4;
+  const int64_t r = (int64_t)blockIdx.x * (UG_THREADS / LPR) + threadIdx.x / LPR;
+  if (r >= N) return;
+  const int c = (threadIdx.x % LPR) * 4;                      // a column of the live 128: [0, 64) is v's, [64, 128) t's
+  const float4 gr = *reinterpret_cast<const float4 *>(g + r * CF_W + CF_D + c);
+  const bool is_t = c >= CF_D;
+  const int cc = is_t ? c - CF_D : c;
+  float4 *dst = reinterpret_cast<float4 *>((is_t ? dt : dv) + r * CF_D + cc);
+  if (r >= U) {
+    *dst = gr;
+    float *dh = is_t ? dh_t : dh_v;
+    if (dh) *reinterpret_cast<float4 *>(dh + (r - U) * CF_D + cc) = gr;
+    return;
+  }
+  int64_t q = row_chunk[r], q_end = row_chunk[r + 1];
+  q = q < 0 ? 0 : q;
+  q_end = q_end > n_chunks ? n_chunks : q_end;
+  float4 S = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (q < q_end) {
+    S = *reinterpret_cast<const float4 *>(part + q * CF_LIVE + c);
+    for (++q; q < q_end; ++q) S = add_rn4(S, *reinterpret_cast<const float4 *>(part + q * CF_LIVE + c));
+  }
+  *dst = add_rn4(gr, S);
+}
+
 static int ug_tile(int64_t U, int32_t tile_users) {
   int64_t tile = U < UG_MAX_TILE ? U : UG_MAX_TILE;
   if (tile_users > 0 && tile_users < tile) tile = tile_users;
@@ -485,4 +592,43 @@ extern "C" int chaorec_dualgnn_fuse_bwd_f32(const float *g, const float *v, cons
     hipLaunchKernelGGL(dg_fuse_bwd_kernel<128>, dim3((unsigned)((N + 7) / 8)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, v, t, weight_u,
                        rev_ptr, rev_u, rev_w, U, N, dv, dt, dw);
   return check_launch("dg_fuse_bwd_kernel");
+}
+
+static int cf_check(const char *what, int64_t U, int64_t N, int32_t k, int32_t D) {
+  if (U <= 0 || U > chaorec_usergraph_max_users() || N < U || N > 2 * chaorec_usergraph_max_users() || k < 1 || D != CF_D)
+    return fail(CHAOREC_E_INVALID, "%s: U=%lld N=%lld k=%d D=%d (1 <= U <= N, k >= 1, D is 64)", what, (long long)U, (long long)N,
+                (int)k, (int)D);
+  return CHAOREC_OK;
+}
+
+extern "C" int chaorec_cohesion_fuse_fwd_f32(const float *idr, const float *v, const float *t, const float *h_id, const float *h_v,
+                                             const float *h_t, const int32_t *epoch_idx, const float *epoch_w, int64_t U, int64_t N,
+                                             int32_t k, int32_t D, float *result, void *stream) {
+  if (!idr || !v || !t || !epoch_idx || !epoch_w || !result) return fail(CHAOREC_E_INVALID, "cohesion_fuse_fwd: NULL argument");
+  if ((h_id != nullptr) != (h_v != nullptr) || (h_id != nullptr) != (h_t != nullptr))
+    return fail(CHAOREC_E_INVALID, "cohesion_fuse_fwd: h_id, h_v, h_t are given together or not at all");
+  if (const int rc = cf_check("cohesion_fuse_fwd", U, N, k, D)) return rc;
+  hipLaunchKernelGGL(cf_fuse_fwd_kernel, dim3((unsigned)((N + 15) / 16)), dim3(UG_THREADS), 0, (hipStream_t)stream, idr, v, t, h_id, h_v,
+                     h_t, epoch_idx, epoch_w, U, N, (int)k, result);
+  return check_launch("cf_fuse_fwd_kernel");
+}
+
+extern "C" int chaorec_cohesion_fuse_bwd_f32(const float *g, const int64_t *rev_ptr, const int32_t *rev_u, const float *rev_w,
+                                             const int32_t *chunk_row, const int64_t *chunk_first, const int64_t *row_chunk,
+                                             int64_t n_chunks, int32_t chunk, int64_t U, int64_t N, int32_t D, float *part, float *dv,
+                                             float *dt, float *dh_v, float *dh_t, void *stream) {
+  if (!g || !rev_ptr || !rev_u || !rev_w || !row_chunk || !dv || !dt) return fail(CHAOREC_E_INVALID, "cohesion_fuse_bwd: NULL argument");
+  if (n_chunks < 0 || chunk < 0 || (n_chunks > 0 && (!chunk_row || !chunk_first || !part)))
+    return fail(CHAOREC_E_INVALID, "cohesion_fuse_bwd: n_chunks=%lld chunk=%d (chunk_row, chunk_first and part hold n_chunks entries)",
+                (long long)n_chunks, (int)chunk);
+  if ((dh_v != nullptr) != (dh_t != nullptr)) return fail(CHAOREC_E_INVALID, "cohesion_fuse_bwd: dh_v and dh_t are given together or not at all");
+  if (const int rc = cf_check("cohesion_fuse_bwd", U, N, 1, D)) return rc;
+  if (n_chunks > 0) {
+    hipLaunchKernelGGL(cf_chunk_kernel, dim3((unsigned)((n_chunks + 7) / 8)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, rev_ptr, rev_u,
+                       rev_w, chunk_row, chunk_first, n_chunks, (int64_t)chunk, U, part);
+    if (const int rc = check_launch("cf_chunk_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(cf_rows_kernel, dim3((unsigned)((N + 7) / 8)), dim3(UG_THREADS), 0, (hipStream_t)stream, g, part, row_chunk, n_chunks,
+                     U, N, dv, dt, dh_v, dh_t);
+  return check_launch("cf_rows_kernel");
 }

@@ -1088,7 +1088,7 @@ def dualvae_loss(mu, std_pre, xlog, sum_p, cl, kl_weight, ssl_reg):
 
 # --------------------------------------------------------------------------------------------
 # The user-user co-occurrence graph (csrc/usergraph.hip): DRAGON's user_graph_dict built, sampled and aggregated on the device;
-# DualGNN's fused node over the same structure
+# DualGNN's fused node over the same structure; COHESION's over three tables, with a chunked backward
 # --------------------------------------------------------------------------------------------
 USERGRAPH_TOPN = 200         # dualgnn-gen-u-u-matrix.py:92-103 keeps the 200 largest co-occurrence counts of a user
 USERGRAPH_MAX_N = 256        # what the build kernel's sorting network holds
@@ -1127,6 +1127,7 @@ class UserGraphStructure:
         self.nbr_len = _ug_i32(nbr_len, "nbr_len", (U,))
         self.k = 0
         self.epoch_idx = self.epoch_w = self.rev_ptr = self.rev_slot = self.rev_u = self.rev_w = self._ids = None
+        self.rev_chunks = {}      # chunk -> usergraph_rev_chunks() of the current epoch graph (COHESION's backward)
 
     @classmethod
     def from_dict(cls, user_graph_dict, num_user, n=USERGRAPH_TOPN, device="cpu"):
@@ -1144,6 +1145,7 @@ class UserGraphStructure:
         for name in ("nbr_idx", "nbr_cnt", "nbr_len", "epoch_idx", "epoch_w", "rev_ptr", "rev_slot", "rev_u", "rev_w", "_ids"):
             if getattr(self, name) is not None:
                 setattr(self, name, getattr(self, name).to(device))
+        self.rev_chunks = {}
         return self
 
     def _epoch_buffers(self, k):
@@ -1167,6 +1169,7 @@ class UserGraphStructure:
         self.epoch_idx.copy_(epoch_idx)
         self.epoch_w.copy_(epoch_w)
         self.index_epoch()
+        self.rev_chunks = {}
 
     def index_epoch(self):
         """The reverse structure of the current epoch_idx: torch's STABLE sort of the flattened slots by the user they name
@@ -1218,6 +1221,7 @@ def usergraph_sample(s, k, seed, epoch):
                                          int(seed) & (2**64 - 1), int(epoch) & (2**64 - 1), _ptr(s.epoch_idx), _ptr(s.epoch_w),
                                          _stream())
     s.index_epoch()
+    s.rev_chunks = {}
     return s.epoch_idx, s.epoch_w
 
 
@@ -1300,3 +1304,92 @@ def dualgnn_fuse(v, t, weight_u, s, num_user):
     """result[u] = x[u] + sum_j s.epoch_w[u, j] x[s.epoch_idx[u, j]] with x[r] = weight_u[r, 0] v[r] + weight_u[r, 1] t[r] for
     u < num_user, result[r] = v[r] + t[r] below: DualGNN's whole table from the two modality tables in one launch."""
     return _DualGNNFuse.apply(v, t, weight_u, s, num_user)
+
+
+COHESION_DIM = 64            # Model/COHESION.py:92 hard-codes dim_latent; the cf_* kernels are instantiated for it alone
+COHESION_CHUNK = 64          # entries of a reverse list one lane group sums in the backward
+
+
+class RevChunks:
+    """The reverse lists of an epoch graph cut into chunks of `chunk` entries (0: one chunk per non-empty list):
+    chunk_row int32 [n_chunks] (the row a chunk belongs to), chunk_first int64 [n_chunks] (its first entry in rev_u / rev_w),
+    row_chunk int64 [U + 1] (row r's chunks are [row_chunk[r], row_chunk[r + 1]), in list order)."""
+
+    def __init__(self, chunk, chunk_row, chunk_first, row_chunk):
+        self.chunk, self.n_chunks = int(chunk), int(chunk_row.numel())
+        self.chunk_row, self.chunk_first, self.row_chunk = chunk_row, chunk_first, row_chunk
+
+
+def usergraph_rev_chunks(s, chunk=COHESION_CHUNK):
+    """Index the chunks of s.rev_ptr (once per epoch graph; tensor ops and one read of the chunk count) -> RevChunks, kept
+    in s.rev_chunks[chunk] until the next usergraph_sample / set_epoch."""
+    chunk = int(chunk)
+    if chunk < 0 or chunk > 2**31 - 1:
+        raise ValueError(f"usergraph: chunk = {chunk} (0 = one chunk per list, else the entries per chunk)")
+    if s.k < 1:
+        raise ValueError("usergraph: no epoch graph yet (usergraph_sample / set_epoch)")
+    U, dev = s.num_user, s.rev_ptr.device
+    length = s.rev_ptr[1:] - s.rev_ptr[:-1]
+    per_row = torch.div(length + (chunk - 1), chunk, rounding_mode="floor") if chunk > 0 else (length > 0).to(torch.int64)
+    row_chunk = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(per_row, 0, out=row_chunk[1:])
+    n_chunks = int(row_chunk[-1])
+    rows = torch.repeat_interleave(torch.arange(U, dtype=torch.int64, device=dev), per_row, output_size=n_chunks)
+    within = torch.arange(n_chunks, dtype=torch.int64, device=dev) - row_chunk[rows]
+    chunk_first = (s.rev_ptr[rows] + within * chunk).contiguous()
+    out = RevChunks(chunk, rows.to(torch.int32).contiguous(), chunk_first, row_chunk)
+    s.rev_chunks[chunk] = out
+    return out
+
+
+class _CohesionFuse(torch.autograd.Function):
+    """(idr, v, t [N, 64]; h_id, h_v, h_t [I, 64] or None) -> result [N, 192] (Model/COHESION.py:340-359): none of the
+    [N, 192] concatenation, user_rep, features[user_graph] [U, k, 192] or h_u exists in memory, forward or backward."""
+
+    @staticmethod
+    def forward(ctx, idr, v, t, h_id, h_v, h_t, s, num_user, chunk):
+        _need_cuda(idr, v, t, s.epoch_idx)
+        D = COHESION_DIM
+        if v.dim() != 2 or v.shape[1] != D:
+            raise ValueError(f"cohesion_fuse: v is {tuple(v.shape)}, the kernels are built for D = {D}")
+        U, N = int(num_user), int(v.shape[0])
+        if U != s.num_user or N < U:
+            raise ValueError(f"cohesion_fuse: {U} users, a table of {N} rows, a user graph of {s.num_user} users")
+        idr, v, t = (_vae_f32("cohesion_fuse", a, n, (N, D)) for a, n in ((idr, "idr"), (v, "v"), (t, "t")))
+        hs = (h_id, h_v, h_t)
+        if any(h is None for h in hs) != all(h is None for h in hs):
+            raise ValueError("cohesion_fuse: h_id, h_v, h_t are given together or not at all")
+        has_h = h_id is not None
+        if has_h:
+            _need_cuda(*hs)
+            h_id, h_v, h_t = (_vae_f32("cohesion_fuse", a, n, (N - U, D)) for a, n in zip(hs, ("h_id", "h_v", "h_t")))
+        if s.k < 1:
+            raise ValueError("cohesion_fuse: no epoch graph yet (usergraph_sample / set_epoch)")
+        ctx.chunks = s.rev_chunks.get(int(chunk)) or usergraph_rev_chunks(s, chunk)
+        out = torch.empty((N, 3 * D), dtype=torch.float32, device=v.device)
+        _lib.load().chaorec_cohesion_fuse_fwd_f32(_ptr(idr), _ptr(v), _ptr(t), _ptr(h_id), _ptr(h_v), _ptr(h_t), _ptr(s.epoch_idx),
+                                                  _ptr(s.epoch_w), U, N, s.k, D, _ptr(out), _stream())
+        ctx.s, ctx.U, ctx.N, ctx.has_h = s, U, N, has_h
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        s, U, N, c, D = ctx.s, ctx.U, ctx.N, ctx.chunks, COHESION_DIM
+        g = _f32c(g)
+        dev = g.device
+        dv, dt = torch.empty((N, D), dtype=torch.float32, device=dev), torch.empty((N, D), dtype=torch.float32, device=dev)
+        dh_v = torch.empty((N - U, D), dtype=torch.float32, device=dev) if ctx.has_h else None
+        dh_t = torch.empty((N - U, D), dtype=torch.float32, device=dev) if ctx.has_h else None
+        part = torch.empty((c.n_chunks, 2 * D), dtype=torch.float32, device=dev)     # every row is written before it is read
+        _lib.load().chaorec_cohesion_fuse_bwd_f32(_ptr(g), _ptr(s.rev_ptr), _ptr(s.rev_u), _ptr(s.rev_w), _ptr(c.chunk_row),
+                                                  _ptr(c.chunk_first), _ptr(c.row_chunk), c.n_chunks, c.chunk, U, N, D, _ptr(part),
+                                                  _ptr(dv), _ptr(dt), _ptr(dh_v), _ptr(dh_t), _stream())
+        return None, dv, dt, None, dh_v, dh_t, None, None, None
+
+
+def cohesion_fuse(idr, v, t, h_id, h_v, h_t, s, num_user, chunk=COHESION_CHUNK):
+    """result[u] = x[u] + sum_j s.epoch_w[u, j] x[s.epoch_idx[u, j]] with x[r] = (idr[r] | v[r] | t[r]) for u < num_user,
+    result[r] = x[r] + (h_id | h_v | h_t)[r - num_user] below (x[r] when the h tables are None): COHESION's whole [N, 192]
+    table in one launch.  idr and h_id receive no gradient (the reference detaches the id third).  The backward sums every
+    reverse list in chunks of `chunk` entries (0: unchunked) and adds the partials in chunk order: see the header."""
+    return _CohesionFuse.apply(idr, v, t, h_id, h_v, h_t, s, num_user, chunk)

@@ -12,7 +12,7 @@ import torch
 from .utils import EarlyStopping, EvalLists, gene_metrics, gene_metrics_device
 
 MMGCN_STYLE = ("MMGCN", "GRCN")
-PRE_EPOCH = ("FREEDOM", "LayerGCN", "POWERec", "DRAGON", "DualGNN")     # reference train_and_evaluate.py:555
+PRE_EPOCH = ("FREEDOM", "LayerGCN", "POWERec", "DRAGON", "DualGNN", "COHESION")     # reference train_and_evaluate.py:555
 E_STEP = ("NCL", "VGCL")                # reference train_and_evaluate.py:107-114, :116-125
 BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate.py:96-103: the first batch of an epoch rebuilds the item graphs
 # eager launches: clustering with host decisions inside the step (NCL, VGCL), an operand whose structure is rebuilt per epoch

@@ -1133,6 +1133,32 @@ int chaorec_dualgnn_fuse_bwd_f32(const float *g, const float *v, const float *t,
                                  const int32_t *rev_u, const float *rev_w, int64_t U, int64_t N, int32_t D, float *dv, float *dt,
                                  float *dw, void *stream);
 
+/* Model/COHESION.py:340-359 in one pass over the whole result table of N = U + I rows.  idr, v, t fp32 [N, 64]: the three
+ * modality tables (id, visual, textual), x[r, :] = (idr[r, :] | v[r, :] | t[r, :]), 192 floats that are never concatenated.
+ * h_id, h_v, h_t fp32 [I, 64]: the item-graph terms mm_adj^L table[U:], all three given or all three NULL (mm_layers = 0).
+ * result [N, 192]: result[u] = x[u] + sum_j epoch_w[u, j] x[epoch_idx[u, j]] for u < U (ascending j, product and add
+ * rounded separately, the residual last; a slot whose index lies outside [0, U) is skipped); result[r] = x[r] + (h_id |
+ * h_v | h_t)[r - U] for r >= U, x[r] itself without h tables.  N == U is legal.  D is 64. */
+int chaorec_cohesion_fuse_fwd_f32(const float *idr, const float *v, const float *t, const float *h_id, const float *h_v,
+                                  const float *h_t, const int32_t *epoch_idx, const float *epoch_w, int64_t U, int64_t N, int32_t k,
+                                  int32_t D, float *result, void *stream);
+/* Its backward from g [N, 192] to dv, dt [N, 64] and dh_v, dh_t [I, 64] (both or neither NULL).  The id third is detached
+ * (Model/COHESION.py:321): columns 0 .. 63 of g are never read and nothing is written for them.  Item row r >= U:
+ * dv[r] = dh_v[r - U] = g[r, 64:128], dt[r] = dh_t[r - U] = g[r, 128:192].  User row r: gx[r] = g[r, 64:192] + S_r,
+ * dv[r] = gx[r, :64], dt[r] = gx[r, 64:].  THE ORDER OF S_r: row r's reverse list, entries [rev_ptr[r], rev_ptr[r + 1]) of
+ * rev_u / rev_w (the structure of chaorec_usergraph_aggregate_bwd_f32), is cut into consecutive chunks of `chunk` entries
+ * (the last may be shorter; chunk = 0: the whole list is one chunk); a chunk's partial is p_c = ((0 + w_1 g_1) + w_2 g_2)
+ * + ... in list order, the row's sum S_r = ((p_0 + p_1) + p_2) + ... in chunk order, every product and add rounded
+ * separately; an empty list gives S_r = 0.  The chunks are listed by the caller: chunk_row int32 [n_chunks] (the row a
+ * chunk belongs to), chunk_first int64 [n_chunks] (its first entry), row_chunk int64 [U + 1] (row r's chunks are
+ * [row_chunk[r], row_chunk[r + 1]), ascending); part fp32 [n_chunks, 128] is the workspace of the partials.  Two launches,
+ * a lane group per chunk and then a lane group per row; no atomics: the same bits every run, whatever the grid.  Every
+ * element of dv, dt, dh_v, dh_t is written.  D is 64. */
+int chaorec_cohesion_fuse_bwd_f32(const float *g, const int64_t *rev_ptr, const int32_t *rev_u, const float *rev_w,
+                                  const int32_t *chunk_row, const int64_t *chunk_first, const int64_t *row_chunk, int64_t n_chunks,
+                                  int32_t chunk, int64_t U, int64_t N, int32_t D, float *part, float *dv, float *dt, float *dh_v,
+                                  float *dh_t, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
