@@ -1159,6 +1159,51 @@ int chaorec_cohesion_fuse_bwd_f32(const float *g, const int64_t *rev_ptr, const 
                                   int32_t chunk, int64_t U, int64_t N, int32_t D, float *part, float *dv, float *dt, float *dh_v,
                                   float *dh_t, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * MVGAE (Model/MVGAE.py) -- csrc/mvgae.hip.  Additive to ABI 16: new names only.
+ * D = 64 is what the kernels tile (chaorec_mvgae_check_shape: CHAOREC_E_INVALID otherwise).  16 lanes hold a row (one
+ * float4 each), a wave chaorec_mvgae_rows_per_wave() = 4 rows, a workgroup chaorec_mvgae_rows_per_block() = 16.  fp32, no
+ * atomics: every sum has one owner and a fixed order.  state int64 [2]: chaorec_mvgae_tick does state[0] += 1,
+ * state[1] = state[0]; every draw is keyed (seed, state[1], salt, counters) and a backward redraws its forward's values.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_mvgae_check_shape(int32_t D);
+int64_t chaorec_mvgae_rows_per_wave(void);
+int64_t chaorec_mvgae_rows_per_block(void);
+int chaorec_mvgae_tick(int64_t *state, void *stream);
+/* The conv epilogue, per row r of s [N, 64]: a = s[r] + bias, n = |a|, q = a / max(n, 1e-12), y = leaky_relu(q m, 0.01);
+ * m = 1 in evaluation; in training 1 / 0.9 for a kept element and 0 for a dropped one, kept = keep[r, d] != 0 (uint8 [N, 64])
+ * or, keep NULL, uniform(seed, state[1], salt, r * 64 + d) >= 0.1.  salt in 0 .. 15: the conv's number. */
+int chaorec_mvgae_conv_fwd_f32(const float *s, const float *bias, int64_t N, const uint8_t *keep, uint64_t seed,
+                               const int64_t *state, int32_t salt, int32_t training, float *y, void *stream);
+/* gs [N, 64] from gy: gq = gy (q m > 0 ? 1 : 0.01) m, gs = (gq - q <gq, q>) / n for n >= 1e-12, gq / 1e-12 below; q, n, m
+ * recomputed from s, bias and the same draw.  The bias gradient is the column sum of gs. */
+int chaorec_mvgae_conv_bwd_f32(const float *gy, const float *s, const float *bias, int64_t N, const uint8_t *keep,
+                               uint64_t seed, const int64_t *state, int32_t salt, int32_t training, float *gs, void *stream);
+/* The tail over six [N, 64] tables (mean, log-variance of the visual, textual, collaborative view) and a batch of B
+ * samples of global row ids in [0, N).  PoE(a, b): t = 1 / (exp(l) + 1e-8), mean (ma ta + mb tb) / (ta + tb), log-variance
+ * log(1 / (ta + tb)); P = PoE(PoE(V, T), C).  Views x = P, V, T, C: lc = min(l, 10), KL_x = -0.5 / N sum(1 + lc - m^2 -
+ * exp(lc)), z = m + (eps 0.1) exp(0.5 lc) in training (m otherwise), BPR_x = -1 / B sum log(sigmoid(<zu, zp> - <zu, zn>) +
+ * 1e-5).  eps: given [4, N, 64], or NULL: normal(seed, state[1], 16 + x, row, d).  Written whole: Pm [N, 64]; zrows
+ * [4, 3, B, 64] (the z rows of user, positive, negative); eps_out likewise unless NULL; bpr, coef [4, B] (a sample's term and
+ * its derivative by the score difference, 1 / B included; both from z rows and scores evaluated in double); out [9] = total,
+ * BPR_P V T C, KL_P V T C (summed in double: strided per thread, then a tree, the same order every run).  workspace:
+ * chaorec_mvgae_tail_workspace_bytes(N) bytes, 8-byte aligned.  Three launches. */
+size_t chaorec_mvgae_tail_workspace_bytes(int64_t N);
+int chaorec_mvgae_tail_fwd_f32(const float *Vm, const float *Vl, const float *Tm, const float *Tl, const float *Cm,
+                               const float *Cl, int64_t N, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t B,
+                               const float *eps, uint64_t seed, const int64_t *state, int32_t training, float kl_weight, float *Pm,
+                               float *zrows, float *eps_out, float *bpr, float *coef, void *workspace, size_t workspace_bytes,
+                               float *out, void *stream);
+/* Its backward, one launch, every row of the six gradient tables written by its one owner: the KL terms, plus the dz of the
+ * slots perm[slot_ptr[r] .. slot_ptr[r + 1]) -- perm int64 [3B] = a stable sort of [users; pos; neg], slot_ptr int64 [N + 1]
+ * -- added in that order (as user, as positive, as negative, ascending sample number), then the reparametrisation (the
+ * clamp passes gradient where l <= 10) and both PoE stages, times gtotal[0]. */
+int chaorec_mvgae_tail_bwd_f32(const float *Vm, const float *Vl, const float *Tm, const float *Tl, const float *Cm,
+                               const float *Cl, int64_t N, const int64_t *slot_ptr, const int64_t *perm, int64_t B,
+                               const float *zrows, const float *coef, const float *eps, uint64_t seed, const int64_t *state,
+                               int32_t training, float kl_weight, const float *gtotal, float *dVm, float *dVl, float *dTm,
+                               float *dTl, float *dCm, float *dCl, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
