@@ -258,3 +258,26 @@ class DeviceBatchSampler:
                 yield users, pos, neg, second
             else:
                 yield users, pos, neg
+
+
+class DeviceUserBatches:
+    """Epoch iterator over shuffled batches of user ids on the device: DiffMM's diffusion loader (reference main.py:202-203,
+    DataLoader(DiffusionData, batch_size, shuffle=True)) without DiffusionData's dense [U, I] host matrix -- a batch is its
+    user ids, the rows are written from the history CSR by the launch that noises them.  Every user once per epoch, the
+    short last batch kept; shuffle=False walks the users in order (the reference's test_diffusionLoader)."""
+
+    def __init__(self, num_user, batch_size, device, seed=42, shuffle=True):
+        self.num_user, self.batch_size, self.device, self.shuffle = int(num_user), int(batch_size), device, shuffle
+        self.gen = torch.Generator(device=device)
+        self.gen.manual_seed(seed)
+
+    def __len__(self):
+        return (self.num_user + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        if self.shuffle:
+            order = torch.randperm(self.num_user, device=self.device, generator=self.gen)
+        else:
+            order = torch.arange(self.num_user, device=self.device)
+        for b in range(len(self)):
+            yield order[b * self.batch_size:(b + 1) * self.batch_size]

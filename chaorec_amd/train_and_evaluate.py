@@ -20,7 +20,8 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 # rate is np.random.random(), Model/SelfCF.py:55: a capture would freeze it), host-built sequence batches (LightGT).
 # SimGCL / XSimGCL / SLMRec draw only with rand_like on the device generator, which a captured step advances per replay:
 # they are captured (round 5: 2 x the eager epoch rate at baby size, tools/capture_family_probe.py).
-NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL")    # (MMSSL: two optimizers per batch, its own loop)
+# DiffMM: three phases per epoch, the graphs its loss() multiplies with are rebuilt in the second.
+NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM")    # (MMSSL: two optimizers per batch, its own loop)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):
@@ -75,11 +76,55 @@ def _train_epoch_mmssl(model, train_loader, optimizer):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_diffmm(model, train_loader, optimizer, diffusion_loader=None):
+    """reference train_and_evaluate.py:140-244 in its three phases: (1) one pass of the diffusion loader, per batch a step of
+    each denoiser under two Adam optimizers created anew every epoch (:142-145: their moments restart); (2) the two modal
+    graphs rebuilt from the denoised rows; (3) the BPR steps over them.  The returned sum is the BPR losses', as there.
+    diffusion_loader: user-id batches; by default a dataload.DeviceUserBatches at the train loader's batch size, kept on
+    the model between epochs."""
+    if diffusion_loader is None:
+        diffusion_loader = model.__dict__.get("_diffusion_loader")
+        if diffusion_loader is None:
+            from .dataload import DeviceUserBatches
+            diffusion_loader = model.__dict__["_diffusion_loader"] = DeviceUserBatches(
+                model.num_user, train_loader.batch_size, model.device, getattr(train_loader, "seed", 42))
+    lr = optimizer.param_groups[0]['lr']
+    denoise_opt_image = torch.optim.Adam(model.denoise_model_image.parameters(), lr=lr, weight_decay=0)
+    denoise_opt_text = torch.optim.Adam(model.denoise_model_text.parameters(), lr=lr, weight_decay=0)
+    diff_sum = None
+    for users in diffusion_loader:
+        denoise_opt_image.zero_grad()
+        denoise_opt_text.zero_grad()
+        loss_image, loss_text = model.diffusion_step(users)
+        loss = loss_image + loss_text
+        loss.backward()
+        denoise_opt_image.step()
+        denoise_opt_text.step()
+        d = loss.detach()
+        diff_sum = d.clone() if diff_sum is None else diff_sum.add_(d)
+    if diff_sum is not None:
+        logging.info('Diffusion Loss (sum over %d steps) %.6f' % (len(diffusion_loader), float(diff_sum.item())))
+    logging.info('Start to re-build UI matrix')
+    image_adj, text_adj = model.rebuild_graphs(diffusion_loader)
+    logging.info('UI matrix built!')
+    sum_loss = None
+    for users, pos_items, neg_items in train_loader:
+        optimizer.zero_grad()
+        loss = model.loss(users, pos_items, neg_items, image_adj, text_adj)
+        loss.backward()
+        optimizer.step()
+        d = loss.detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    return float(sum_loss.item()) if sum_loss is not None else 0.0
+
+
 def train(model, train_loader, optimizer, model_name="LightGCN", graphed=None):
     """One epoch.  `graphed` (optim.GraphedTrainStep) replays the captured step for full-size batches."""
     model.train()
     if model_name == "MMSSL":
         return _train_epoch_mmssl(model, train_loader, optimizer)
+    if model_name == "DiffMM":
+        return _train_epoch_diffmm(model, train_loader, optimizer)
     if graphed is not None and getattr(graphed, "draws_in_launch", False):
         return _train_epoch_in_launch(model, train_loader, optimizer, graphed)
     sum_loss = None

@@ -1204,6 +1204,46 @@ int chaorec_mvgae_tail_bwd_f32(const float *Vm, const float *Vl, const float *Tm
                                int32_t training, float kl_weight, const float *gtotal, float *dVm, float *dVl, float *dTm,
                                float *dTl, float *dCm, float *dCl, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * DiffMM (Model/DiffMM.py) -- csrc/diffmm.hip.  Additive to ABI 16: new names only.  fp32, no float atomics, no scratch.
+ * The embedding width of r and F is 64; H (the denoiser's hidden width) is a multiple of 4
+ * (chaorec_diffmm_check_shape: CHAOREC_E_INVALID otherwise).  The output layer runs on the f32 MFMA pipe
+ * (v_mfma_f32_32x32x2_f32): exact fp32 products in a k-ascending chain per element, as chaorec_gemm_f32, cut into segments
+ * of 64 k whose values are added in ascending order -- not the three-plane bf16 split; chaorec_diffmm_tiles gives its tile (128 x 128 x 16), chaorec_diffmm_rows_per_block the rows of
+ * a workgroup of the rows launch (4, a wave each).
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_diffmm_check_shape(int64_t B, int64_t I, int64_t H, int32_t D);
+int chaorec_diffmm_tiles(int32_t *bm, int32_t *bn, int32_t *bk);
+int64_t chaorec_diffmm_rows_per_block(void);
+/* The denoiser's input rows without the dense [U, I] matrix and without a [B, I] batch, noise or x_t tensor
+ * (dataload.DiffusionData, GaussianDiffusion.q_sample :580-592 called at :627-632, nn.Dropout(0.5) in Denoise.forward
+ * :458-459).  Row b is user users[b]'s history row of the CSR (rowptr int64 [U + 1], col int32 local item ids; an id outside
+ * [0, U) or a column outside [0, I) counts as absent): x0[b, i] in {0, 1}, x_t = fl(fl(a_row[b] x0) + fl(s_row[b] n)) -- two
+ * roundings, no fused multiply-add --, x_in = kept ? fl(2 x_t) : 0.  n = noise[b, i] (fp32 [B, I]) or, noise NULL, a
+ * Box-Muller normal keyed (seed, step, 2 salt, user id, item id); kept = keep[b, i] != 0 (uint8 [B, I]) or, keep NULL, a
+ * uniform keyed (seed, step, 2 salt + 1, user id, item id) < 1/2: a draw does not depend on the row's place in the batch.
+ * plain != 0: x_in = x0 (a_row, s_row, noise, keep unused): the multi-hot rows p_sample starts from at steps = 0 (:549-550).
+ * x_in fp32 [B, ld], ld = I rounded up to a multiple of 4, columns I .. ld written 0; bits uint32 [B, ceil(I / 32)]: bit
+ * i % 32 of word i / 32 is x0[b, i].  One launch, one wave per row. */
+int chaorec_diffmm_rows_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col, int64_t I,
+                            int64_t ld, const float *a_row, const float *s_row, const float *noise, const uint8_t *keep,
+                            uint64_t seed, uint64_t step, uint32_t salt, int32_t plain, float *x_in, uint32_t *bits,
+                            void *stream);
+/* The output layer of Denoise.forward (:468-471) with GaussianDiffusion.training_losses' mse, weight, diff_loss and gc_loss
+ * (:640-658) and the mean over the batch of both, in one pass; model_output, the squared error and usr_model_embeds do
+ * not exist.  out = h W_out^T + b_out (h [B, H] row stride ldh, W_out [I, H] row stride ldw), err = out - x0 (x0 from bits
+ * as above), r fp32 [B, 64] = out F - x0 E supplied by the caller as h (W_out^T F) + b_out F - x0 E, F fp32 [I, 64]:
+ *   d_out[b, i] = c_row[b] err[b, i] + kf <r_b, F_i>        (fp32 [B, ldd], columns I .. ldd written 0)
+ *   diff_rows[b] = w[b] / I sum_i err^2   (double; w double [B])      gc_rows[b] = mean_d r[b, d]^2
+ *   loss[0] = mean_b diff_rows + e_loss mean_b gc_rows
+ * With c_row[b] = 2 w[b] / (B I) and kf = 2 e_loss / (B 64), d_out is d loss / d out.  part fp32 [B, ceil(I / 128)] holds
+ * every row's sum of err^2 per item tile; a second launch adds them in tile order, in double: no atomics, the same bits
+ * every run. */
+int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const float *W_out, int64_t ldw, const float *b_out,
+                                const uint32_t *bits, const float *r, const float *F, const double *w, const float *c_row,
+                                float kf, float e_loss, int64_t B, int64_t I, int64_t H, float *d_out, int64_t ldd,
+                                float *part, double *diff_rows, float *gc_rows, float *loss, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

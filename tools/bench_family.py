@@ -21,7 +21,7 @@ from chaorec_amd.optim import FusedAdam  # noqa: E402
 
 ALL = ["LightGCN", "NGCF", "LayerGCN", "BPR", "VBPR", "MGCN", "FREEDOM", "MMGCN", "SimGCL", "XSimGCL", "NCL", "SelfCF", "SLMRec", "MCLN",
        "DHCF", "LGMRec", "POWERec", "SMORE", "GUME", "MMGCL", "FKAN_GCF", "VGCL", "DDRec", "DCCF", "MICRO", "LATTICE", "MENTOR", "HCCF",
-       "LightGCL", "SGL", "BM3", "MGCL", "MMSSL", "GRCN", "MGAT", "DGCF", "MultVAE", "MacridVAE", "DualVAE", "MVGAE"]
+       "LightGCL", "SGL", "BM3", "MGCL", "MMSSL", "GRCN", "MGAT", "DGCF", "MultVAE", "MacridVAE", "DualVAE", "MVGAE", "DiffMM"]
 models = sys.argv[1:] or ALL
 os.chdir(tempfile.mkdtemp())
 logging.disable(logging.CRITICAL)
@@ -35,7 +35,7 @@ for name in models:
             setattr(args, p, cfg[p][0])
         cmain.setup_seed(args.seed)
         needs = name in ("MMGCN", "FREEDOM", "MGCN", "VBPR", "SLMRec", "MCLN", "POWERec", "LGMRec", "SMORE", "MMGCL", "LightGT", "GUME",
-                         "DDRec", "MICRO", "MENTOR", "BM3", "MGCL", "LATTICE", "MMSSL", "GRCN", "MGAT", "MVGAE")
+                         "DDRec", "MICRO", "MENTOR", "BM3", "MGCL", "LATTICE", "MMSSL", "GRCN", "MGAT", "MVGAE", "DiffMM")
         train, val, test, uid, U, I, v, t = dataload.data_load("sports", has_v=needs, has_t=needs, data_root=args.data_root, synthetic=False)
         loader = dataload.DeviceBatchSampler(U, I, uid, train, args.batch_size, dev, name, args.seed)
         args.num_user, args.num_item = U, I
