@@ -12,7 +12,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import dataload
-from .Model import (BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
+from .Model import (AdaGCL, BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
                     SMORE, VBPR, VGCL, XSimGCL)
 from .arg_parser import load_yaml_config, parse_args
 from .train_and_evaluate import train_and_evaluate
@@ -153,6 +153,10 @@ def build_model(args, num_user, num_item, train_data, user_item_dict, v_feat, t_
         'DiffMM': lambda: DiffMM(num_user, num_item, train_data, user_item_dict, v_feat, t_feat, dim_E, args.reg_weight,
                                  args.n_layers, args.ssl_alpha, args.ssl_temp, args.ris_lambda, args.e_loss, args.rebuild_k,
                                  device),
+        # (main.py:327-328) two learned view generators over one fixed structure: the edge gate from two per-node scores and
+        # the per-edge keep MLP on the f32 MFMA pipe, csrc/adagcl.hip; three optimizers per batch (train_and_evaluate.py:72-97)
+        'AdaGCL': lambda: AdaGCL(num_user, num_item, train_data, user_item_dict, dim_E, args.reg_weight, args.n_layers,
+                                 args.ssl_temp, args.ssl_alpha, device),
     }
     if args.Model == 'COHESION':   # Model/COHESION.py:96-99 reads the same file
         COHESION.user_graph_path = os.path.join(args.data_root, args.data_path, 'user_graph_dict.npy')

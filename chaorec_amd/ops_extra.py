@@ -1647,3 +1647,107 @@ def diffmm_denoise_loss(h, W_out, b_out, bits, x0E, F, w, e_loss):
     diffmm_rows; x0E [B, 64] = the batch's history-row sums of the item embeddings; F [I, 64] the modality's projected
     features; w float64 [B] the SNR weight.  x0E and F carry no gradient (the reference detaches them)."""
     return _DiffMMDenoiseLoss.apply(h, W_out, b_out, bits, x0E.detach(), F.detach(), w, float(e_loss))
+
+
+# --------------------------------------------------------------------------------------------
+# AdaGCL (csrc/adagcl.hip): the per-entry work of its two view generators over one graph.DropoutStructure
+# --------------------------------------------------------------------------------------------
+ADAGCL_DIM = 64              # the row width the keep kernel tiles
+
+
+def adagcl_check_shape(D):
+    if int(D) != ADAGCL_DIM:
+        raise ValueError(f"AdaGCL: dim_E={D}; the kernels tile D={ADAGCL_DIM}")
+
+
+def adagcl_tick(state):
+    """state int64 [2] on the device: [0] += 1, [1] = [0] -- the step the device draws are keyed by."""
+    _need_cuda(state)
+    _lib.load().chaorec_adagcl_tick(_ptr(state), _stream())
+
+
+def _adagcl_parts(structure, device):
+    n = int(_lib.load().chaorec_adagcl_rows_per_block())
+    n_part = (structure.n_rows + n - 1) // n
+    return torch.empty(n_part, dtype=torch.float32, device=device), n_part
+
+
+class _AdaGCLEdgeGate(torch.autograd.Function):
+    """Two per-node scores -> (val [E], l0 [1], m [E], d [N], u [E] or None) (csrc/adagcl.hip (a), (b))."""
+
+    @staticmethod
+    def forward(ctx, s_nb, s_self, b_att, st, beta, eps, training, state, seed, salt, u):
+        _need_cuda(s_nb, s_self, b_att, st.rowptr, state, u)
+        N, E = st.n_rows, st.nnz
+        s_nb = _vae_f32("adagcl", s_nb.detach().contiguous(), "s_nb", (N,))
+        s_self = _vae_f32("adagcl", s_self.detach().contiguous(), "s_self", (N,))
+        b_att = _vae_f32("adagcl", b_att.detach().contiguous().reshape(-1), "b_att", (1,))
+        if u is not None:
+            u = _vae_f32("adagcl", u, "u", (E,))
+        elif training and state is None:
+            raise ValueError("adagcl: the training form needs given draws u or a device step counter")
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=s_nb.device)  # noqa: E731
+        m, S, d, val, l0 = f(E), f(N), f(N), f(E), f(1)
+        u_used = u if (u is not None or not training) else f(E)
+        part, n_part = _adagcl_parts(st, s_nb.device)
+        _lib.load().chaorec_adagcl_gate_fwd_f32(_ptr(st.rowptr), _ptr(st.col), _ptr(st.entry_row), N, E, _ptr(s_nb), _ptr(s_self),
+                                                _ptr(b_att), float(beta), float(eps), int(bool(training)), _ptr(u), int(seed),
+                                                _ptr(state), int(salt), _ptr(m), _ptr(S), _ptr(d), _ptr(val), _ptr(l0),
+                                                _ptr(u_used if u is None else None), _ptr(part), n_part, _stream())
+        ctx.st, ctx.beta, ctx.training = st, float(beta), bool(training)
+        ctx.save_for_backward(s_nb, s_self, b_att, m, S, d, u_used if training else None)
+        ctx.mark_non_differentiable(m, d)
+        if training:
+            ctx.mark_non_differentiable(u_used)
+        return val, l0, m, d, (u_used if training else None)
+
+    @staticmethod
+    def backward(ctx, g_val, g_l0, *_):
+        s_nb, s_self, b_att, m, S, d, u = ctx.saved_tensors
+        st = ctx.st
+        N, E = st.n_rows, st.nnz
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=s_nb.device)  # noqa: E731
+        g_val = torch.zeros(E, dtype=torch.float32, device=s_nb.device) if g_val is None else _f32c(g_val)
+        g_l0 = None if g_l0 is None else _f32c(g_l0).reshape(-1)
+        g_logit, g_S, g_nb, g_self, g_b = f(E), f(N), f(N), f(N), f(1)
+        part, n_part = _adagcl_parts(st, s_nb.device)
+        _lib.load().chaorec_adagcl_gate_bwd_f32(_ptr(st.rowptr), _ptr(st.col), _ptr(st.transpose_entry), N, E, _ptr(s_nb), _ptr(s_self),
+                                                _ptr(b_att), ctx.beta, int(ctx.training), _ptr(u), _ptr(m), _ptr(S), _ptr(d),
+                                                _ptr(g_val), _ptr(g_l0), _ptr(g_logit), _ptr(g_S), _ptr(g_nb), _ptr(g_self), _ptr(g_b),
+                                                _ptr(part), n_part, _stream())
+        return g_nb, g_self, g_b, None, None, None, None, None, None, None, None
+
+
+def adagcl_edge_gate(structure, s_nb, s_self, b_att, beta, eps, training, state, seed, salt, u=None, return_parts=False):
+    """DenoisingNet's hard-concrete gate over the stored entries of `structure` (a graph.DropoutStructure) from the two
+    per-node scores: -> (val [E], l0 [1]); return_parts adds (m [E], d [N], u [E] -- the draws used, None in evaluation).
+    training: the noised form at temperature beta with eps on the row sums; u: given draws in [1e-7, 1 - 1e-7], else drawn in
+    the launch keyed (seed, state[1], salt).  b_att: the one-element bias tensor.  One autograd node."""
+    out = _AdaGCLEdgeGate.apply(s_nb, s_self, b_att.reshape(-1), structure, beta, eps, bool(training), state, seed, salt, u)
+    return out if return_parts else out[:2]
+
+
+def adagcl_edge_keep(structure, z, W1, b1, w2, b2, vals, return_logits=False):
+    """vgae.generate's keep decision per stored entry (csrc/adagcl.hip (c)); no gradient.  z [N, 64], W1 [64, 64], b1 [64],
+    w2 [64] or [1, 64], b2 [1], vals [E] -> (out [E] = kept ? vals / fl32(kept / E) : +0, keep bool [E], kept int64 [1] on the
+    device[, logits [E]])."""
+    _need_cuda(z, W1, b1, w2, b2, vals, structure.rowptr)
+    N, E = structure.n_rows, structure.nnz
+    with torch.no_grad():
+        if z.dim() != 2:
+            raise ValueError(f"adagcl: z is {tuple(z.shape)}, expected [N, {ADAGCL_DIM}]")
+        adagcl_check_shape(z.shape[1])
+        z = _vae_f32("adagcl", z.detach().contiguous(), "z", (N, ADAGCL_DIM))
+        W1 = _vae_f32("adagcl", W1.detach().contiguous(), "W1", (ADAGCL_DIM, ADAGCL_DIM))
+        b1 = _vae_f32("adagcl", b1.detach().contiguous(), "b1", (ADAGCL_DIM,))
+        w2 = _vae_f32("adagcl", w2.detach().contiguous().reshape(-1), "w2", (ADAGCL_DIM,))
+        b2 = _vae_f32("adagcl", b2.detach().contiguous().reshape(-1), "b2", (1,))
+        vals = _vae_f32("adagcl", vals.detach().contiguous(), "vals", (E,))
+        keep = torch.empty(E, dtype=torch.uint8, device=z.device)
+        out = torch.empty(E, dtype=torch.float32, device=z.device)
+        kept = torch.empty(1, dtype=torch.int64, device=z.device)
+        logits = torch.empty(E, dtype=torch.float32, device=z.device) if return_logits else None
+        _lib.load().chaorec_adagcl_keep_f32(_ptr(z), N, _ptr(structure.entry_row), _ptr(structure.col), E, _ptr(W1), _ptr(b1), _ptr(w2),
+                                            _ptr(b2), _ptr(vals), _ptr(keep), _ptr(out), _ptr(kept), _ptr(logits), _stream())
+    res = (out, keep.to(torch.bool), kept)
+    return res + (logits,) if return_logits else res

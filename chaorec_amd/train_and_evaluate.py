@@ -21,7 +21,7 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 # SimGCL / XSimGCL / SLMRec draw only with rand_like on the device generator, which a captured step advances per replay:
 # they are captured (round 5: 2 x the eager epoch rate at baby size, tools/capture_family_probe.py).
 # DiffMM: three phases per epoch, the graphs its loss() multiplies with are rebuilt in the second.
-NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM")    # (MMSSL: two optimizers per batch, its own loop)
+NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL")    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):
@@ -76,6 +76,40 @@ def _train_epoch_mmssl(model, train_loader, optimizer):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_adagcl(model, train_loader, optimizer):
+    """reference train_and_evaluate.py:72-97: three Adam optimizers created anew every epoch (their moments restart) -- `opt` over
+    ALL parameters, one per generator (generator 2's with eps = 0.001) -- and per batch four losses: loss_1 and loss_2 each
+    stepped by `opt`; bpr_reg_loss and gen_loss accumulate into one gradient, after which all three optimizers step, so the
+    generators' parameters are stepped twice.  The optimizer main() built only gives the learning rate."""
+    lr = optimizer.param_groups[0]['lr']
+    opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=0)
+    opt_gen_1 = torch.optim.Adam(model.generator_1.parameters(), lr=lr, weight_decay=0)
+    opt_gen_2 = torch.optim.Adam(filter(lambda p: p.requires_grad, model.generator_2.parameters()), lr=lr, weight_decay=0, eps=0.001)
+    sum_loss = None
+    for users, pos_items, neg_items in train_loader:
+        opt.zero_grad()
+        opt_gen_1.zero_grad()
+        opt_gen_2.zero_grad()
+        loss_1, out1, out2 = model.loss_1(users, pos_items, neg_items)
+        loss_1.backward()
+        opt.step()
+        opt.zero_grad()
+        loss_2 = model.loss_2(users, pos_items, neg_items, out1, out2)
+        loss_2.backward()
+        opt.step()
+        opt.zero_grad()
+        bpr_reg_loss = model.bpr_reg_loss(users, pos_items, neg_items)
+        bpr_reg_loss.backward()
+        gen_loss = model.gen_loss(users, pos_items, neg_items)
+        gen_loss.backward()
+        opt.step()
+        opt_gen_1.step()
+        opt_gen_2.step()
+        d = (loss_1 + loss_2 + bpr_reg_loss + gen_loss).detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    return float(sum_loss.item()) if sum_loss is not None else 0.0
+
+
 def _train_epoch_diffmm(model, train_loader, optimizer, diffusion_loader=None):
     """reference train_and_evaluate.py:140-244 in its three phases: (1) one pass of the diffusion loader, per batch a step of
     each denoiser under two Adam optimizers created anew every epoch (:142-145: their moments restart); (2) the two modal
@@ -125,6 +159,8 @@ def train(model, train_loader, optimizer, model_name="LightGCN", graphed=None):
         return _train_epoch_mmssl(model, train_loader, optimizer)
     if model_name == "DiffMM":
         return _train_epoch_diffmm(model, train_loader, optimizer)
+    if model_name == "AdaGCL":
+        return _train_epoch_adagcl(model, train_loader, optimizer)
     if graphed is not None and getattr(graphed, "draws_in_launch", False):
         return _train_epoch_in_launch(model, train_loader, optimizer, graphed)
     sum_loss = None

@@ -1244,6 +1244,49 @@ int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const float *W_out,
                                 float kf, float e_loss, int64_t B, int64_t I, int64_t H, float *d_out, int64_t ldd,
                                 float *part, double *diff_rows, float *gc_rows, float *loss, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * AdaGCL (Model/AdaGCL.py) -- csrc/adagcl.hip.  Additive to ABI 16: new names only.
+ * The E-sized work of the two view generators over ONE symmetric-pattern CSR of N = U + I nodes: rowptr int64 [N + 1],
+ * col int32 [E], entry_row int32 [E], tentry int32 [E] (the stored entry of the reversed pair).  D = 64 is what the keep
+ * kernel tiles (chaorec_adagcl_check_shape: CHAOREC_E_INVALID otherwise).  A row is owned by 8 lanes, a row longer than
+ * chaorec_adagcl_long_row() = 64 entries by its wave; chaorec_adagcl_rows_per_block() = 32 rows per workgroup, which is also
+ * the number of rows behind one float of `part` (n_part >= ceil(N / 32)).  No float atomics: every sum has one owner and a
+ * fixed order.  state int64 [2]: chaorec_adagcl_tick does state[0] += 1, state[1] = state[0]; device draws are keyed
+ * (seed, state[1], salt, entry).
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_adagcl_check_shape(int32_t D);
+int64_t chaorec_adagcl_rows_per_block(void);
+int64_t chaorec_adagcl_long_row(void);
+int chaorec_adagcl_tick(int64_t *state, void *stream);
+/* DenoisingNet's hard-concrete edge gate (Model/AdaGCL.py:572-624, :647-689) from two per-node scores:
+ *   logit[e] = s_nb[row e] + s_self[col e] + b_att[0]
+ *   gate = sigmoid(logit) (training = 0) | sigmoid((log u - log(1 - u) + logit) / beta) (training != 0; evaluated in double
+ *   and rounded once, as the reference's float64 draw makes it)
+ *   m[e] = clamp(1.5 gate - 0.45, 0, 1), S[n] = sum_row m + eps, d[n] = clamp(S^-1/2, 0, 10), val[e] = m[e] d[row e] d[col e]
+ *   l0[0] = mean_e sigmoid(logit[e] - beta log(0.45 / 1.05))
+ * u fp32 [E] in [1e-7, 1 - 1e-7] given, or NULL: drawn in the launch; u_out (may be NULL) receives the values used.
+ * Two launches; every output is written whole. */
+int chaorec_adagcl_gate_fwd_f32(const int64_t *rowptr, const int32_t *col, const int32_t *entry_row, int64_t N, int64_t E,
+                                const float *s_nb, const float *s_self, const float *b_att, float beta, float eps,
+                                int32_t training, const float *u, uint64_t seed, const int64_t *state, int32_t salt, float *m,
+                                float *S, float *d, float *val, float *l0, float *u_out, float *part, int64_t n_part,
+                                void *stream);
+/* Its backward: g_val fp32 [E] and g_l0 fp32 [1] (NULL = 0) -> g_s_nb [N], g_s_self [N], g_b [1]; g_logit [E] and g_S [N] are
+ * scratch the three launches hand to each other; m, S, d as the forward wrote them, u the values it used. */
+int chaorec_adagcl_gate_bwd_f32(const int64_t *rowptr, const int32_t *col, const int32_t *tentry, int64_t N, int64_t E,
+                                const float *s_nb, const float *s_self, const float *b_att, float beta, int32_t training,
+                                const float *u, const float *m, const float *S, const float *d, const float *g_val,
+                                const float *g_l0, float *g_logit, float *g_S, float *g_s_nb, float *g_s_self, float *g_b,
+                                float *part, int64_t n_part, void *stream);
+/* vgae.generate's keep decision (Model/AdaGCL.py:483-501) per stored entry, on v_mfma_f32_32x32x2_f32 (exact fp32 products):
+ *   logit[e] = w2 . relu(W1 relu(z[row e] * z[col e]) + b1) + b2[0], keep[e] = floor(sigmoid(logit) + 0.5) != 0
+ *   out[e] = keep ? vals[e] / fl32(kept / E) : +0, kept[0] = the number of kept entries (0: out is all zero)
+ * z fp32 [N, 64] (16-byte aligned), W1 [64, 64] row-major (out, in), b1 [64], w2 [64], b2 [1]; logit_out may be NULL.
+ * Two launches and one 8-byte memset, no host synchronisation. */
+int chaorec_adagcl_keep_f32(const float *z, int64_t N, const int32_t *entry_row, const int32_t *col, int64_t E, const float *W1,
+                            const float *b1, const float *w2, const float *b2, const float *vals, uint8_t *keep, float *out,
+                            int64_t *kept, float *logit_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
