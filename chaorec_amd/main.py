@@ -12,7 +12,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import dataload
-from .Model import (AdaGCL, BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
+from .Model import (AdaGCL, BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, GraphAug, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
                     SMORE, VBPR, VGCL, XSimGCL)
 from .arg_parser import load_yaml_config, parse_args
 from .train_and_evaluate import train_and_evaluate
@@ -157,6 +157,10 @@ def build_model(args, num_user, num_item, train_data, user_item_dict, v_feat, t_
         # the per-edge keep MLP on the f32 MFMA pipe, csrc/adagcl.hip; three optimizers per batch (train_and_evaluate.py:72-97)
         'AdaGCL': lambda: AdaGCL(num_user, num_item, train_data, user_item_dict, dim_E, args.reg_weight, args.n_layers,
                                  args.ssl_temp, args.ssl_alpha, device),
+        # (main.py:339-341) a learned view sampler over the fixed structure plus 100 000 random entries per step: the per-edge
+        # sampler and the contrastive terms' whole-table log-sum-exp on kernels of their own, csrc/graphaug.hip
+        'GraphAug': lambda: GraphAug(num_user, num_item, train_data, user_item_dict, dim_E, args.reg_weight, args.n_layers,
+                                     args.ssl_temp, args.ssl_alpha, device),
     }
     if args.Model == 'COHESION':   # Model/COHESION.py:96-99 reads the same file
         COHESION.user_graph_path = os.path.join(args.data_root, args.data_path, 'user_graph_dict.npy')

@@ -1751,3 +1751,142 @@ def adagcl_edge_keep(structure, z, W1, b1, w2, b2, vals, return_logits=False):
                                             _ptr(b2), _ptr(vals), _ptr(keep), _ptr(out), _ptr(kept), _ptr(logits), _stream())
     res = (out, keep.to(torch.bool), kept)
     return res + (logits,) if return_logits else res
+
+
+# --------------------------------------------------------------------------------------------
+# GraphAug (csrc/graphaug.hip): the view learner's edge sampler, the contrastive loss's whole-table log-sum-exp, the
+# propagate's random-entry term
+# --------------------------------------------------------------------------------------------
+GRAPHAUG_DIM = 64            # the row width the kernels tile
+
+
+def graphaug_check_shape(D):
+    if int(D) != GRAPHAUG_DIM:
+        raise ValueError(f"GraphAug: dim_E={D}; the kernels tile D={GRAPHAUG_DIM}")
+
+
+def graphaug_edge_sample(structure, P, Q, b1, w2, b2, u1=None, u2=None, state=None, seed=0, salt=0, want_val_t=True,
+                         return_logits=False, return_draws=False):
+    """The view learner's sampled value per stored entry of `structure` (a graph.DropoutStructure), csrc/graphaug.hip (a); no
+    gradient.  P = z W1[:, :64]^T and Q = z W1[:, 64:]^T fp32 [N, 64], b1 [64], w2 [64] or [1, 64], b2 [1]; u1, u2 fp32 [E]
+    given draws, or None: drawn in the launch keyed (seed, state[1], salt).  -> (val [E], val_t [E] or None, logits [E] or
+    None, u [2, E] -- the draws used -- or None)."""
+    _need_cuda(P, Q, b1, w2, b2, u1, u2, state, structure.rowptr)
+    N, E = structure.n_rows, structure.nnz
+    with torch.no_grad():
+        if P.dim() != 2:
+            raise ValueError(f"graphaug: P is {tuple(P.shape)}, expected [N, {GRAPHAUG_DIM}]")
+        graphaug_check_shape(P.shape[1])
+        P = _vae_f32("graphaug", P.detach().contiguous(), "P", (N, GRAPHAUG_DIM))
+        Q = _vae_f32("graphaug", Q.detach().contiguous(), "Q", (N, GRAPHAUG_DIM))
+        b1 = _vae_f32("graphaug", b1.detach().contiguous(), "b1", (GRAPHAUG_DIM,))
+        w2 = _vae_f32("graphaug", w2.detach().contiguous().reshape(-1), "w2", (GRAPHAUG_DIM,))
+        b2 = _vae_f32("graphaug", b2.detach().contiguous().reshape(-1), "b2", (1,))
+        if (u1 is None) != (u2 is None):
+            raise ValueError("graphaug: give both u1 and u2, or neither")
+        if u1 is not None:
+            u1, u2 = _vae_f32("graphaug", u1, "u1", (E,)), _vae_f32("graphaug", u2, "u2", (E,))
+        elif state is None:
+            raise ValueError("graphaug: the sampler needs given draws or a device step counter")
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=P.device)  # noqa: E731
+        val = f(E)
+        val_t = f(E) if want_val_t else None
+        logits = f(E) if return_logits else None
+        u_out = f(2, E) if return_draws else None
+        _lib.load().chaorec_graphaug_sample_f32(_ptr(structure.rowptr), _ptr(structure.col), _ptr(structure.transpose_entry), N, E,
+                                                _ptr(P), _ptr(Q), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(u1), _ptr(u2), int(seed),
+                                                _ptr(state), int(salt), _ptr(val), _ptr(val_t), _ptr(logits), _ptr(u_out), _stream())
+    return val, val_t, logits, u_out
+
+
+class _GraphAugLSE(torch.autograd.Function):
+    """lse[b] = log sum_m exp(<A_b, T_m> inv_temp) without a [B, M] buffer (csrc/graphaug.hip (b))."""
+
+    @staticmethod
+    def forward(ctx, A, T, inv_temp):
+        _need_cuda(A, T)
+        if A.dim() != 2 or T.dim() != 2 or A.shape[1] != T.shape[1]:
+            raise ValueError(f"graphaug_lse: A is {tuple(A.shape)}, T is {tuple(T.shape)}")
+        graphaug_check_shape(A.shape[1])
+        A = _vae_f32("graphaug_lse", A.detach().contiguous(), "A")
+        T = _vae_f32("graphaug_lse", T.detach().contiguous(), "T")
+        B, M = A.shape[0], T.shape[0]
+        lib = _lib.load()
+        splits = int(lib.chaorec_graphaug_lse_splits(B, M))
+        part = torch.empty(splits * B, dtype=torch.float32, device=A.device)
+        lse = torch.empty((2, B), dtype=torch.float32, device=A.device)      # [1]: what rounding [0] to fp32 lost
+        lib.chaorec_graphaug_lse_fwd_f32(_ptr(A), _ptr(T), B, M, float(inv_temp), _ptr(part), splits, _ptr(lse), _stream())
+        ctx.inv_temp, ctx.splits = float(inv_temp), splits
+        ctx.save_for_backward(A, T, lse)
+        return lse[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        A, T, lse = ctx.saved_tensors
+        B, M = A.shape[0], T.shape[0]
+        g = _f32c(g)
+        part = torch.empty(ctx.splits * B * GRAPHAUG_DIM, dtype=torch.float32, device=A.device)
+        dA, dT = torch.empty_like(A), torch.empty_like(T)
+        _lib.load().chaorec_graphaug_lse_bwd_f32(_ptr(A), _ptr(T), B, M, ctx.inv_temp, _ptr(lse), _ptr(g), _ptr(part), ctx.splits,
+                                                 _ptr(dA), _ptr(dT), _stream())
+        return dA, dT, None
+
+
+def graphaug_lse(A, T, inv_temp):
+    """-> lse [B] = log sum_m exp(<A_b, T_m> inv_temp), A [B, 64], T [M, 64]: a plain sum without a running max (rows are
+    expected normalised: |<a, t>| inv_temp stays far from fp32's exp range), no [B, M] buffer, one autograd node."""
+    return _GraphAugLSE.apply(A, T, inv_temp)
+
+
+class RandEntries:
+    """A step's random entries (rows[k], cols[k]), all of one value, as a CSR and its transpose (duplicates kept: they add)."""
+
+    def __init__(self, rows, cols, n):
+        rows, cols = rows.long(), cols.long()
+        self.n = int(n)
+        self.rowptr, self.col = self._csr(rows, cols, self.n)
+        self.rowptr_t, self.col_t = self._csr(cols, rows, self.n)
+
+    @staticmethod
+    def _csr(rows, cols, n):
+        """sorted by (row, col) on the device; no host synchronisation"""
+        key, _ = torch.sort(rows * n + cols)
+        r = torch.div(key, n, rounding_mode="floor")
+        rowptr = torch.searchsorted(r, torch.arange(n + 1, dtype=torch.int64, device=rows.device))
+        return rowptr.contiguous(), (key - r * n).to(torch.int32).contiguous()
+
+
+def _graphaug_rand_spmm(rowptr, col, n, x, z, alpha, slope):
+    y = torch.empty((n, GRAPHAUG_DIM), dtype=torch.float32, device=x.device)
+    _lib.load().chaorec_graphaug_rand_spmm_f32(_ptr(rowptr), _ptr(col), n, x.shape[0], _ptr(x), _ptr(z), float(alpha), float(slope),
+                                               _ptr(y), _stream())
+    return y
+
+
+class _GraphAugRandLayer(torch.autograd.Function):
+    """y = LeakyReLU_slope(z + alpha R x), R a RandEntries (csrc/graphaug.hip (c)); backward: g = gy (y > 0 ? 1 : slope),
+    gz = g, gx = alpha R^T g."""
+
+    @staticmethod
+    def forward(ctx, z, x, R, alpha, slope):
+        _need_cuda(z, x, R.rowptr)
+        graphaug_check_shape(x.shape[1])
+        z = _vae_f32("graphaug", z.detach().contiguous(), "z", (R.n, GRAPHAUG_DIM))
+        x = _vae_f32("graphaug", x.detach().contiguous(), "x", (R.n, GRAPHAUG_DIM))
+        y = _graphaug_rand_spmm(R.rowptr, R.col, R.n, x, z, alpha, slope)
+        ctx.R, ctx.alpha, ctx.slope = R, float(alpha), float(slope)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, = ctx.saved_tensors
+        g = torch.where(y > 0, gy, gy * ctx.slope).contiguous()
+        gx = _graphaug_rand_spmm(ctx.R.rowptr_t, ctx.R.col_t, ctx.R.n, g, None, ctx.alpha, 1.0) if ctx.needs_input_grad[1] else None
+        return g, gx, None, None, None
+
+
+def graphaug_rand_layer(z, x, R, alpha=0.05, slope=0.5):
+    """GCNLayer over a GraphAug view (Model/GraphAug.py:47-71): z = the learned entries' product with x, R the step's random
+    entries of value alpha -> LeakyReLU_slope(z + alpha R x)."""
+    return _GraphAugRandLayer.apply(z, x, R, alpha, slope)

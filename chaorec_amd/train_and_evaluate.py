@@ -21,7 +21,8 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 # SimGCL / XSimGCL / SLMRec draw only with rand_like on the device generator, which a captured step advances per replay:
 # they are captured (round 5: 2 x the eager epoch rate at baby size, tools/capture_family_probe.py).
 # DiffMM: three phases per epoch, the graphs its loss() multiplies with are rebuilt in the second.
-NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL")    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
+NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL",    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
+              "GraphAug")             # (its views' structure -- the random entries -- changes every step; the plain loss() loop below)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):

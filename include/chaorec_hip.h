@@ -1287,6 +1287,46 @@ int chaorec_adagcl_keep_f32(const float *z, int64_t N, const int32_t *entry_row,
                             const float *b1, const float *w2, const float *b2, const float *vals, uint8_t *keep, float *out,
                             int64_t *kept, float *logit_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * GraphAug (Model/GraphAug.py) -- csrc/graphaug.hip.  Additive to ABI 16: new names only.  D = 64 is what the kernels
+ * tile (chaorec_graphaug_check_shape: CHAOREC_E_INVALID otherwise).  No float atomics: every output has one owner and
+ * every sum a fixed order, so two runs on the same inputs give the same bits.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_graphaug_check_shape(int32_t D);
+int64_t chaorec_graphaug_rows_per_block(void);
+int64_t chaorec_graphaug_long_row(void);
+/* The view learner's edge sampler (Model/GraphAug.py:268-309) per stored entry e = (row, col) of a symmetric-pattern CSR
+ * (rowptr int64 [N + 1], col int32 [E], tentry int32 [E]: the stored entry of the reversed pair), forward only, fp32:
+ *   logit = b2[0] + sum_j w2[j] relu((P[row][j] + b1[j]) + Q[col][j])     P = z W1[:, :64]^T, Q = z W1[:, 64:]^T, fp32 [N, 64]
+ *   eps = -0.9998 u1 + 0.9999;  att = clamp(sigmoid(log eps - log(1 - eps) + logit), 0.01, 0.99)
+ *   u2' = clamp(u2, 2^-23, 1 - 2^-23);  s = clamp(sigmoid((log u2' - log1p(-u2') + log att - log1p(-att)) / 0.9), FLT_MIN, 1 - 2^-23)
+ *   val[e] = s > 0.2 ? s : +0
+ * A row is owned by 8 lanes (chaorec_graphaug_rows_per_block() = 32 rows per workgroup), a row longer than
+ * chaorec_graphaug_long_row() = 64 entries by its wave.  u1, u2 fp32 [E] given, or NULL: drawn in the launch, keyed
+ * (seed, state[1], salt, entry) -- state int64 [2] as chaorec_adagcl_tick keeps it; u_out fp32 [2, E] (may be NULL) receives
+ * the draws used.  val_t (may be NULL): val_t[tentry[e]] = val[e]; logit_out may be NULL.  One launch. */
+int chaorec_graphaug_sample_f32(const int64_t *rowptr, const int32_t *col, const int32_t *tentry, int64_t N, int64_t E,
+                                const float *P, const float *Q, const float *b1, const float *w2, const float *b2,
+                                const float *u1, const float *u2, uint64_t seed, const int64_t *state, int32_t salt, float *val,
+                                float *val_t, float *logit_out, float *u_out, void *stream);
+/* lse[b] = log sum_m exp(<A_b, T_m> inv_temp) for A fp32 [B, 64], T fp32 [M, 64] (16-byte aligned): a plain sum, no running
+ * max -- for normalised rows, as contrastLoss (Model/GraphAug.py:534-541) has them.  v_mfma_f32_32x32x2_f32; per-split
+ * partials part fp32 [splits, B], splits = chaorec_graphaug_lse_splits(B, M), added in split order (in double) by a second
+ * launch.  lse fp32 [2, B]: row 0 the result, row 1 what its rounding to fp32 lost (the backward subtracts both in turn). */
+int64_t chaorec_graphaug_lse_splits(int64_t B, int64_t M);
+int chaorec_graphaug_lse_fwd_f32(const float *A, const float *T, int64_t B, int64_t M, float inv_temp, float *part, int64_t splits,
+                                 float *lse, void *stream);
+/* Its backward for g fp32 [B] and lse [2, B] as the forward wrote it: w_bm = g_b inv_temp exp(<A_b, T_m> inv_temp - lse_b), dA_b = sum_m w_bm T_m (per-split partials
+ * part fp32 [splits, B, 64], added in split order), dT_m = sum_b w_bm A_b (one owner per 64 table rows, looping over B).
+ * Three launches; dA and dT are written whole. */
+int chaorec_graphaug_lse_bwd_f32(const float *A, const float *T, int64_t B, int64_t M, float inv_temp, const float *lse,
+                                 const float *g, float *part, int64_t splits, float *dA, float *dT, void *stream);
+/* y[n] = act(z[n] + alpha sum_{e in row n} x[col e]) over the CSR of a step's random entries (rowptr int64 [n_rows + 1], col
+ * int32), x fp32 [n_cols, 64], z (may be NULL) and y fp32 [n_rows, 64]; act = LeakyReLU(slope), slope = 1: none.  A wave per
+ * row, the entries in order. */
+int chaorec_graphaug_rand_spmm_f32(const int64_t *rowptr, const int32_t *col, int64_t n_rows, int64_t n_cols, const float *x,
+                                   const float *z, float alpha, float slope, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
