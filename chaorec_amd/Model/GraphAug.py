@@ -411,7 +411,7 @@ class GraphAug(nn.Module):
             draws = dict(u1=u1[0], u2=u2[0]) if (u1 is not None and u2 is not None) else {}
             if fused and not draws:
                 if not ticked:
-                    ops_extra.adagcl_tick(self._state)
+                    ops_extra.step_tick(self._state)
                     ticked = True
                 draws = dict(state=self._state, seed=self.seed, salt=j)
             ant_node, ant_adj = self.view_learner(ofea, st, st, fused, masks, **draws)

@@ -15,7 +15,7 @@
 //              numpy draw is float64 and promotes this one expression (Model/AdaGCL.py:583-596 ends in .float())
 //   m[e]     = clamp(gate * 1.5 - 0.45, 0, 1);  S[n] = sum_{e in row n} m[e] + eps;  d[n] = clamp(S^-1/2, 0, 10)  (S = 0: 10)
 //   val[e]   = (m[e] d[row e]) d[col e];  l0 = 1 / E sum_e sigmoid(logit[e] - beta log(0.45 / 1.05))
-//   u: given fp32 [E], or u NULL: lo + (hi - lo) vae_uniform<24>(vae_key(seed, state[1], salt), 0, e) clamped into
+//   u: given fp32 [E], or u NULL: lo + (hi - lo) draw_uniform<24>(draw_key(seed, state[1], salt), 0, e) clamped into
 //   [lo, hi] = [1e-7f, fl32(1 - 1e-7)]; written to u_out if not NULL (the backward reads it: no redraw).
 //   Launch 1 (ag_gate_rows_kernel) owns rows: m, S, d, u_out, one l0 partial per workgroup.  Launch 2 (ag_gate_vals_kernel)
 //   owns entries: val; its workgroup 0 adds the partials in double, thread t the entries t, t + 256, ..., then a tree.
@@ -39,7 +39,7 @@ namespace chaorec {
 
 constexpr int AG_D = 64;
 constexpr int AG_RW = 8;           // rows per wave
-constexpr int AG_RB = 32;          // rows per workgroup
+constexpr int AG_RB = kRowsPerBlock8;      // rows per workgroup
 constexpr int AG_LONG = 64;        // a longer row is taken by the whole wave
 constexpr float AG_GAMMA = -0.45f, AG_STRETCH = 1.5f;      // zeta - gamma = 1.05 + 0.45
 constexpr float AG_U_LO = 1e-7f, AG_U_HI = 0.99999988f;    // fl32(1 - 1e-7)
@@ -61,11 +61,8 @@ __device__ __forceinline__ ag2 ag_row_reduce(int64_t n, int64_t beg, int64_t end
       acc.a += t.a;
       acc.b += t.b;
     }
-#pragma unroll
-  for (int off = 4; off > 0; off >>= 1) {
-    acc.a += __shfl_xor(acc.a, off, 64);
-    acc.b += __shfl_xor(acc.b, off, 64);
-  }
+  acc.a = group_sum<8>(acc.a);
+  acc.b = group_sum<8>(acc.b);
   unsigned long long mask = __ballot(is_long && sub == 0);
   while (mask) {
     const int src = __ffsll((long long)mask) - 1;
@@ -98,18 +95,11 @@ __device__ __forceinline__ void ag_block_total(const float *__restrict__ part, i
   __shared__ double red[256];
   double v = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) v += (double)part[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum_f64(v, red);
   if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
 }
 
-__device__ __forceinline__ float ag_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float ag_l0_shift(float beta) { return beta * logf(0.45f / 1.05f); }
-__device__ __forceinline__ int ag_node(int c, int64_t N) { return c < 0 ? 0 : ((int64_t)c >= N ? (int)(N - 1) : c); }
 
 struct AgGate {
   float m;        // the mask
@@ -123,31 +113,10 @@ __device__ __forceinline__ AgGate ag_gate(float logit, float u, float beta, int 
     const bool in = s >= 0.0 && s <= 1.0;
     return {(float)(s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s)), in ? (float)(1.5 * g * (1.0 - g) / (double)beta) : 0.f};
   }
-  const float g = ag_sigmoid(logit);
+  const float g = sigmoidf_acc(logit);
   const float s = g * AG_STRETCH + AG_GAMMA;
   const bool in = s >= 0.f && s <= 1.f;
   return {fminf(fmaxf(s, 0.f), 1.f), in ? AG_STRETCH * (g * (1.f - g)) : 0.f};
-}
-
-__global__ void ag_tick_kernel(int64_t *state) {
-  if (threadIdx.x || blockIdx.x) return;
-  const int64_t c = state[0] + 1;
-  state[0] = c;
-  state[1] = c;
-}
-
-struct AgRow {
-  int64_t n, beg, end;
-  bool valid;
-};
-__device__ __forceinline__ AgRow ag_my_row(const int64_t *__restrict__ rowptr, int64_t N) {
-  const int64_t n0 = (int64_t)blockIdx.x * AG_RB + (threadIdx.x >> 3);
-  AgRow r;
-  r.valid = n0 < N;
-  r.n = r.valid ? n0 : 0;
-  r.beg = r.valid ? rowptr[r.n] : 0;
-  r.end = r.valid ? rowptr[r.n + 1] : 0;
-  return r;
 }
 
 __global__ __launch_bounds__(256) void ag_gate_rows_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t N,
@@ -157,19 +126,19 @@ __global__ __launch_bounds__(256) void ag_gate_rows_kernel(const int64_t *__rest
                                                            uint64_t salt, float *__restrict__ m, float *__restrict__ S, float *__restrict__ d,
                                                            float *__restrict__ u_out, float *__restrict__ l0_part) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const AgRow row = ag_my_row(rowptr, N);
+  const LaneRow row = lane_group_row(rowptr, N);
   const float b = b_att[0], shift = ag_l0_shift(beta);
-  const uint64_t key = (training && !u) ? vae_key(seed, (uint64_t)state[1], salt) : 0;
+  const uint64_t key = (training && !u) ? draw_key(seed, (uint64_t)state[1], salt) : 0;
   const ag2 acc = ag_row_reduce(row.n, row.beg, row.end, lane, [&](int64_t e, int64_t r) -> ag2 {
-    const float logit = (s_nb[r] + s_self[ag_node(col[e], N)]) + b;
+    const float logit = (s_nb[r] + s_self[clamp_index(col[e], N)]) + b;
     float ue = 0.5f;
     if (training) {
-      ue = u ? u[e] : fminf(fmaxf(AG_U_LO + (AG_U_HI - AG_U_LO) * vae_uniform<24>(key, 0, (uint64_t)e), AG_U_LO), AG_U_HI);
+      ue = u ? u[e] : fminf(fmaxf(AG_U_LO + (AG_U_HI - AG_U_LO) * draw_uniform<24>(key, 0, (uint64_t)e), AG_U_LO), AG_U_HI);
       if (u_out) u_out[e] = ue;
     }
     const float me = ag_gate(logit, ue, beta, training).m;
     m[e] = me;
-    return {me, ag_sigmoid(logit - shift)};
+    return {me, sigmoidf_acc(logit - shift)};
   });
   if (row.valid && (lane & 7) == 0) {
     const float s = acc.a + eps;
@@ -184,7 +153,7 @@ __global__ __launch_bounds__(256) void ag_gate_vals_kernel(const int32_t *__rest
                                                            float *__restrict__ val, const float *__restrict__ l0_part, int64_t n_part,
                                                            float *__restrict__ l0) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < E) val[e] = mul_rn(mul_rn(m[e], d[ag_node(entry_row[e], N)]), d[ag_node(col[e], N)]);
+  if (e < E) val[e] = mul_rn(mul_rn(m[e], d[clamp_index(entry_row[e], N)]), d[clamp_index(col[e], N)]);
   if (blockIdx.x == 0) ag_block_total(l0_part, n_part, 1.0 / (double)E, l0);
 }
 
@@ -193,11 +162,10 @@ __global__ __launch_bounds__(256) void ag_bwd_gd_kernel(const int64_t *__restric
                                                         const float *__restrict__ S, const float *__restrict__ d,
                                                         const float *__restrict__ g_val, float *__restrict__ g_S) {
   const int lane = threadIdx.x & 63;
-  const AgRow row = ag_my_row(rowptr, N);
+  const LaneRow row = lane_group_row(rowptr, N);
   const ag2 acc = ag_row_reduce(row.n, row.beg, row.end, lane, [&](int64_t e, int64_t) -> ag2 {
-    int64_t t = tentry[e];
-    t = t < 0 ? 0 : (t >= E ? E - 1 : t);
-    return {(g_val[e] * m[e] + g_val[t] * m[t]) * d[ag_node(col[e], N)], 0.f};
+    const int64_t t = clamp_index((int64_t)tentry[e], E);
+    return {(g_val[e] * m[e] + g_val[t] * m[t]) * d[clamp_index(col[e], N)], 0.f};
   });
   if (row.valid && (lane & 7) == 0) {
     const float s = S[row.n], r = 1.0f / sqrtf(s);
@@ -213,14 +181,14 @@ __global__ __launch_bounds__(256) void ag_bwd_logit_kernel(const int64_t *__rest
                                                            const float *__restrict__ g_l0, float *__restrict__ g_logit,
                                                            float *__restrict__ g_s_nb, float *__restrict__ gb_part) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const AgRow row = ag_my_row(rowptr, N);
+  const LaneRow row = lane_group_row(rowptr, N);
   const float b = b_att[0], shift = ag_l0_shift(beta);
   const float gl = g_l0 ? g_l0[0] / (float)E : 0.f;
   const ag2 acc = ag_row_reduce(row.n, row.beg, row.end, lane, [&](int64_t e, int64_t r) -> ag2 {
-    const int c = ag_node(col[e], N);
+    const int c = clamp_index(col[e], N);
     const float logit = (s_nb[r] + s_self[c]) + b;
     const float gm = (g_val[e] * d[r]) * d[c] + g_S[r];
-    const float s0 = ag_sigmoid(logit - shift);
+    const float s0 = sigmoidf_acc(logit - shift);
     const float gz = gm * ag_gate(logit, training ? u[e] : 0.5f, beta, training).slope + gl * (s0 * (1.f - s0));
     g_logit[e] = gz;
     return {gz, 0.f};
@@ -233,10 +201,9 @@ __global__ __launch_bounds__(256) void ag_bwd_self_kernel(const int64_t *__restr
                                                           int64_t E, const float *__restrict__ g_logit, float *__restrict__ g_s_self,
                                                           const float *__restrict__ gb_part, int64_t n_part, float *__restrict__ g_b) {
   const int lane = threadIdx.x & 63;
-  const AgRow row = ag_my_row(rowptr, N);
+  const LaneRow row = lane_group_row(rowptr, N);
   const ag2 acc = ag_row_reduce(row.n, row.beg, row.end, lane, [&](int64_t e, int64_t) -> ag2 {
-    int64_t t = tentry[e];
-    t = t < 0 ? 0 : (t >= E ? E - 1 : t);
+    const int64_t t = clamp_index((int64_t)tentry[e], E);
     return {g_logit[t], 0.f};
   });
   if (row.valid && (lane & 7) == 0) g_s_self[row.n] = acc.a;
@@ -270,8 +237,8 @@ __global__ __launch_bounds__(256) void ag_keep_kernel(const float *__restrict__ 
 #pragma unroll
     for (int et = 0; et < 2; ++et) {
       const int64_t e = e0 + 32 * et + r, ee = e < E ? e : E - 1;
-      const float4 *zr = reinterpret_cast<const float4 *>(z + (int64_t)ag_node(entry_row[ee], N) * AG_D);
-      const float4 *zc = reinterpret_cast<const float4 *>(z + (int64_t)ag_node(col[ee], N) * AG_D);
+      const float4 *zr = reinterpret_cast<const float4 *>(z + (int64_t)clamp_index(entry_row[ee], N) * AG_D);
+      const float4 *zc = reinterpret_cast<const float4 *>(z + (int64_t)clamp_index(col[ee], N) * AG_D);
       float bf[AG_D / 2];                // P[entry r][k = 2 s + h]
 #pragma unroll
       for (int q = 0; q < AG_D / 4; ++q) {
@@ -297,7 +264,7 @@ __global__ __launch_bounds__(256) void ag_keep_kernel(const float *__restrict__ 
     }
     const int64_t e = e0 + lane;
     const bool valid = e < E;
-    const bool kp = valid && floorf(ag_sigmoid(mine) + 0.5f) != 0.f;
+    const bool kp = valid && floorf(sigmoidf_acc(mine) + 0.5f) != 0.f;
     if (valid) {
       keep[e] = kp ? 1 : 0;
       out[e] = kp ? vals[e] : 0.f;
@@ -331,9 +298,7 @@ extern "C" int64_t chaorec_adagcl_rows_per_block(void) { return AG_RB; }
 extern "C" int64_t chaorec_adagcl_long_row(void) { return AG_LONG; }
 
 extern "C" int chaorec_adagcl_tick(int64_t *state, void *stream) {
-  if (!state) return fail(CHAOREC_E_INVALID, "adagcl_tick: NULL argument");
-  hipLaunchKernelGGL(ag_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
-  return check_launch("adagcl_tick");
+  return launch_step_tick("adagcl_tick", state, stream);
 }
 
 static int ag_check_graph(const char *what, int64_t N, int64_t E) {

@@ -10,12 +10,11 @@
 // launch/latency-bound (0.79 MB gathered at B=1024), so the forward is two launches with a
 // fixed reduction order (bit-reproducible loss) and the backward is one launch of 256-B
 // atomic row adds (the full-rate atomic shape on gfx950).
-#include "common.h"
+#include "draws.h"
 #include <cstdlib>
 
 namespace chaorec {
 
-__device__ __forceinline__ float sigmoidf_acc(float d) { return 1.0f / (1.0f + expf(-d)); }
 
 // the wave of triple b: three row gathers, five wave butterflies, lane 0 writes the term / coefficient / L2 parts
 __device__ __forceinline__ float bpr_terms_wave(const float *__restrict__ tab_u, const float *__restrict__ tab_i,
@@ -572,10 +571,10 @@ static bool launch_bpr_ordered(OrdArgs &P, int groups, hipStream_t st) {
 // ---- sampler -------------------------------------------------------------------------------
 // Counter-based generator: splitmix64 finaliser over (seed, step, b, attempt).  Stateless, so a
 // draw does not depend on launch geometry or on how many draws other samples needed.
-// (mix64: common.h)
+// (mix64: common.h; the keying: draws.h)
 __device__ __forceinline__ uint32_t sampler_draw(uint64_t seed, uint64_t step, uint32_t b,
                                                  uint32_t attempt, uint32_t num_item) {
-  uint64_t h = mix64(seed ^ mix64(step ^ mix64(((uint64_t)b << 32) | attempt)));
+  uint64_t h = draw_hash(seed, step, ((uint64_t)b << 32) | attempt);
   // Lemire multiply-shift onto [0, num_item): bias <= num_item / 2^32, far below test resolution
   return (uint32_t)(((h >> 32) * (uint64_t)num_item) >> 32);
 }
@@ -620,7 +619,7 @@ __device__ __forceinline__ void draw_triple(const int64_t *__restrict__ edges, i
     const int64_t q = perm_pos + (int64_t)b;
     idx = (uint64_t)perm[q < n_edges ? (q < 0 ? 0 : q) : n_edges - 1];
   } else {
-    const uint64_t hsel = mix64(seed ^ mix64(step ^ mix64(0xED6E5ull ^ ((uint64_t)b << 32))));
+    const uint64_t hsel = draw_hash(seed, step, 0xED6E5ull ^ ((uint64_t)b << 32));
     // 64x64 -> high 64 multiply-shift onto [0, n_edges)
     idx = (uint64_t)(((unsigned __int128)hsel * (unsigned __int128)(uint64_t)n_edges) >> 64);
   }

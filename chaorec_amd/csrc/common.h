@@ -77,11 +77,49 @@ __device__ __forceinline__ void adam_bias_corrections(int step, float b1, float 
   bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-  // fixed butterfly order -> identical result on every lane and every run
+// sum over each aligned group of LANES lanes (a power of two <= 64): the DESCENDING xor butterfly, off = LANES / 2 .. 1 --
+// a fixed order -> identical result on every lane of the group and every run.  (An ascending butterfly adds the same
+// terms in another order and gives other bits: dgcf.hip's slice_sum is one, and stays one.)
+template <int LANES, class T>
+__device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  for (int off = LANES / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
+
+// sum of v over the 256 threads of a workgroup in double, one fixed tree (128 .. 1): every thread calls; the result is in
+// red[0] (256 doubles of LDS) once the call returns.  The order of every fp64 total the loss parts are compared by.
+__device__ __forceinline__ void block_sum_f64(double v, double *red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ float sigmoidf_acc(float d) { return 1.0f / (1.0f + expf(-d)); }
+
+// an index clamped into [0, n): for memory safety only, the callers' ids are in range
+__device__ __forceinline__ int clamp_index(int i, int64_t n) { return i < 0 ? 0 : ((int64_t)i >= n ? (int)(n - 1) : i); }
+__device__ __forceinline__ int64_t clamp_index(int64_t i, int64_t n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// Row ownership of the per-entry graph kernels (adagcl.hip, graphaug.hip): a workgroup of 256 threads holds kRowsPerBlock8
+// = 32 rows, 8 lanes each.  The lane group's row n with its entries [beg, end); past the last row: row 0, no entries.
+constexpr int kRowsPerBlock8 = 32;
+struct LaneRow {
+  int64_t n, beg, end;
+  bool valid;
+};
+__device__ __forceinline__ LaneRow lane_group_row(const int64_t *__restrict__ rowptr, int64_t N) {
+  const int64_t n0 = (int64_t)blockIdx.x * kRowsPerBlock8 + (threadIdx.x >> 3);
+  LaneRow r;
+  r.valid = n0 < N;
+  r.n = r.valid ? n0 : 0;
+  r.beg = r.valid ? rowptr[r.n] : 0;
+  r.end = r.valid ? rowptr[r.n + 1] : 0;
+  return r;
 }
 
 __device__ __forceinline__ int wave_max_i32(int v) {

@@ -16,7 +16,8 @@ using namespace chaorec;
 
 namespace {
 
-// sum over the LPS lanes of one slice (aligned groups of LPS lanes: xor offsets below LPS never leave the group)
+// sum over the LPS lanes of one slice (aligned groups of LPS lanes: xor offsets below LPS never leave the group).
+// NOT common.h's group_sum: this butterfly ASCENDS (off = 1 first), another summation order and therefore other bits.
 template <int LPS>
 __device__ __forceinline__ float slice_sum(float v) {
 #pragma unroll
@@ -215,12 +216,7 @@ __global__ __launch_bounds__(256) void dcor_pass1_kernel(const float *__restrict
   // workgroup partials: a fixed tree over the 256 threads
   for (int q = 0; q < 2 * K; ++q) {
     __syncthreads();
-    red[threadIdx.x] = q < K ? ps[q] : qs[q - K];
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
+    block_sum_f64(q < K ? ps[q] : qs[q - K], red);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.x * 2 * K + q] = red[0];
   }
 }
@@ -235,13 +231,8 @@ __global__ __launch_bounds__(256) void dcor_combine_kernel(const double *__restr
   __shared__ double sums[3 * 8 + 2 * 8];          // sumR[k], RR[k] (k,k+1), R2[k], pair sums, square sums
   const double nd = (double)n;
   auto reduce = [&](double v) -> double {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
+    __syncthreads();      // (the previous total is still being read)
+    block_sum_f64(v, red);
     return red[0];
   };
   for (int k = 0; k < K; ++k) {

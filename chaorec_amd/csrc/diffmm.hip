@@ -35,7 +35,7 @@ static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
   const int64_t u = live ? users[b] : -1;
   const VaeHistRow hr = vae_hist_row(rowptr, u, U);
   const float a = (live && !plain) ? a_row[b] : 1.f, s = (live && !plain) ? s_row[b] : 0.f;
-  const uint64_t key_n = vae_key(seed, step, 2 * salt), key_k = vae_key(seed, step, 2 * salt + 1);
+  const uint64_t key_n = draw_key(seed, step, 2 * salt), key_k = draw_key(seed, step, 2 * salt + 1);
   for (int64_t c0 = 0; c0 < ld; c0 += DM_CH) {      // the same trip count for every wave of the workgroup
     words[wave][lane] = 0u;
     __syncthreads();
@@ -62,8 +62,8 @@ static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
             const float x0 = ((word >> ((4 * v + q) & 31)) & 1u) ? 1.f : 0.f;
             if (plain) x = x0;
             else {
-              const float n = noise ? noise[b * I + i] : vae_normal<DM_BITS>(key_n, (uint64_t)u, (uint64_t)i);
-              const bool kept = keep ? keep[b * I + i] != 0 : vae_uniform<DM_BITS>(key_k, (uint64_t)u, (uint64_t)i) < 0.5f;
+              const float n = noise ? noise[b * I + i] : draw_normal<DM_BITS>(key_n, (uint64_t)u, (uint64_t)i);
+              const bool kept = keep ? keep[b * I + i] != 0 : draw_uniform<DM_BITS>(key_k, (uint64_t)u, (uint64_t)i) < 0.5f;
               const float xt = add_rn(mul_rn(a, x0), mul_rn(s, n));
               x = kept ? mul_rn(2.f, xt) : 0.f;
             }

@@ -1,0 +1,54 @@
+// The device-drawn layer: the counter RNG over common.h's mix64 and the step counter its draws are keyed by.  One
+// definition of the bits of a draw; every file that draws on the device includes this (the autoencoders through
+// vae_common.h).  A draw depends on its counters only, never on launch geometry: a replayed graph whose step counter moved
+// draws fresh values and a backward redraws its forward's.
+// The kernels here are static templates: a file that launches one has its own copy (the link sees no duplicate), a file
+// that does not has none -- `template <class = void>` is there for that alone.
+#pragma once
+#include "common.h"
+
+namespace chaorec {
+
+// (seed, step, salt) -> key; (key, a, b) -> uniform STRICTLY inside (0, 1), BITS random bits + 0.5 (exact in fp32 for
+// BITS <= 24; log(-log(u)) is finite)
+__device__ __forceinline__ uint64_t draw_key(uint64_t seed, uint64_t step, uint64_t salt) { return mix64(mix64(seed ^ salt) + step); }
+template <int BITS>
+__device__ __forceinline__ float draw_uniform(uint64_t key, uint64_t a, uint64_t b) {
+  const uint64_t r = mix64(key ^ mix64((a << 32) ^ b));
+  return ((float)(r >> (64 - BITS)) + 0.5f) * (1.0f / (float)(1 << BITS));
+}
+template <int BITS>
+__device__ __forceinline__ float draw_normal(uint64_t key, uint64_t a, uint64_t c) {   // Box-Muller
+  const float u1 = draw_uniform<BITS>(key, a, 2 * c), u2 = draw_uniform<BITS>(key, a, 2 * c + 1);
+  return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
+// the older keying (the negative sampler, the edge dropouts, the user graph's neighbour pick): 64 bits of (seed, step, x);
+// each caller packs its own x (salts and shifts stay with it) and cuts its own bits from the result
+__device__ __forceinline__ uint64_t draw_hash(uint64_t seed, uint64_t step, uint64_t x) { return mix64(seed ^ mix64(step ^ mix64(x))); }
+
+// out[e] = std * N(0, 1) keyed (seed, state[1], SALT, e) (the autoencoders' epsilon: it keeps their prefix, and its name)
+template <int BITS, uint64_t SALT>
+static __global__ __launch_bounds__(256) void vae_normal_kernel(float *__restrict__ out, int64_t n, uint64_t seed,
+                                                                const int64_t *__restrict__ state, float std) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  out[e] = std * draw_normal<BITS>(draw_key(seed, (uint64_t)state[1], SALT), (uint64_t)e, 0);
+}
+
+// the step tick: state[0] += 1, state[1] = state[0] -- state[1] is the step the launches after it key their draws by
+template <class = void>
+static __global__ void step_tick_kernel(int64_t *state) {
+  if (threadIdx.x || blockIdx.x) return;
+  const int64_t c = state[0] + 1;
+  state[0] = c;
+  state[1] = c;
+}
+template <class = void>
+static int launch_step_tick(const char *what, int64_t *state, void *stream) {
+  if (!state) return fail(CHAOREC_E_INVALID, "%s: NULL argument", what);
+  hipLaunchKernelGGL(step_tick_kernel<>, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
+  return check_launch(what);
+}
+
+}  // namespace chaorec

@@ -25,16 +25,6 @@ constexpr int DV_HS = 10;         // MFMA k-steps over H
 constexpr int DV_AK = DV_A * DV_K, DV_AH = DV_A * DV_H;
 constexpr float DV_EPS = 1e-10f;  // (:15)
 
-__device__ __forceinline__ float dv_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// the step counter the device-drawn epsilon is keyed by: state[0] += 1, state[1] = state[0]
-__global__ void dv_tick_kernel(int64_t *state) {
-  if (threadIdx.x || blockIdx.x) return;
-  const int64_t c = state[0] + 1;
-  state[0] = c;
-  state[1] = c;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // encoder first layer: pre[b, a, :] = bias + sum_{n in row(b)} w[n, a] We_t[n, :].  One workgroup per sample, thread =
 // (aspect, column): the 80-byte row We_t[n, :] is gathered once per entry for all A aspects.
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int n = 32 * jt + vae_row(q, h);
-          const float v = ws[n] * dv_sigmoid(ad[q] + tanhf(am[q]));
+          const float v = ws[n] * sigmoidf_acc(ad[q] + tanhf(am[q]));
           ssum += v;
           o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Ts[rk][n], v, o1, 0, 0, 0);
         }
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256) void dv_rows_kernel(const float *__restrict__ 
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int n = 32 * jt + vae_row(q, h);
-          const float tm = tanhf(am[q]), sg = dv_sigmoid(ad[q] + tm);
+          const float tm = tanhf(am[q]), sg = sigmoidf_acc(ad[q] + tm);
           const float dl = ws[n] * (my_g1 + an[q]) * (sg * (1.0f - sg));
           const float dm = dl * (1.0f - tm * tm);
           o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Ts[rk][n], dl, o1, 0, 0, 0);
@@ -212,7 +202,7 @@ __device__ __forceinline__ float dv_pair(const float (&zk)[DV_A], const float (&
   for (int a = 0; a < DV_A; ++a) {
     wa[a] = wrow[a];
     tm[a] = tanhf(wave_sum(hk[a] * thk[a]));
-    s[a] = dv_sigmoid(wave_sum(zk[a] * tk[a]) + tm[a]);
+    s[a] = sigmoidf_acc(wave_sum(zk[a] * tk[a]) + tm[a]);
     p += wa[a] * s[a];
   }
   return p;
@@ -382,7 +372,7 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
           am = __builtin_amdgcn_mfma_f32_32x32x2f32(ZHs[wave * 32 + r][2 * s + h], Hs[2 * s + h][32 * jt + r], am, 0, 0, 0);
         if (SCORES) {
 #pragma unroll
-          for (int q = 0; q < 16; ++q) acc2[jt][q] += wl * dv_sigmoid(ad[q] + tanhf(am[q]));
+          for (int q = 0; q < 16; ++q) acc2[jt][q] += wl * sigmoidf_acc(ad[q] + tanhf(am[q]));
         } else {
           f32x16 an = vae_zero();
 #pragma unroll
@@ -392,7 +382,7 @@ __global__ __launch_bounds__(256) void dv_table_kernel(const float *__restrict__
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             const int sm = wave * 32 + vae_row(q, h);
-            const float tm = tanhf(am[q]), sg = dv_sigmoid(ad[q] + tm);
+            const float tm = tanhf(am[q]), sg = sigmoidf_acc(ad[q] + tm);
             const float qq = g1s[sm] + an[q];
             bk += sg * qq;
             const float dm = wl * qq * (sg * (1.0f - sg)) * (1.0f - tm * tm);
@@ -543,12 +533,7 @@ __global__ __launch_bounds__(256) void dv_kl_partial_kernel(const float *__restr
     const double ls = x >= 0.0 ? -log1p(exp(-x)) : x - log1p(exp(x));      // log sigmoid(x)
     a += -0.5 * (1.0 + 2.0 * ls - m * m - exp(2.0 * ls));
   }
-  red[t] = a;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
+  block_sum_f64(a, red);
   if (t == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -561,12 +546,7 @@ __global__ __launch_bounds__(256) void dv_loss_kernel(const double *__restrict__
   const int t = threadIdx.x;
   double b = 0.0;
   for (int64_t e = t; e < B; e += 256) b += (double)xlog[e] - (double)sum_p[e];
-  red[t] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
+  block_sum_f64(b, red);
   if (t == 0) {
     double a = 0.0;
     for (int p = 0; p < n_partial; ++p) a += partial[p];
@@ -598,9 +578,7 @@ extern "C" int64_t chaorec_dualvae_splits(int64_t B, int64_t N) {
 extern "C" int chaorec_dualvae_check_shape(int32_t k, int32_t a, int32_t hidden) { return dv_shape("dualvae_check_shape", k, a, hidden); }
 
 extern "C" int chaorec_dualvae_tick(int64_t *state, void *stream) {
-  if (!state) return fail(CHAOREC_E_INVALID, "dualvae_tick: NULL argument");
-  hipLaunchKernelGGL(dv_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
-  return check_launch("dv_tick_kernel");
+  return launch_step_tick("dualvae_tick", state, stream);      // the step the device-drawn epsilon is keyed by
 }
 
 extern "C" int chaorec_dualvae_encode_fwd_f32(const int64_t *ids, int64_t B, int64_t S, const int64_t *rowptr, const int32_t *col,

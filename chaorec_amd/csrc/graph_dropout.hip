@@ -12,13 +12,13 @@
 //     an exact 64-bit radix select with integer histograms -> deterministic for a given (seed, step), any edge count.
 //
 // Both are HBM-streaming integer/byte work: one coalesced pass per launch, no LDS tiles beyond the histograms.
-#include "common.h"
+#include "draws.h"
 
 namespace chaorec {
 
 // uniform in [0,1) with 24 random bits (what torch.rand yields for fp32), from the stateless counter generator
 __device__ __forceinline__ float edge_uniform(uint64_t seed, uint64_t step, uint64_t salt, uint64_t k) {
-  const uint64_t h = mix64(seed ^ mix64(step ^ mix64((salt << 48) ^ k)));
+  const uint64_t h = draw_hash(seed, step, (salt << 48) ^ k);
   return (float)(uint32_t)(h >> 40) * 5.9604644775390625e-08f;  // 2^-24, exact
 }
 
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void edge_dropout_norm_kernel(
 // 64-bit key of entry e: high 32 bits = fp32 bits of -log(u)/w (positive -> unsigned order == float order), low 32
 // bits = fresh hash bits that order entries whose fp32 keys coincide.  w <= 0 -> never selected.
 __device__ __forceinline__ uint64_t race_key_of(float we, int64_t e, uint64_t seed, uint64_t step) {
-  const uint64_t h = mix64(seed ^ mix64(step ^ mix64(0x5A3Bull << 48 ^ (uint64_t)e)));
+  const uint64_t h = draw_hash(seed, step, 0x5A3Bull << 48 ^ (uint64_t)e);
   if (!(we > 0.f)) return ~0ull;
   const float u = ((float)(uint32_t)(h >> 40) + 0.5f) * 5.9604644775390625e-08f;   // (0,1): log finite
   const float key = fabsf(logf(u)) / we;          // >= +0: unsigned order of the bits == float order

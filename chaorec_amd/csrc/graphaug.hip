@@ -13,7 +13,7 @@
 //   Row-owned like ag_*: a wave holds GA_RW = 8 rows, 8 lanes each; a lane keeps its row's P + b1 in 64 registers and takes the
 //   row's entries j, j + 8, ...; a row longer than GA_LONG = 64 entries is taken by its whole wave afterwards (lane j: entries
 //   j, j + 64, ...).  Every entry has one owner and no sum crosses lanes: the same bits every run, no atomics.
-//   u1, u2 given fp32 [E], or NULL: vae_uniform<24>(vae_key(seed, state[1], salt 2 view + {0, 1}), 0, e), written to
+//   u1, u2 given fp32 [E], or NULL: draw_uniform<24>(draw_key(seed, state[1], salt 2 view + {0, 1}), 0, e), written to
 //   u_out [2, E] if not NULL.  val_t (may be NULL): val_t[tentry[e]] = val[e] -- tentry is a permutation, one store per element.
 // (b) log-sum-exp of a batch against a whole table (contrastLoss's denominator, :534-541), no running max (the reference has
 //   none; rows arrive normalised, so |<a, t>| inv_temp <= inv_temp):
@@ -32,14 +32,11 @@ namespace chaorec {
 
 constexpr int GA_D = 64;
 constexpr int GA_RW = 8;           // rows per wave
-constexpr int GA_RB = 32;          // rows per workgroup
+constexpr int GA_RB = kRowsPerBlock8;      // rows per workgroup
 constexpr int GA_LONG = 64;        // a longer row is taken by the whole wave
 constexpr uint64_t GA_SALT = 0x6772617068617567ull;
 constexpr float GA_P_LO = 1.1920928955078125e-07f, GA_P_HI = 0.99999988079071044921875f;      // 2^-23, 1 - 2^-23
 static_assert(GA_D == VAE_D, "the staging helpers move rows of the latent width");
-
-__device__ __forceinline__ float ga_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ int ga_node(int c, int64_t N) { return c < 0 ? 0 : ((int64_t)c >= N ? (int)(N - 1) : c); }
 
 struct GaSample {
   const int32_t *col, *tentry;
@@ -52,7 +49,7 @@ struct GaSample {
 
 // pb[j] = P[row][j] + b1[j]: the entry's value, stored by its one owner
 __device__ __forceinline__ void ga_entry(const GaSample &a, const float (&pb)[GA_D], int64_t e) {
-  const float4 *q = reinterpret_cast<const float4 *>(a.Q + (int64_t)ga_node(a.col[e], a.N) * GA_D);
+  const float4 *q = reinterpret_cast<const float4 *>(a.Q + (int64_t)clamp_index(a.col[e], a.N) * GA_D);
   float logit = a.b2;
 #pragma unroll
   for (int k = 0; k < GA_D / 4; ++k) {
@@ -62,25 +59,23 @@ __device__ __forceinline__ void ga_entry(const GaSample &a, const float (&pb)[GA
     logit = fmaf(a.w2[4 * k + 2], fmaxf(add_rn(pb[4 * k + 2], x.z), 0.f), logit);
     logit = fmaf(a.w2[4 * k + 3], fmaxf(add_rn(pb[4 * k + 3], x.w), 0.f), logit);
   }
-  const float v1 = a.u1 ? a.u1[e] : vae_uniform<24>(a.key1, 0, (uint64_t)e);
-  const float v2 = a.u2 ? a.u2[e] : vae_uniform<24>(a.key2, 0, (uint64_t)e);
+  const float v1 = a.u1 ? a.u1[e] : draw_uniform<24>(a.key1, 0, (uint64_t)e);
+  const float v2 = a.u2 ? a.u2[e] : draw_uniform<24>(a.key2, 0, (uint64_t)e);
   if (a.u_out) {
     a.u_out[e] = v1;
     a.u_out[a.E + e] = v2;
   }
   const float eps = add_rn(mul_rn(-0.9998f, v1), 0.9999f);
   const float gate = add_rn(add_rn(logf(eps), -logf(add_rn(1.0f, -eps))), logit);
-  const float att = fminf(fmaxf(ga_sigmoid(gate), 0.01f), 0.99f);
+  const float att = fminf(fmaxf(sigmoidf_acc(gate), 0.01f), 0.99f);
   const float uc = fminf(fmaxf(v2, GA_P_LO), GA_P_HI);
   const float x = add_rn(add_rn(add_rn(logf(uc), -log1pf(-uc)), logf(att)), -log1pf(-att)) / 0.9f;
-  const float s = fminf(fmaxf(ga_sigmoid(x), FLT_MIN), GA_P_HI);
+  const float s = fminf(fmaxf(sigmoidf_acc(x), FLT_MIN), GA_P_HI);
   const float v = s > 0.2f ? s : 0.f;
   a.val[e] = v;
   if (a.logit_out) a.logit_out[e] = logit;
   if (a.val_t) {
-    int64_t t = a.tentry[e];
-    t = t < 0 ? 0 : (t >= a.E ? a.E - 1 : t);
-    a.val_t[t] = v;
+    a.val_t[clamp_index((int64_t)a.tentry[e], a.E)] = v;
   }
 }
 
@@ -99,13 +94,11 @@ __device__ __forceinline__ void ga_load_row(float (&pb)[GA_D], const float *__re
 __global__ __launch_bounds__(256) void ga_sample_kernel(const int64_t *__restrict__ rowptr, const float *__restrict__ P, GaSample a,
                                                         uint64_t seed, const int64_t *__restrict__ state, uint64_t salt) {
   const int lane = threadIdx.x & 63, sub = lane & 7;
-  const int64_t n0 = (int64_t)blockIdx.x * GA_RB + (threadIdx.x >> 3);
-  const bool valid = n0 < a.N;
-  const int64_t n = valid ? n0 : 0;
-  const int64_t beg = valid ? rowptr[n] : 0, end = valid ? min(rowptr[n + 1], a.E) : 0;      // (a rowptr past E walks nothing past it)
+  const LaneRow row = lane_group_row(rowptr, a.N);
+  const int64_t n = row.n, beg = row.beg, end = min(row.end, a.E);      // (a rowptr past E walks nothing past it)
   a.b2 = a.b2p[0];
-  if (!a.u1) a.key1 = vae_key(seed, (uint64_t)state[1], GA_SALT + 2 * salt);
-  if (!a.u2) a.key2 = vae_key(seed, (uint64_t)state[1], GA_SALT + 2 * salt + 1);
+  if (!a.u1) a.key1 = draw_key(seed, (uint64_t)state[1], GA_SALT + 2 * salt);
+  if (!a.u2) a.key2 = draw_key(seed, (uint64_t)state[1], GA_SALT + 2 * salt + 1);
   const bool is_long = end - beg > GA_LONG;
   float pb[GA_D];
   if (!is_long && end > beg) {
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(256) void ga_rand_spmm_kernel(const int64_t *__rest
   if (n >= N) return;
   const int64_t beg = rowptr[n], end = rowptr[n + 1];
   float acc = 0.f;
-  for (int64_t e = beg; e < end; ++e) acc += x[(int64_t)ga_node(col[e], n_cols) * GA_D + lane];
+  for (int64_t e = beg; e < end; ++e) acc += x[(int64_t)clamp_index(col[e], n_cols) * GA_D + lane];
   float v = alpha * acc;
   if (z) v = z[n * GA_D + lane] + v;
   y[n * GA_D + lane] = v > 0.f ? v : slope * v;

@@ -67,13 +67,13 @@ __global__ __launch_bounds__(256) void mc_concept_fwd_kernel(const float *__rest
   const float x = E[i * MC_D + lane];
   const float it = x / fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);
   items[i * MC_D + lane] = it;
-  const uint64_t key = training && !gumbel_in ? vae_key(seed, (uint64_t)state[1], MC_SALT_GUMBEL) : 0;
+  const uint64_t key = training && !gumbel_in ? draw_key(seed, (uint64_t)state[1], MC_SALT_GUMBEL) : 0;
   float l[MC_K], m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < MC_K; ++k) {
     l[k] = wave_sum(it * cs[k][lane]) * inv_tau;
     if (training)      // g = -log(Exp(1)) (F.gumbel_softmax, tau = 1): Exp(1) = -log(u)
-      l[k] += gumbel_in ? gumbel_in[i * MC_K + k] : -logf(-logf(vae_uniform<MC_BITS>(key, (uint64_t)i, (uint64_t)k)));
+      l[k] += gumbel_in ? gumbel_in[i * MC_K + k] : -logf(-logf(draw_uniform<MC_BITS>(key, (uint64_t)i, (uint64_t)k)));
     m = fmaxf(m, l[k]);
   }
   float sum = 0.f;
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(192) void mc_encode_fwd_kernel(
   const int c4 = 4 * (active ? t : 0);
   const int64_t b = blockIdx.x;
   const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
-  if (kf.training && !kf.keep) kf.key = vae_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
+  if (kf.training && !kf.keep) kf.key = draw_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
   float4 acc[MC_K];
 #pragma unroll
   for (int k = 0; k < MC_K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(192) void mc_encode_dw_kernel(
   const bool active = t < MC_H4;
   const int c4 = 4 * (active ? t : 0);
   const int64_t i = blockIdx.x;
-  if (kf.training && !kf.keep) kf.key = vae_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
+  if (kf.training && !kf.keep) kf.key = draw_key(seed, (uint64_t)state[1], MC_SALT_KEEP);
   float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
   if (active) w = *reinterpret_cast<const float4 *>(W1_t + i * MC_H + c4);
   float c[MC_K], dc[MC_K];

@@ -43,12 +43,7 @@ __global__ __launch_bounds__(256) void mv_sumsq_kernel(const float *__restrict__
   const int64_t beg = (int64_t)blockIdx.x * chunk, end = min(n, beg + chunk);
   double v = 0.0;
   for (int64_t i = beg + threadIdx.x; i < end; i += 256) v += (double)x[i] * (double)x[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum_f64(v, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = (float)red[0];
 }
 
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(256) void mv_encode_fwd_kernel(
   if (b >= B) return;
   const auto [beg, n] = vae_hist_row(rowptr, users[b], U);
   const uint64_t step = (uint64_t)state[1];
-  kf.key = vae_key(seed, step, MV_SALT_KEEP);
+  kf.key = draw_key(seed, step, MV_SALT_KEEP);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t j = half; j < n; j += 8) {      // four gathers in flight per half-wave
     float4 w[4];
@@ -89,14 +84,14 @@ __global__ __launch_bounds__(256) void mv_encode_fwd_kernel(
   float hv[4] = {bias.x + sc * acc.x, bias.y + sc * acc.y, bias.z + sc * acc.z, bias.w + sc * acc.w};
   if (half == 0) *reinterpret_cast<float4 *>(h_out + b * MV_H + c4) = make_float4(hv[0], hv[1], hv[2], hv[3]);
   // epilogue (Model/MultVAE.py:87-91, :113-114): lanes 0-15 hold mu, lanes 16-31 the logvar of the same columns
-  const uint64_t ekey = vae_key(seed, step, MV_SALT_EPS);
+  const uint64_t ekey = draw_key(seed, step, MV_SALT_EPS);
   double kl = 0.0;
   float zv[4], ev[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float lv = __shfl(hv[q], (lane & 15) + 16, 64), mu = hv[q];
     const int c = c4 + q;                              // (a column of z for lanes 0-15)
-    const float e = (lane < 16) ? (eps_in ? eps_in[b * MV_D + c] : vae_normal<MV_BITS>(ekey, (uint64_t)b, (uint64_t)c)) : 0.f;
+    const float e = (lane < 16) ? (eps_in ? eps_in[b * MV_D + c] : draw_normal<MV_BITS>(ekey, (uint64_t)b, (uint64_t)c)) : 0.f;
     ev[q] = e;
     zv[q] = mu + e * expf(0.5f * lv);
     kl += (double)(0.5f * (-lv + expf(lv) + mu * mu - 1.0f));
@@ -153,7 +148,7 @@ __global__ __launch_bounds__(256) void mv_encode_dw_kernel(
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= I) return;
-  kf.key = vae_key(seed, (uint64_t)state[1], MV_SALT_KEEP);
+  kf.key = draw_key(seed, (uint64_t)state[1], MV_SALT_KEEP);
   float2 acc = make_float2(0.f, 0.f);
   vae_item_walk(i, item_ptr, item_users, item_pos, slot_ptr, perm, lane, [&](int64_t slot, int pos) {
     if (kf(slot, pos)) {

@@ -5,10 +5,10 @@
 // butterfly (xor 8, 4, 2, 1), the same on every run.  No atomics.  LDS: 128 bytes of KL partials in mg_tail_rows_kernel, 2 112
 // bytes (256 + 8 doubles) in the single workgroup of mg_tail_final_kernel.
 //
-// The draws: key = vae_key(seed, state[1], salt); state[1] is the step counter chaorec_mvgae_tick advanced (state[0] += 1,
+// The draws: key = draw_key(seed, state[1], salt); state[1] is the step counter chaorec_mvgae_tick advanced (state[0] += 1,
 // state[1] = state[0]).  A draw is a function of (seed, step, salt, counters) alone, so a backward redraws its forward's.
-//   dropout of conv `salt` in 0..14: element (r, d) is KEPT when vae_uniform<24>(key, 0, r * 64 + d) >= 0.1
-//   noise of view x in (P, V, T, C) = 0..3: salt 16 + x (apart from the convs'), eps_x[r][d] = vae_normal<24>(key, r, d) --
+//   dropout of conv `salt` in 0..14: element (r, d) is KEPT when draw_uniform<24>(key, 0, r * 64 + d) >= 0.1
+//   noise of view x in (P, V, T, C) = 0..3: salt 16 + x (apart from the convs'), eps_x[r][d] = draw_normal<24>(key, r, d) --
 //   keyed by the table ROW: two batch slots that name one row see one noise row, as the reference's whole-table draw gives.
 //
 // (a) conv epilogue (BaseModel.update + the leaky_relu around it), per row r:
@@ -41,7 +41,7 @@
 //   chaorec_bpr_bwd_ordered_f32) -- dz_x += coef (z_p - z_n) | coef z_u | -coef z_u, one running fp32 sum per element; then
 //   the reparametrisation (the clamp passes gradient where l <= 10, equality included), the two PoE stages, all times
 //   gtotal[0].  A row without slots draws no noise.  All six tables are written whole.
-#include "vae_common.h"
+#include "draws.h"
 
 namespace chaorec {
 
@@ -62,18 +62,6 @@ __device__ __forceinline__ f4 mg_ld(const float *__restrict__ p) {
 __device__ __forceinline__ void mg_st(float *__restrict__ p, const f4 &a) {
   *reinterpret_cast<float4 *>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
 }
-__device__ __forceinline__ float mg_row_sum(float v) {   // over the row's 16 lanes, fixed order
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__global__ void mg_tick_kernel(int64_t *state) {
-  if (threadIdx.x || blockIdx.x) return;
-  const int64_t c = state[0] + 1;
-  state[0] = c;
-  state[1] = c;
-}
 
 // the dropout multiplier of the four elements (r, d0 .. d0 + 3)
 __device__ __forceinline__ f4 mg_mult(const uint8_t *__restrict__ keep, uint64_t key, int training, int64_t r, int d0) {
@@ -81,7 +69,7 @@ __device__ __forceinline__ f4 mg_mult(const uint8_t *__restrict__ keep, uint64_t
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     bool k = true;
-    if (training) k = keep ? keep[r * MG_D + d0 + j] != 0 : vae_uniform<24>(key, 0, (uint64_t)(r * MG_D + d0 + j)) >= MG_DROP;
+    if (training) k = keep ? keep[r * MG_D + d0 + j] != 0 : draw_uniform<24>(key, 0, (uint64_t)(r * MG_D + d0 + j)) >= MG_DROP;
     m.v[j] = training ? (k ? MG_KEEP_SCALE : 0.f) : 1.f;
   }
   return m;
@@ -103,8 +91,8 @@ __global__ __launch_bounds__(256) void mg_conv_kernel(const float *__restrict__ 
     a.v[j] = x.v[j] + b.v[j];
     ss += a.v[j] * a.v[j];
   }
-  const float n = sqrtf(mg_row_sum(ss)), dn = fmaxf(n, 1e-12f);
-  const f4 m = mg_mult(keep, training ? vae_key(seed, (uint64_t)state[1], salt) : 0, training, r, d0);
+  const float n = sqrtf(group_sum<16>(ss)), dn = fmaxf(n, 1e-12f);
+  const f4 m = mg_mult(keep, training ? draw_key(seed, (uint64_t)state[1], salt) : 0, training, r, d0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) q.v[j] = a.v[j] / dn;
   if constexpr (!BWD) {
@@ -123,7 +111,7 @@ __global__ __launch_bounds__(256) void mg_conv_kernel(const float *__restrict__ 
       gq.v[j] = g.v[j] * (t > 0.f ? 1.f : MG_SLOPE) * m.v[j];
       dot += gq.v[j] * q.v[j];
     }
-    dot = mg_row_sum(dot);
+    dot = group_sum<16>(dot);
 #pragma unroll
     for (int j = 0; j < 4; ++j) y.v[j] = n >= 1e-12f ? (gq.v[j] - q.v[j] * dot) / n : gq.v[j] / 1e-12f;
   }
@@ -184,7 +172,7 @@ __device__ __forceinline__ MgViews mg_views(const MgTables &t, int64_t r, int d0
 
 __device__ __forceinline__ float mg_eps(const float *__restrict__ eps, uint64_t seed, uint64_t step, int x, int64_t N, int64_t r, int d) {
   if (eps) return eps[((int64_t)x * N + r) * MG_D + d];
-  return vae_normal<24>(vae_key(seed, step, MG_VIEW_SALT + (uint64_t)x), (uint64_t)r, (uint64_t)d);
+  return draw_normal<24>(draw_key(seed, step, MG_VIEW_SALT + (uint64_t)x), (uint64_t)r, (uint64_t)d);
 }
 
 __global__ __launch_bounds__(256) void mg_tail_rows_kernel(MgTables t, int64_t N, float *__restrict__ Pm, double *__restrict__ partial) {
@@ -204,16 +192,13 @@ __global__ __launch_bounds__(256) void mg_tail_rows_kernel(MgTables t, int64_t N
       acc += (double)(1.f + lc - m * m - expf(lc));
     }
     if (!valid) acc = 0.0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = group_sum<64>(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][x] = acc;
   }
   __syncthreads();
   if (threadIdx.x < MG_VIEWS)
     partial[(int64_t)blockIdx.x * MG_VIEWS + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
-
-__device__ __forceinline__ int64_t mg_clamp_row(int64_t r, int64_t N) { return r < 0 ? 0 : (r >= N ? N - 1 : r); }
 
 __global__ __launch_bounds__(256) void mg_tail_batch_kernel(MgTables t, int64_t N, const int64_t *__restrict__ users, const int64_t *__restrict__ pos,
                                                             const int64_t *__restrict__ neg, int64_t B, const float *__restrict__ eps, uint64_t seed,
@@ -224,7 +209,7 @@ __global__ __launch_bounds__(256) void mg_tail_batch_kernel(MgTables t, int64_t 
   const int64_t b = valid ? b0 : B - 1;
   const int d0 = (threadIdx.x & 15) * 4;
   const uint64_t step = (uint64_t)state[1];
-  const int64_t rows[3] = {mg_clamp_row(users[b], N), mg_clamp_row(pos[b], N), mg_clamp_row(neg[b], N)};
+  const int64_t rows[3] = {clamp_index(users[b], N), clamp_index(pos[b], N), clamp_index(neg[b], N)};
   // The z rows and the scores in DOUBLE (3B rows only): a sample's coefficient is as sensitive to its score difference as
   // 1 : 1, and fp32 z rows of magnitude 30 leave that difference with an error of 1e-5 and more.  The rows kept for the
   // backward are these values rounded once.
@@ -269,12 +254,7 @@ __global__ __launch_bounds__(256) void mg_tail_batch_kernel(MgTables t, int64_t 
   }
 #pragma unroll
   for (int x = 0; x < MG_VIEWS; ++x) {
-    double p = dp[x], q = dq[x];
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      p += __shfl_xor(p, off, 64);
-      q += __shfl_xor(q, off, 64);
-    }
+    const double p = group_sum<16>(dp[x]), q = group_sum<16>(dq[x]);
     const double diff = p - q, e = exp(-diff), sg = 1.0 / (1.0 + e);
     const double om = e < 1.0 ? e / (1.0 + e) : 1.0 - sg;      // 1 - sigmoid without the cancellation near 1
     if (valid && (threadIdx.x & 15) == 0) {
@@ -295,12 +275,7 @@ __global__ __launch_bounds__(256) void mg_tail_final_kernel(const double *__rest
     } else {
       for (int64_t i = threadIdx.x; i < nblk; i += 256) v += partial[i * MG_VIEWS + (p - MG_VIEWS)];
     }
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-      __syncthreads();
-    }
+    block_sum_f64(v, red);
     if (threadIdx.x == 0) parts[p] = p < MG_VIEWS ? red[0] / (double)B : red[0] * (-0.5 / (double)N);
     __syncthreads();
   }
@@ -405,9 +380,7 @@ extern "C" int64_t chaorec_mvgae_rows_per_wave(void) { return MG_RW; }
 extern "C" int64_t chaorec_mvgae_rows_per_block(void) { return MG_RB; }
 
 extern "C" int chaorec_mvgae_tick(int64_t *state, void *stream) {
-  if (!state) return fail(CHAOREC_E_INVALID, "mvgae_tick: NULL argument");
-  hipLaunchKernelGGL(mg_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
-  return check_launch("mg_tick_kernel");
+  return launch_step_tick("mvgae_tick", state, stream);
 }
 
 extern "C" int chaorec_mvgae_conv_fwd_f32(const float *s, const float *bias, int64_t N, const uint8_t *keep, uint64_t seed, const int64_t *state,

@@ -14,13 +14,6 @@ namespace chaorec {
 
 constexpr float kCosEps = 1e-8f;   // F.cosine_similarity's eps (clamp on each norm)
 
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // out = w * y with w = <y, e> / (max(|y|, eps) * max(|e|, eps));  w_out[r] = w (optional)
 template <int LPR, int CPL>
 __global__ __launch_bounds__(256) void row_cosine_scale_fwd_kernel(const float4 *__restrict__ y,

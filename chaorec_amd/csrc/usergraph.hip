@@ -17,7 +17,7 @@
 //
 // Key convention (the project's): (count << 32) | (0xFFFFFFFF - id), larger key first = count descending, id ascending.
 // A key of 0 is "no entry" (a count of 0 is never stored).
-#include "common.h"
+#include "draws.h"
 
 namespace chaorec {
 
@@ -25,15 +25,9 @@ constexpr int UG_THREADS = 256;
 constexpr int UG_MAX_N = 256;          // neighbours kept per user (the reference keeps 200)
 constexpr int UG_MAX_TILE = 32768;     // 32-bit counters of one tile: 128 KiB of the CU's 160 KiB LDS
 
-__device__ __forceinline__ int ug_wave_sum_i32(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // sum / max of one int per thread over the workgroup, the same value returned to every thread (red: 4 ints of LDS)
 __device__ __forceinline__ int ug_block_sum(int v, int *red) {
-  v = ug_wave_sum_i32(v);
+  v = group_sum<64>(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(UG_THREADS) void ug_build_kernel(const int64_t *__r
 
 // r uniform in [0, n): the negative sampler's generator (bpr.hip sampler_draw) over (seed, epoch, user, slot)
 __device__ __forceinline__ uint32_t ug_draw(uint64_t seed, uint64_t epoch, uint32_t u, uint32_t slot, uint32_t n) {
-  const uint64_t h = mix64(seed ^ mix64(epoch ^ mix64(((uint64_t)u << 32) | slot)));
+  const uint64_t h = draw_hash(seed, epoch, ((uint64_t)u << 32) | slot);
   return (uint32_t)(((h >> 32) * (uint64_t)n) >> 32);
 }
 
@@ -293,8 +287,7 @@ __global__ __launch_bounds__(UG_THREADS) void ug_agg_bwd_kernel(const float *__r
   const float4 x = ln.raw(r);
   *reinterpret_cast<float4 *>((ln.which ? dt : dv) + r * D + ln.c) = mul_rn4(wu[r * 2 + ln.which], gx);
   float dot = add_rn(add_rn(mul_rn(gx.x, x.x), mul_rn(gx.y, x.y)), add_rn(mul_rn(gx.z, x.z), mul_rn(gx.w, x.w)));
-#pragma unroll
-  for (int off = D / 8; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);   // within the half's D / 4 lanes, fixed order
+  dot = group_sum<D / 4>(dot);   // within the half's D / 4 lanes
   if (ln.c == 0) dw[r * 2 + ln.which] = dot;
 }
 

@@ -1,13 +1,14 @@
-// What multvae.hip, macridvae.hip and dualvae.hip share: the tile geometry of their MFMA passes, the counter RNG, the
-// history-row and item-owner walks, the LDS staging of 64-float rows and the fixed-order reductions.  One definition each:
-// the three files keep their formulas, their kernel bodies and their exports.  Three things differ between the models ON
+// What multvae.hip, macridvae.hip and dualvae.hip share (and what graphaug.hip, adagcl.hip and diffmm.hip borrow of it): the
+// tile geometry of their MFMA passes, the history-row and item-owner walks, the LDS staging of 64-float rows and the
+// fixed-order reductions.  The counter RNG and the step tick are draws.h's, the arithmetic helpers common.h's.  One definition
+// each: the three files keep their formulas, their kernel bodies and their exports.  Three things differ between the models ON
 // PURPOSE and stay with them: the uniform's bit count (MultVAE 24, MacridVAE and -- through its epsilon -- DualVAE 23),
 // the tick kernels (MultVAE reads the counter and then increments it, the other two increment first) and vae_sum_kernel's
 // `accumulate` (MultVAE's sum of squares adds one parameter after the other).
 // The kernels here are static templates: a file that launches one has its own copy (the link sees no duplicate), a file
 // that does not has none -- `template <class = void>` is there for that alone.
 #pragma once
-#include "common.h"
+#include "draws.h"
 
 namespace chaorec {
 
@@ -27,21 +28,6 @@ __device__ __forceinline__ f32x16 vae_zero() {
   return v;
 }
 
-// counter RNG (seed, step, a, b) -> uniform STRICTLY inside (0, 1), BITS random bits + 0.5 (exact in fp32 for BITS <= 24;
-// log(-log(u)) is finite): a draw depends on its counters only, so a replayed graph whose step counter moved draws fresh
-// values and the backward redraws the forward's
-__device__ __forceinline__ uint64_t vae_key(uint64_t seed, uint64_t step, uint64_t salt) { return mix64(mix64(seed ^ salt) + step); }
-template <int BITS>
-__device__ __forceinline__ float vae_uniform(uint64_t key, uint64_t a, uint64_t b) {
-  const uint64_t r = mix64(key ^ mix64((a << 32) ^ b));
-  return ((float)(r >> (64 - BITS)) + 0.5f) * (1.0f / (float)(1 << BITS));
-}
-template <int BITS>
-__device__ __forceinline__ float vae_normal(uint64_t key, uint64_t a, uint64_t c) {   // Box-Muller
-  const float u1 = vae_uniform<BITS>(key, a, 2 * c), u2 = vae_uniform<BITS>(key, a, 2 * c + 1);
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
-
 template <int BITS>
 struct VaeKeep {   // is entry j of sample b's history row kept?  given flags (parity tests) or the counter RNG
   const uint8_t *keep;
@@ -52,7 +38,7 @@ struct VaeKeep {   // is entry j of sample b's history row kept?  given flags (p
   __device__ __forceinline__ bool operator()(int64_t b, int64_t j) const {
     if (!training) return true;
     if (keep) return keep[keep_off[b] + j] != 0;
-    return vae_uniform<BITS>(key, (uint64_t)b, (uint64_t)j) < keep_prob;
+    return draw_uniform<BITS>(key, (uint64_t)b, (uint64_t)j) < keep_prob;
   }
 };
 
@@ -178,22 +164,8 @@ static __global__ __launch_bounds__(256) void vae_sum_kernel(const float *__rest
   __shared__ double red[256];
   double v = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) v += (double)in[i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum_f64(v, red);
   if (threadIdx.x == 0) out[0] = (float)((accumulate ? (double)out[0] : 0.0) + red[0] * (double)scale);
-}
-
-// out[e] = std * N(0, 1) keyed (seed, state[1], SALT, e)
-template <int BITS, uint64_t SALT>
-static __global__ __launch_bounds__(256) void vae_normal_kernel(float *__restrict__ out, int64_t n, uint64_t seed,
-                                                                const int64_t *__restrict__ state, float std) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  out[e] = std * vae_normal<BITS>(vae_key(seed, (uint64_t)state[1], SALT), (uint64_t)e, 0);
 }
 
 // scores[u - u0, i] = mask for the history entries of users u0 .. u1 (the rankers' masking of seen items): one wave per user

@@ -898,10 +898,16 @@ def dualvae_check_shape(k, a=DUALVAE_A, hidden=DUALVAE_H):
                          f"hidden={DUALVAE_H}")
 
 
-def dualvae_tick(state):
-    """state[0] += 1, state[1] = state[0]: the step counter the device-drawn epsilon is keyed by."""
+def step_tick(state, export="chaorec_adagcl_tick"):
+    """state int64 [2] on the device: [0] += 1, [1] = [0] -- the step the device draws of the launches after it are keyed
+    by.  One kernel (csrc/draws.h) behind three exports, one per library file that launches it; a model without an export
+    of its own (GraphAug) calls this with the default."""
     _need_cuda(state)
-    _lib.load().chaorec_dualvae_tick(_ptr(state), _stream())
+    getattr(_lib.load(), export)(_ptr(state), _stream())
+
+
+def dualvae_tick(state):
+    step_tick(state, "chaorec_dualvae_tick")
 
 
 class _DualVAEEncode(torch.autograd.Function):
@@ -1414,9 +1420,7 @@ def mvgae_rows():
 
 
 def mvgae_tick(state):
-    """state[0] += 1, state[1] = state[0]: the step counter the device-drawn masks and noise are keyed by."""
-    _need_cuda(state)
-    _lib.load().chaorec_mvgae_tick(_ptr(state), _stream())
+    step_tick(state, "chaorec_mvgae_tick")
 
 
 class _MVGAEConvTail(torch.autograd.Function):
@@ -1661,9 +1665,7 @@ def adagcl_check_shape(D):
 
 
 def adagcl_tick(state):
-    """state int64 [2] on the device: [0] += 1, [1] = [0] -- the step the device draws are keyed by."""
-    _need_cuda(state)
-    _lib.load().chaorec_adagcl_tick(_ptr(state), _stream())
+    step_tick(state, "chaorec_adagcl_tick")
 
 
 def _adagcl_parts(structure, device):

@@ -1251,8 +1251,8 @@ int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const float *W_out,
  * kernel tiles (chaorec_adagcl_check_shape: CHAOREC_E_INVALID otherwise).  A row is owned by 8 lanes, a row longer than
  * chaorec_adagcl_long_row() = 64 entries by its wave; chaorec_adagcl_rows_per_block() = 32 rows per workgroup, which is also
  * the number of rows behind one float of `part` (n_part >= ceil(N / 32)).  No float atomics: every sum has one owner and a
- * fixed order.  state int64 [2]: chaorec_adagcl_tick does state[0] += 1, state[1] = state[0]; device draws are keyed
- * (seed, state[1], salt, entry).
+ * fixed order.  state int64 [2]: chaorec_adagcl_tick does state[0] += 1, state[1] = state[0] (the shared step tick of
+ * csrc/draws.h, as chaorec_dualvae_tick and chaorec_mvgae_tick launch it); device draws are keyed (seed, state[1], salt, entry).
  * --------------------------------------------------------------------------------------------------------------- */
 int chaorec_adagcl_check_shape(int32_t D);
 int64_t chaorec_adagcl_rows_per_block(void);
@@ -1303,7 +1303,7 @@ int64_t chaorec_graphaug_long_row(void);
  *   val[e] = s > 0.2 ? s : +0
  * A row is owned by 8 lanes (chaorec_graphaug_rows_per_block() = 32 rows per workgroup), a row longer than
  * chaorec_graphaug_long_row() = 64 entries by its wave.  u1, u2 fp32 [E] given, or NULL: drawn in the launch, keyed
- * (seed, state[1], salt, entry) -- state int64 [2] as chaorec_adagcl_tick keeps it; u_out fp32 [2, E] (may be NULL) receives
+ * (seed, state[1], salt, entry) -- state int64 [2] as the shared step tick keeps it (any of the three *_tick exports); u_out fp32 [2, E] (may be NULL) receives
  * the draws used.  val_t (may be NULL): val_t[tentry[e]] = val[e]; logit_out may be NULL.  One launch. */
 int chaorec_graphaug_sample_f32(const int64_t *rowptr, const int32_t *col, const int32_t *tentry, int64_t N, int64_t E,
                                 const float *P, const float *Q, const float *b1, const float *w2, const float *b2,

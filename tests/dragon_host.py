@@ -8,6 +8,7 @@ import os
 import numpy as np
 import scipy.sparse as sp
 import torch
+from vae_ops_host import mix64      # csrc/common.h mix64 on uint64 arrays
 
 TOPN = 200
 EPS32 = 2.0 ** -24          # unit roundoff of fp32
@@ -96,17 +97,8 @@ def check_ids(u, ids, counts, C, N=TOPN):
 
 
 # ---- (b) the epoch sample -------------------------------------------------------------------------------------------------
-def mix64(z):
-    """csrc/common.h mix64 on uint64 arrays (wrapping arithmetic)."""
-    with np.errstate(over="ignore"):
-        z = np.atleast_1d(np.asarray(z, dtype=np.uint64)) + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
 def draw(seed, epoch, u, slot, n):
-    """r uniform in [0, n): ((mix64(seed ^ mix64(epoch ^ mix64(u << 32 | slot))) >> 32) * n) >> 32, elementwise."""
+    """r uniform in [0, n): ((mix64(seed ^ mix64(epoch ^ mix64(u << 32 | slot))) >> 32) * n) >> 32, elementwise (csrc/draws.h draw_hash)."""
     u, slot, n = (np.atleast_1d(np.asarray(a, dtype=np.uint64)) for a in (u, slot, n))
     h = mix64(np.uint64(seed) ^ mix64(np.uint64(epoch) ^ mix64((u << np.uint64(32)) | slot)))
     return ((h >> np.uint64(32)) * n) >> np.uint64(32)

@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 import torch
+from vae_ops_host import vae_key, vae_uniform      # the counter RNG of csrc/draws.h in uint64 numpy
 
 D = 64
 E = 1e-8
@@ -51,34 +52,10 @@ def load_fixture(golden_dir, name="mvgae_small.npz"):
     return g
 
 
-# ---- the counter RNG (csrc/common.h mix64, csrc/vae_common.h) in uint64 numpy ------------------------------------------------
-_M = np.uint64
-
-
-def mix64(z):
-    z = np.asarray(z, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = z + _M(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> _M(30))) * _M(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> _M(27))) * _M(0x94D049BB133111EB)
-    return z ^ (z >> _M(31))
-
-
-def rng_key(seed, step, salt):
-    with np.errstate(over="ignore"):
-        return mix64(mix64(_M(seed) ^ _M(salt)) + _M(step))
-
-
-def rng_uniform24(key, a, b):
-    a, b = np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64)
-    r = mix64(key ^ mix64((a << _M(32)) ^ b))
-    return ((r >> _M(40)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / (1 << 24))
-
-
 def keep_mask(seed, step, salt, N):
     """The device's dropout flags of conv `salt`: uniform(key, 0, r * 64 + d) >= 0.1 (exact: the uniform is exact in fp32)."""
     e = np.arange(N * D, dtype=np.uint64)
-    return (rng_uniform24(rng_key(seed, step, salt), np.zeros_like(e), e) >= np.float32(0.1)).reshape(N, D)
+    return (vae_uniform(vae_key(seed, step, salt), 0, e, 24) >= np.float32(0.1)).reshape(N, D)
 
 
 # ---- (a) the conv epilogue -------------------------------------------------------------------------------------------------

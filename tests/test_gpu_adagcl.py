@@ -17,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adagcl_host as ah  # noqa: E402
+import vae_ops_host as vo  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -200,6 +201,34 @@ def test_device_draw():
     assert np.abs(m1 - ref).max() <= 4 * ULP
     # the evaluation form draws nothing and hands no u back
     assert ops_extra.adagcl_edge_gate(st, z, z, b, 1.0, 0.0, False, state, 1234, 0, None, return_parts=True)[4] is None
+
+
+@pytest.mark.parametrize("salt", [0, 1])
+def test_device_draw_is_the_host_generator_bit_for_bit(salt):
+    """On the ragged 40-node graph of vae_ops_host.ragged_rows, two ticks in: u = clamp(lo + (hi - lo) uniform24, lo, hi) in fp32."""
+    from chaorec_amd import ops_extra
+    st = vo.ragged_structure(dev())
+    lens = np.diff(vo.ragged_rows()[0])
+    assert st.n_rows == 40 and lens.max() == 70 and lens.min() == 0 and lens[lens < 70].max() <= 9
+    state = torch.zeros(2, dtype=torch.int64, device=dev())
+    ops_extra.adagcl_tick(state)
+    ops_extra.adagcl_tick(state)
+    z, b = torch.zeros(40, device=dev()), torch.zeros(1, device=dev())
+    u = ops_extra.adagcl_edge_gate(st, z, z, b, 0.5, 1e-6, True, state, 1234, salt, None, return_parts=True)[4].cpu().numpy()
+    lo, hi = np.float32(1e-7), np.float32(0.99999988)
+    ref = vo.vae_uniform(vo.vae_key(1234, 2, salt), 0, np.arange(st.nnz), 24)
+    ref = np.clip(lo + (hi - lo) * ref, lo, hi)
+    assert ref.dtype == np.float32 and u.dtype == np.float32 and np.array_equal(u.view(np.uint32), ref.view(np.uint32))
+
+
+def test_the_three_step_ticks_count_alike():
+    from chaorec_amd import ops_extra
+    ticks = (ops_extra.dualvae_tick, ops_extra.mvgae_tick, ops_extra.adagcl_tick)
+    states = [torch.zeros(2, dtype=torch.int64, device=dev()) for _ in ticks]
+    for step in (1, 2):
+        for tick, state in zip(ticks, states):
+            tick(state)
+        assert all(state.tolist() == [step, step] for state in states)
 
 
 # ---- the edge keep ------------------------------------------------------------------------------------------------------------

@@ -163,6 +163,34 @@ def test_device_draws_statistics(dev):
     assert abs(mean) <= 5 / np.sqrt(n.size) and abs(var - 1) <= 5 * np.sqrt(2 / n.size) and abs(rate - 0.5) <= 2.5 / np.sqrt(N)
 
 
+def test_device_draws_are_the_host_generator(dev):
+    """Users without history at B = 5, I = 33, a = 1, s = 1/2: x_in = kept ? n : 0 with no rounding of its own.  The non-zero
+    pattern is uniform(keep key, user, item) < 1/2 exactly; the kept n against the Box-Muller of the noise key's two uniforms in
+    float64, under test_gpu_vae_ops's rule: 4 x the same lines' deviation in float32, at least 2^-22, per row."""
+    import re
+    import vae_ops_host as vo
+    from chaorec_amd import ops_extra
+    with open(os.path.join(os.path.dirname(GOLDEN), "..", "chaorec_amd", "csrc", "diffmm.hip")) as f:
+        nbits = int(re.search(r"constexpr int DM_BITS = (\d+);", f.read()).group(1))
+    B, I, seed, step, salt = 5, 33, 123, 2, 1
+    rowptr, col = torch.zeros(B + 1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    x, bits = ops_extra.diffmm_rows(torch.arange(B, device=dev), rowptr, col, I, torch.ones(B, device=dev), torch.full((B,), 0.5, device=dev),
+                                    seed=seed, step=step, salt=salt)
+    x = x.cpu().numpy()
+    u, i = np.arange(B)[:, None], np.arange(I)[None, :]
+    kept = vo.vae_uniform(vo.vae_key(seed, step, 2 * salt + 1), u, i, nbits) < np.float32(0.5)
+    assert not bits.any() and kept.any() and not kept.all() and np.array_equal(x != 0, kept)
+    key = vo.vae_key(seed, step, 2 * salt)
+    u1, u2 = vo.vae_uniform(key, u, 2 * i, nbits), vo.vae_uniform(key, u, 2 * i + 1, nbits)
+    n64 = np.sqrt(-2.0 * np.log(u1.astype(np.float64))) * np.cos(2.0 * np.pi * u2.astype(np.float64))
+    n32 = np.sqrt(np.float32(-2.0) * np.log(u1)) * np.cos(np.float32(2.0 * np.pi) * u2)
+    assert n32.dtype == np.float32
+    got, ref64, ref32 = np.where(kept, x, 0), np.where(kept, n64, 0), np.where(kept, n32, 0)
+    d, bound = vo.row_dev(got, ref64), vo.bound_of(ref32, ref64)
+    print(f"device normal: deviation {d:.3e}, the float32 lines' own {vo.row_dev(ref32, ref64):.3e}, bound {bound:.3e}")
+    assert d <= bound
+
+
 # ---- (b) the one-pass node -----------------------------------------------------------------------------------------------------
 def node_case(B, I, Hd, seed):
     rng = np.random.default_rng(seed)

@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import graphaug_host as gh  # noqa: E402
+import vae_ops_host as vo  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,6 +132,22 @@ def test_sampler_device_draws():
     ops_extra.adagcl_tick(state)
     ticked = run_sampler(state=state, return_draws=True)
     assert not torch.equal(draws, ticked[3]) and not torch.equal(val, ticked[0])    # a tick later: fresh draws
+
+
+@pytest.mark.parametrize("salt", [0, 1])
+def test_sampler_device_draws_are_the_host_generator_bit_for_bit(salt):
+    """On the ragged 40-node graph of vae_ops_host.ragged_rows (a row of 70 entries, an empty one), two ticks in."""
+    from chaorec_amd import ops_extra
+    st = vo.ragged_structure(dev())
+    E = st.nnz
+    state = torch.zeros(2, dtype=torch.int64, device=dev())
+    ops_extra.adagcl_tick(state)
+    ops_extra.adagcl_tick(state)
+    PQ, v = torch.zeros((40, gh.D), device=dev()), torch.zeros(gh.D, device=dev())
+    u = ops_extra.graphaug_edge_sample(st, PQ, PQ, v, v, v[:1], None, None, state, 12345, salt, want_val_t=False, return_draws=True)[3].cpu().numpy()
+    GA_SALT = 0x6772617068617567
+    ref = np.stack([vo.vae_uniform(vo.vae_key(12345, 2, GA_SALT + 2 * salt + k), 0, np.arange(E), 24) for k in (0, 1)])
+    assert u.shape == (2, E) and u.dtype == ref.dtype == np.float32 and np.array_equal(u.view(np.uint32), ref.view(np.uint32))
 
 
 def test_sampler_rejects_other_widths():

@@ -7,16 +7,14 @@ construction); a check allows 4 x that.  The reference's summation order is torc
 so its own rounding noise is the floor; a formula error (a wrong anneal, a missing 1 / B, reg_weight instead of its
 square) shows at 1e-3 and up, two orders of magnitude outside."""
 import os
-import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_meta  # noqa: E402
 import multvae_host as mh  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -171,16 +169,9 @@ def test_abi_is_additive_and_every_status_is_checked():
 
 
 def test_kernels_compile_for_gfx950_without_scratch():
-    from chaorec_amd import _lib
-    hipcc = "hipcc" if subprocess.run(["which", "hipcc"], capture_output=True).returncode == 0 else "/opt/rocm/bin/hipcc"
-    flags = [f for f in _lib.HIPCC_FLAGS if f != "-shared"]
-    with tempfile.TemporaryDirectory() as tmp:
-        subprocess.check_call([hipcc] + flags + ["-c", os.path.join(ROOT, "chaorec_amd", "csrc", "multvae.hip"), "-o",
-                                                 os.path.join(tmp, "x.o"), "-save-temps=obj"], stderr=subprocess.DEVNULL)
-        text = open(os.path.join(tmp, [f for f in os.listdir(tmp) if f.endswith("gfx950.s")][0])).read()
-    kernels = re.findall(r"\.name:\s+(_ZN7chaorec\w+)", text)
-    scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text)]
-    spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s+(\d+)", text)]
+    text = kernel_meta.compile_asm("multvae.hip")
+    kernels, m = kernel_meta.kernel_metadata(text)
+    scratch, spills = m["scratch"], m["spills"]
     assert len(kernels) >= 12 and len(scratch) == len(kernels)
     assert not any(scratch) and not any(spills)
     assert "v_mfma_f32_32x32x2_f32" in text or "v_mfma_f32_32x32x2f32" in text

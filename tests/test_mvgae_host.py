@@ -7,15 +7,14 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_meta  # noqa: E402
 import mvgae_host as mh  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -233,17 +232,7 @@ def test_abi_is_additive_and_every_status_is_checked():
 
 def test_kernels_compile_for_gfx950_without_scratch():
     """Read from the compiler's metadata; no instruction text is inspected."""
-    from chaorec_amd import _lib
-    hipcc = "hipcc" if subprocess.run(["which", "hipcc"], capture_output=True).returncode == 0 else "/opt/rocm/bin/hipcc"
-    flags = [f for f in _lib.HIPCC_FLAGS if f != "-shared"]
-    with tempfile.TemporaryDirectory() as tmp:
-        subprocess.check_call([hipcc] + flags + ["-c", os.path.join(ROOT, "chaorec_amd", "csrc", "mvgae.hip"), "-o",
-                                                 os.path.join(tmp, "x.o"), "-save-temps=obj"], stderr=subprocess.DEVNULL)
-        text = open(os.path.join(tmp, [f for f in os.listdir(tmp) if f.endswith("gfx950.s")][0])).read()
-    meta = text.split(".amdgpu_metadata")[1]
-    kernels = re.findall(r"\.name:\s+(_ZN7chaorec\w+)", meta)
-    scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", meta)]
-    spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s+(\d+)", meta)]
-    sspills = [int(x) for x in re.findall(r"\.sgpr_spill_count:\s+(\d+)", meta)]
+    kernels, m = kernel_meta.kernel_metadata(kernel_meta.compile_asm("mvgae.hip"))
+    scratch, spills, sspills = m["scratch"], m["spills"], m["sspills"]
     assert len(kernels) == 7 and len(scratch) == len(kernels) == len(spills) == len(sspills)
     assert not any(scratch) and not any(spills) and not any(sspills)

@@ -1,8 +1,8 @@
 """Per-op torch restatements of the autoencoder ops (chaorec_amd/ops_extra.py over csrc/multvae.hip, macridvae.hip,
 dualvae.hip and csrc/vae_common.h), each on the DENSE form of its inputs and with its gradients taken by torch.autograd,
-plus a numpy uint64 restatement of the counter RNG (mix64 of csrc/common.h; vae_key, vae_uniform<BITS> of
-csrc/vae_common.h).  A helper module, not a conftest: imported by tests/test_vae_ops_host.py, which chains the ops into
-one step of each model against multvae_host / macridvae_host / dualvae_host (themselves tied to the reference's goldens).
+plus THE numpy uint64 restatement of the counter RNG (mix64 of csrc/common.h; draw_key, draw_uniform<BITS> of csrc/draws.h,
+here under the names vae_key, vae_uniform): mvgae_host, dragon_host and the graph models' GPU tests import it.
+A helper module, not a conftest: imported by tests/test_vae_ops_host.py, which chains the ops into one step of each model against multvae_host / macridvae_host / dualvae_host (themselves tied to the reference's goldens).
 It is the oracle for comparing the kernels op by op: each op alone, any upstream gradient, any mask.
 
 Every `*_fwd` function is plain torch on tensors of one dtype: run in float64 it is the oracle, run in float32 on the same
@@ -49,6 +49,27 @@ def vae_uniform(key, a, b, bits):
         r = mix64(_u64(key) ^ mix64((_u64(a) << np.uint64(32)) ^ _u64(b)))
     top = (r >> np.uint64(64 - bits)).astype(np.float32)
     return (top + np.float32(0.5)) * np.float32(1.0 / float(1 << bits))
+
+
+def ragged_rows():
+    """rowptr, col of the 40-node graph the graph models' device draws are pinned on: row 3 holds 70 entries (more than a
+    wave: the whole-wave path), row 7 none, the others 0 .. 9; 40 is no multiple of the 32 rows of a workgroup nor of the 8 of
+    a wave.  Columns repeat: the draws are keyed by the entry's place alone."""
+    lens = np.array([(3 * n + 1) % 10 for n in range(40)])
+    lens[3], lens[7] = 70, 0
+    rowptr = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+    col = np.concatenate([(n + 1 + np.arange(k)) % 40 for n, k in enumerate(lens)]).astype(np.int32)
+    return rowptr, col
+
+
+def ragged_structure(device):
+    """ragged_rows as a graph.DropoutStructure on `device` (the launches drawn on it read no transposed entry)."""
+    from chaorec_amd import graph
+    rowptr, col = (torch.from_numpy(v) for v in ragged_rows())
+    E = col.numel()
+    entry_row = torch.repeat_interleave(torch.arange(40, dtype=torch.int32), rowptr[1:] - rowptr[:-1])
+    csr = graph.CSR(rowptr, col, torch.ones(E), 40, 40, symmetric=True)
+    return graph.DropoutStructure(csr, entry_row, torch.arange(E, dtype=torch.int32)).to(device)
 
 
 def predict_keep(seed, step, salt, bits, keep_prob, rowptr, col, users, I):
