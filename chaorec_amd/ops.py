@@ -276,6 +276,34 @@ def spmm_rowsparse_raw(csr, x, y, alpha=1.0, z=None, beta=0.0, src_bits=None, z_
     return y
 
 
+FEWSRC_WIDTHS = (64,)                 # csrc/spmm_fewsrc.hip: the widths it is built for ..
+FEWSRC_MAX_ROWS = 48 * 1024 * 8       # .. and the rows whose bitmap fits its LDS copy (tests/test_gpu_fewsrc.py: both refused beyond)
+
+
+def spmm_fewsrc_raw(csr, x, y, bits, alpha=1.0, z=None, beta=0.0, z_bits=None):
+    """y = alpha * (A x) [+ beta z] for an x with FEW non-zero rows over a graph whose row bitmap fits in LDS
+    (chaorec_spmm_csr_fewsrc_f32): every row of y is written, only the rows of x flagged in `bits` are gathered and only the
+    rows of z flagged in z_bits (default: `bits`) are read -- the others hold +0 and are never loaded.  spmm_raw's result bit
+    for bit.  D in FEWSRC_WIDTHS, at most FEWSRC_MAX_ROWS rows, a square graph with static values."""
+    if z is not None and z_bits is None:
+        z_bits = bits
+    _need_cuda(csr.rowptr, x, y, z, bits, z_bits)
+    x = _f32c(x)
+    D = x.shape[1]
+    if x.shape[0] != csr.n_cols or y.shape != (csr.n_rows, D) or not y.is_contiguous() or y.dtype != torch.float32 or \
+            (z is not None and (z.shape != y.shape or not z.is_contiguous() or z.dtype != torch.float32)):
+        raise ValueError("spmm_fewsrc: contiguous float32 [n, D] operands of the graph's size")
+    if getattr(csr, "dynamic_values", False):
+        raise ValueError("spmm_fewsrc: a graph with per-step values has no static schedule")
+    for b in (bits, z_bits):
+        if b is not None and b.numel() * 32 < csr.n_rows:
+            raise ValueError("spmm_fewsrc: bitmap shorter than the graph's rows")
+    _lib.load().chaorec_spmm_csr_fewsrc_f32(_ptr(csr.col), _ptr(csr.val), _ptr(x), _ptr(y), csr.n_rows, csr.n_cols, D, alpha,
+                                            _ptr(z), beta, _ptr(csr.schedule(D)), _ptr(bits),
+                                            _ptr(z_bits if z is not None else None), _stream())
+    return y
+
+
 def spmm_adam_raw(csr, x, param, exp_avg, exp_avg_sq, bias_corr, lr, betas, eps, weight_decay, alpha=1.0, z=None,
                   beta=0.0, clear_z=False, grad_out=None, clear_bits=()):
     """g = alpha * (A x) [+ beta z] and the Adam update of `param` with that gradient, row by row, in ONE launch

@@ -469,6 +469,17 @@ def _frontier_modes(n_rows, n_layers, D, width_ok, sparse_bwd=None):
     return wide_ok, sparse_bwd, light
 
 
+def _few_source_mode(n_rows, n_layers, D, batch_size, sparse_bwd):
+    """-> whether the first backward propagate of a fused step gathers the batch's rows only (ops.spmm_fewsrc_raw): a mode of
+    its own, for the graphs the row-sparse backward is switched off for.  On when the row-sparse backward is off, n_layers >= 2,
+    the launch is built for D, the row bitmap fits its LDS copy and the batch's 3 B rows are at most a quarter of the table
+    (12 B <= n_rows: a rule, not a tuned number -- sports is at 7 %).  CHAOREC_FEW_SOURCE_BACKWARD = auto / 0 / 1: by that
+    rule / off / on wherever the launch exists."""
+    mode = os.environ.get("CHAOREC_FEW_SOURCE_BACKWARD", "auto")
+    built = (not sparse_bwd) and n_layers >= 2 and D in ops.FEWSRC_WIDTHS and n_rows <= ops.FEWSRC_MAX_ROWS
+    return bool(built and mode != "0" and (mode == "1" or 12 * batch_size <= n_rows))
+
+
 class _FusedStep:
     """What FusedLightGCNStep and dist_lightgcn.FusedShardedLightGCNStep share around their launch sequences: the
     constructor checks, the moment views, state save / restore, the capture protocol and replay.  A subclass supplies
@@ -657,6 +668,9 @@ class FusedLightGCNStep(_FusedStep):
         # Same sums bit for bit (the skipped terms are val * (+0)).  bits[0] = R0 (set by the BPR launch), bits[1] = N1.  It pays
         # where the frontier is a part of the graph and costs launches where it is not (sports: N1 is half the graph, N2 all of
         # it), hence by size.  CHAOREC_SPARSE_BACKWARD=0 / 1: off / forced.
+        # Where it is off and the batch is a small part of the table (sports: R0 is 7 % of the rows, their entries 14 % of the
+        # graph's) the FIRST backward propagate alone still gathers G's rows only -- `few_src`, see _few_source_mode: one launch
+        # that writes every row and tests every entry against R0's bitmap in LDS; nothing is expanded, no launch is added.
         wide_ok, self.sparse_bwd, light_by_size = self.frontier_modes(N, L, D)
         # Light forward.  train_and_evaluate.py:43-48 reads the propagated table (Model/LightGCN.py:95's mean) in the batch's
         # rows R0 only; the other rows of `model.result` are a by-product that nothing looks at before the next evaluation.
@@ -675,6 +689,8 @@ class FusedLightGCNStep(_FusedStep):
         self.light = bool(light_forward)
         if self.light and not self.sparse_bwd:
             self.sparse_bwd = True              # (its bitmaps and N1's list are the forward's as well)
+        self.few_src = _few_source_mode(N, L, D, self.B, self.sparse_bwd)
+        self._few_bits = ops.row_bitmap(N, dev) if self.few_src else None     # R0: set by the BPR launch, cleared by Adam's
         self.bits = None
         if self.sparse_bwd:
             words = (N + 31) // 32 + 1
@@ -698,7 +714,8 @@ class FusedLightGCNStep(_FusedStep):
 
     def _state_tensors(self):
         counters = [t for t in (self.step_dev, self.perm_pos, self.loss_accum, self.optimizer._step_dev) if t is not None]
-        return [self.model._flat, self.m, self.v] + counters, [self.G] + ([self._bits_all] if self.sparse_bwd else [])
+        scratch = [self.G] + ([self._bits_all] if self.sparse_bwd else []) + ([self._few_bits] if self.few_src else [])
+        return [self.model._flat, self.m, self.v] + counters, scratch
 
     @staticmethod
     def frontier_modes(n_rows, n_layers, D):
@@ -718,6 +735,7 @@ class FusedLightGCNStep(_FusedStep):
         light = self.light if light is None else bool(light)
         draw = self.edges is not None
         ws = self.ws if k == 1 else self.ws_steps[j]
+        r0_bits = self.bits[0] if self.sparse_bwd else self._few_bits       # (None: no launch of this step reads R0's bitmap)
         if light:
             ops.batch_rows(self.ids, self.bits[0], model.num_user, self._list0, self._list0_n, edges=self.edges,
                            hist=model.hist if draw else None, num_user=model.num_user, num_item=model.num_item, seed=self.seed,
@@ -739,7 +757,7 @@ class FusedLightGCNStep(_FusedStep):
                             ws, self.ids, edges=self.edges, hist=model.hist if draw else None, num_user=model.num_user,
                             num_item=model.num_item, seed=self.seed, step=j, step_dev=self.step_dev, perm=self.perm,
                             perm_pos=self.perm_pos, adam_step=opt._step_dev, betas=group["betas"], adam_bc=self.bc,
-                            pos_offset=j * B, row_bits=self.bits[0] if self.sparse_bwd else None)
+                            pos_offset=j * B, row_bits=r0_bits)
         book = dict(out_total=self.static_loss, loss_accum=self.loss_accum, advance=self.step_dev if draw else None,
                     perm_pos=self.perm_pos if (draw and self.perm is not None) else None)
         if k == 1:
@@ -759,12 +777,15 @@ class FusedLightGCNStep(_FusedStep):
             elif self.sparse_bwd and l < 2:
                 # every row computed and written (its reader is dense), gathers gated by the source's bitmap
                 ops.spmm_rowsparse_raw(csr, g, y, alpha=alpha, z=self.G, beta=w, src_bits=self.bits[l], z_bits=self.bits[0])
+            elif self.few_src and l == 0:
+                # g = G: every row written (the next launch reads y densely), only R0's rows gathered
+                ops.spmm_fewsrc_raw(csr, g, y, r0_bits, alpha=alpha, z=self.G, beta=w)
             else:
                 ops.spmm_raw(csr, g, y=y, alpha=alpha, z=self.G, beta=w)
             g, alpha = y, 1.0
         ops.spmm_adam_raw(csr, g, x0, self.m, self.v, self.bc, group["lr"], group["betas"], group["eps"],
                           group["weight_decay"], alpha=alpha, z=self.G, beta=w, clear_z=L >= 2,
-                          clear_bits=(self._bits_all,) if self.sparse_bwd else ())
+                          clear_bits=(self._bits_all,) if self.sparse_bwd else (self._few_bits,) if self.few_src else ())
         if L < 2:
             self.G.zero_()                      # (the single backward SpMM gathers from G: it cannot clear it)
         self._publish(not light)

@@ -149,6 +149,20 @@ int chaorec_spmm_csr_rowsparse_f32(const int64_t *rowptr, const int32_t *col, co
                                    const uint32_t *z_bits, uint32_t *out_bits, const uint32_t *row_bits,
                                    int32_t write_zeros, void *stream);
 
+/* The same propagate for a source with FEW non-zero rows over a graph small enough that the bitmap fits in LDS (the first
+ * backward propagate of a BPR step, train_and_evaluate.py:46 loss.backward() through Model/LightGCN.py:81-83, on a graph like
+ * sports: 3 B batch rows out of 44 147) -- csrc/spmm_fewsrc.hip.  y = alpha (A x) + beta z with EVERY row of y written and
+ * only the flagged rows of x gathered / of z read: rows of x whose bit in src_bits is clear, and rows of z whose bit in z_bits
+ * is clear, must hold +0 and are never loaded.  Bit for bit chaorec_spmm_csr_f32's result on the same operands (finite
+ * values).  Every workgroup copies src_bits into LDS and tests every entry there; a row's lanes test different entries at
+ * once.  A square graph (n_rows == n_cols, bitmaps over its rows: uint32 words, bit r & 31 of word r >> 5), its static
+ * schedule (chaorec_spmm_build_schedule; no DYNAMIC_VALUES mode), D = 64, (n_rows + 31) / 32 words <= 48 KiB of LDS, x / y /
+ * z 16-byte aligned; z and z_bits come together or not at all (z_bits == src_bits: tested in LDS too).  Anything else:
+ * CHAOREC_E_INVALID. */
+int chaorec_spmm_csr_fewsrc_f32(const int32_t *col, const float *val, const float *x, float *y, int64_t n_rows,
+                                int64_t n_cols, int32_t D, float alpha, const float *z, float beta,
+                                const int32_t *schedule, const uint32_t *src_bits, const uint32_t *z_bits, void *stream);
+
 /* bits_out |= bits_self | {columns of the rows flagged in bits_in}: the rows a propagate can make non-zero when its source
  * is non-zero in the flagged rows only.  bits_in: a bitmap over the CSR's n_rows rows; bits_self (optional) and bits_out:
  * bitmaps over its n_out_rows COLUMNS (symmetric graph: bits_self = bits_in, n_out_rows = n_rows; a user shard's
