@@ -16,17 +16,16 @@
 namespace chaorec {
 
 
-// the wave of triple b: three row gathers, five wave butterflies, lane 0 writes the term / coefficient / L2 parts
-__device__ __forceinline__ float bpr_terms_wave(const float *__restrict__ tab_u, const float *__restrict__ tab_i,
-                                                int64_t iu, int64_t ip, int64_t in, int b, int B, int D, int variant,
-                                                float *__restrict__ coef, float *__restrict__ ws) {
+// the wave of triple b: five wave butterflies over the three rows' elements -- rows(k, u, p, n) yields element k of the user /
+// positive / negative row --, lane 0 writes the term / coefficient / L2 parts
+template <class Rows>
+__device__ __forceinline__ float bpr_terms_wave_of(Rows &&rows, int b, int B, int D, int variant, float *__restrict__ coef,
+                                                   float *__restrict__ ws) {
   const int lane = threadIdx.x & 63;
-  const float *pu = tab_u + (size_t)iu * D;
-  const float *pp = tab_i + (size_t)ip * D;
-  const float *pn = tab_i + (size_t)in * D;
   float sp = 0.f, sn = 0.f, ru = 0.f, rp = 0.f, rn = 0.f;
   for (int k = lane; k < D; k += 64) {
-    const float u = pu[k], p = pp[k], n = pn[k];
+    float u, p, n;
+    rows(k, u, p, n);
     sp += u * p;
     sn += u * n;
     ru += u * u;
@@ -63,6 +62,17 @@ __device__ __forceinline__ float bpr_terms_wave(const float *__restrict__ tab_u,
     ws[3 * B + b] = rn;
   }
   return __shfl(c, 0, 64);
+}
+
+// ... with three row gathers from a table
+__device__ __forceinline__ float bpr_terms_wave(const float *__restrict__ tab_u, const float *__restrict__ tab_i,
+                                                int64_t iu, int64_t ip, int64_t in, int b, int B, int D, int variant,
+                                                float *__restrict__ coef, float *__restrict__ ws) {
+  const float *pu = tab_u + (size_t)iu * D;
+  const float *pp = tab_i + (size_t)ip * D;
+  const float *pn = tab_i + (size_t)in * D;
+  return bpr_terms_wave_of([&](int k, float &u, float &p, float &n) { u = pu[k], p = pp[k], n = pn[k]; }, b, B, D, variant,
+                           coef, ws);
 }
 
 __global__ __launch_bounds__(256) void bpr_fwd_terms_kernel(
@@ -109,11 +119,46 @@ __global__ __launch_bounds__(256) void bpr_fwd_terms_drawn_kernel(
   bpr_terms_wave(tab_u, tab_i, u, p, n, b, B, D, variant, coef, ws);
 }
 
+// Layer-table row source (the MEAN instantiation of the launch below; an INNER step of a k-step replay of the fused LightGCN
+// step): the propagated table the loss reads, final = w x_0 + w x_1 + ... + w x_L, is needed in the batch's 3 B rows only, and
+// nothing outside the step sees it before the next step overwrites it -- so the last forward propagate writes plain x_L and
+// the wave of triple b forms its three rows of the mean itself, with the SAME sequence of separately rounded multiplies and
+// adds as the epilogue that otherwise forms the whole table (csrc/spmm.hip, the acc / mean_t1 / mean_t2 block): the same bits.
+// The wave keeps its rows in registers for its own dot products and gradient adds (D <= 64 kMeanMaxQ; reading them back from
+// memory put a store -> load round trip into a launch that is nothing but latency: 7.3 -> 10.9 us) and parks them in `rows`
+// ([3 B, D]: triple b's user, positive, negative at 3 b, 3 b + 1, 3 b + 2) for the ordered launch, which would otherwise
+// form them again.
+constexpr int kMeanMaxTabs = 4;
+constexpr int kMeanMaxQ = 4;
+struct MeanSrc {
+  const float *t[kMeanMaxTabs];             // x_0 .. x_L, [N, D] each, users first
+  int n;
+  float w;
+  int64_t item_offset;                      // row of item 0
+  float *rows;
+};
+// (NT, the table count, is a template parameter of the launch: with a run-time count every table's load sat in a branch of
+//  its own and waited for the one before -- twelve round trips in a row instead of one, 7.4 -> 10.7 us)
+template <int NT>
+__device__ __forceinline__ void mean_elems(const MeanSrc &M, size_t ou, size_t op, size_t on, float &mu, float &mp, float &mn) {
+  float tu[NT], tp[NT], tn[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) tu[i] = M.t[i][ou], tp[i] = M.t[i][op], tn[i] = M.t[i][on];
+  mu = mul_rn(M.w, tu[0]), mp = mul_rn(M.w, tp[0]), mn = mul_rn(M.w, tn[0]);
+#pragma unroll
+  for (int i = 1; i < NT; ++i) {
+    mu = add_rn(mu, mul_rn(M.w, tu[i]));
+    mp = add_rn(mp, mul_rn(M.w, tp[i]));
+    mn = add_rn(mn, mul_rn(M.w, tn[i]));
+  }
+}
+
 // Forward terms AND the backward's row updates in one launch, for a loss that is differentiated with d(loss) = 1
 // (a plain loss.backward()): the coefficient of sample b depends on its own score difference only, never on the
 // batch total, so the wave that just reduced the triple adds its three gradient rows right away -- the same
 // 256-B atomic row adds, the same values as bpr_bwd_kernel with grad_out = 1.  g_u / g_i must be zero where no
 // sample lands (the caller keeps such a buffer: see chaorec_spmm_csr_adam_f32's clear_z).
+template <int NT>      // 0: the rows of tab_u / tab_i; 1 .. kMeanMaxTabs: the mean of that many layer tables (MeanSrc)
 __global__ __launch_bounds__(256) void bpr_fwd_bwd_drawn_kernel(
     const float *__restrict__ tab_u, const float *__restrict__ tab_i, const int64_t *__restrict__ edges,
     int64_t n_edges, const int64_t *__restrict__ hist_rowptr, const int32_t *__restrict__ hist_col, int64_t num_user,
@@ -122,7 +167,9 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_drawn_kernel(
     int64_t *__restrict__ out_users, int64_t *__restrict__ out_pos, int64_t *__restrict__ out_neg, int B, int D,
     int variant, float reg_weight, float *__restrict__ coef, float *__restrict__ ws, const int64_t *__restrict__ perm,
     const int64_t *__restrict__ perm_pos, float *g_u, float *g_i, int32_t *__restrict__ adam_step, float beta1,
-    float beta2, float *__restrict__ adam_bc, int64_t pos_offset, uint32_t *row_bits, int64_t bits_item_offset) {
+    float beta2, float *__restrict__ adam_bc, int64_t pos_offset, uint32_t *row_bits, int64_t bits_item_offset,
+    const MeanSrc M) {
+  constexpr bool MEAN = NT > 0;
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   // the optimizer's step count and this step's bias corrections (two double pow()s on one otherwise idle thread,
@@ -151,12 +198,33 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_drawn_kernel(
     p = in_pos[b];
     n = in_neg[b];
   }
-  const float c = bpr_terms_wave(tab_u, tab_i, u, p, n, b, B, D, variant, coef, ws) * 1.0f;
+  float mu[kMeanMaxQ], mp[kMeanMaxQ], mn[kMeanMaxQ];     // MEAN: elements lane + 64 i of the three rows
+  auto pick = [&](const float (&m)[kMeanMaxQ], int k) { return k < 64 ? m[0] : k < 128 ? m[1] : k < 192 ? m[2] : m[3]; };
+  float c;
+  if constexpr (MEAN) {
+    float *rows = M.rows + (size_t)3 * b * D;
+#pragma unroll
+    for (int i = 0; i < kMeanMaxQ; ++i) {
+      const int k = lane + 64 * i;
+      mu[i] = mp[i] = mn[i] = 0.f;
+      if (k < D) {
+        mean_elems<MEAN ? NT : 1>(M, (size_t)u * D + k, (size_t)(M.item_offset + p) * D + k, (size_t)(M.item_offset + n) * D + k,
+                                  mu[i], mp[i], mn[i]);
+        rows[k] = mu[i], rows[D + k] = mp[i], rows[2 * D + k] = mn[i];
+      }
+    }
+    c = bpr_terms_wave_of([&](int k, float &uu, float &pp, float &nn) { uu = pick(mu, k), pp = pick(mp, k), nn = pick(mn, k); },
+                          b, B, D, variant, coef, ws) * 1.0f;
+  } else {
+    c = bpr_terms_wave(tab_u, tab_i, u, p, n, b, B, D, variant, coef, ws) * 1.0f;
+  }
   const float r2 = 1.0f * 2.0f * reg_weight / ((float)B * (float)D);
   const size_t ou = (size_t)u * D, op = (size_t)p * D, on = (size_t)n * D;
   if (g_u) {                               // (NULL: the ordered launch that follows adds the rows -- CHAOREC_BPR_ORDERED=2)
     for (int k = lane; k < D; k += 64) {
-      const float uu = tab_u[ou + k], pp = tab_i[op + k], nn = tab_i[on + k];
+      float uu, pp, nn;
+      if constexpr (MEAN) uu = pick(mu, k), pp = pick(mp, k), nn = pick(mn, k);
+      else uu = tab_u[ou + k], pp = tab_i[op + k], nn = tab_i[on + k];
       atomicAdd(g_u + ou + k, c * (pp - nn) + r2 * uu);
       atomicAdd(g_i + op + k, c * uu + r2 * pp);
       atomicAdd(g_i + on + k, -c * uu + r2 * nn);
@@ -422,6 +490,7 @@ struct OrdArgs {
   float *g_u;
   float r2_unit;                            // single term: 2 reg / (B D), times grad_out; multi: 0
   int B, D, T;
+  const float *rows;                        // joined only, or NULL: triple b's three table rows at 3 b .. 3 b + 2 (MeanSrc)
   int joined;                               // 1: ONE group of 3 B slots (users, pos, neg of term 0: g_u and g_i may alias)
   int n_groups;
   int wg_begin[2 * kBprMaxTerms + 2];       // first workgroup of group g (a 1-D grid: no workgroup without slots); [n_groups] = all
@@ -488,8 +557,12 @@ __global__ __launch_bounds__(64 * kOrdWaves) void bpr_bwd_ordered_kernel(const O
   auto contribution = [&](int j, float (&v)[NQ]) __attribute__((always_inline)) {
     const OrdSlot s = ord_slot(P, g, __builtin_amdgcn_readfirstlane(j));
     const float c = P.coef[(size_t)s.term * P.B + s.b] * (go0 * (P.wvec ? P.wvec[s.term] : 1.0f));
-    const float *tab_i = P.A.tab_i[s.term];
-    const size_t ou = (size_t)P.users[s.b] * D, op = (size_t)P.A.pos[s.term][s.b] * D, on = (size_t)P.A.neg[s.term][s.b] * D;
+    const float *tab_u = P.tab_u, *tab_i = P.A.tab_i[s.term];
+    size_t ou = (size_t)P.users[s.b] * D, op = (size_t)P.A.pos[s.term][s.b] * D, on = (size_t)P.A.neg[s.term][s.b] * D;
+    if (P.rows) {                            // (kernel-uniform)
+      tab_u = tab_i = P.rows;
+      ou = (size_t)3 * s.b * D, op = ou + D, on = ou + 2 * D;
+    }
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const int q = lane + 64 * i;
@@ -497,9 +570,9 @@ __global__ __launch_bounds__(64 * kOrdWaves) void bpr_bwd_ordered_kernel(const O
       if (q < D) {
         if (s.role == 0) {
           const float p = tab_i[op + q], nn = tab_i[on + q];
-          v[i] = P.joined ? c * (p - nn) + r2 * P.tab_u[ou + q] : c * (p - nn);
+          v[i] = P.joined ? c * (p - nn) + r2 * tab_u[ou + q] : c * (p - nn);
         } else {
-          const float u = P.tab_u[ou + q];
+          const float u = tab_u[ou + q];
           const float cu = (s.role & 1) ? c * u : -c * u;
           v[i] = (P.joined && s.role <= 2) ? cu + r2 * tab_i[((s.role & 1) ? op : on) + q] : cu;
         }
@@ -804,20 +877,20 @@ extern "C" int chaorec_bpr_fwd_bwd_f32(const float *tab_u, const float *tab_i, c
                                     nullptr, 0, stream);
 }
 
-extern "C" int chaorec_bpr_bwd_ordered_f32(const float *tab_u, const float *tab_i, const int64_t *users, const int64_t *pos,
-                                           const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight,
-                                           const float *grad_out, float *g_u, float *g_i, void *stream);
+static int bpr_bwd_ordered(const float *tab_u, const float *tab_i, const float *rows, const int64_t *users, const int64_t *pos,
+                           const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight, const float *grad_out,
+                           float *g_u, float *g_i, void *stream);
 
-extern "C" int chaorec_bpr_fwd_bwd_at_f32(const float *tab_u, const float *tab_i, const int64_t *edges, int64_t n_edges,
-                                          const int64_t *hist_rowptr, const int32_t *hist_col, int64_t num_user,
-                                          int32_t num_item, uint64_t seed, uint64_t step, const int64_t *step_dev,
-                                          const int64_t *in_users, const int64_t *in_pos, const int64_t *in_neg,
-                                          int32_t B, int32_t D, int32_t variant, float reg_weight, int64_t *out_users,
-                                          int64_t *out_pos, int64_t *out_neg, float *coef, float *workspace,
-                                          const int64_t *perm, const int64_t *perm_pos, int64_t pos_offset, float *g_u,
-                                          float *g_i, int32_t *adam_step, float beta1, float beta2, float *adam_bc,
-                                          uint32_t *row_bits, int64_t bits_item_offset, void *stream) {
-  if (!tab_u || !tab_i || !coef || !workspace || !g_u || !g_i) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: NULL argument");
+// (mean: NULL = the rows of tab_u / tab_i; else the layer-table row source, tab_u / tab_i unused)
+static int bpr_fwd_bwd(const float *tab_u, const float *tab_i, const MeanSrc *mean, const int64_t *edges, int64_t n_edges,
+                       const int64_t *hist_rowptr, const int32_t *hist_col, int64_t num_user, int32_t num_item, uint64_t seed,
+                       uint64_t step, const int64_t *step_dev, const int64_t *in_users, const int64_t *in_pos,
+                       const int64_t *in_neg, int32_t B, int32_t D, int32_t variant, float reg_weight, int64_t *out_users,
+                       int64_t *out_pos, int64_t *out_neg, float *coef, float *workspace, const int64_t *perm,
+                       const int64_t *perm_pos, int64_t pos_offset, float *g_u, float *g_i, int32_t *adam_step, float beta1,
+                       float beta2, float *adam_bc, uint32_t *row_bits, int64_t bits_item_offset, void *stream) {
+  if ((!mean && (!tab_u || !tab_i)) || !coef || !workspace || !g_u || !g_i)
+    return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: NULL argument");
   if (pos_offset < 0) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: pos_offset %lld", (long long)pos_offset);
   if (adam_step && !adam_bc) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: adam_step without adam_bc");
   if (edges) {
@@ -835,14 +908,64 @@ extern "C" int chaorec_bpr_fwd_bwd_at_f32(const float *tab_u, const float *tab_i
   const char *env = std::getenv("CHAOREC_BPR_ORDERED");
   bool ordered = env && env[0] == '2' && 3 * (int64_t)B <= kOrdMaxSlots && D <= 256;
   const int64_t *ids_u = edges ? out_users : in_users, *ids_p = edges ? out_pos : in_pos, *ids_n = edges ? out_neg : in_neg;
-  hipLaunchKernelGGL(bpr_fwd_bwd_drawn_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, tab_u, tab_i, edges,
-                     n_edges, hist_rowptr, hist_col, num_user, (uint32_t)num_item, seed, step, step_dev, in_users, in_pos,
-                     in_neg, out_users, out_pos, out_neg, B, D, variant, reg_weight, coef, workspace, perm, perm_pos,
-                     ordered ? (float *)nullptr : g_u, g_i, adam_step, beta1, beta2, adam_bc, pos_offset, row_bits,
-                     bits_item_offset);
+#define CHAOREC_BPR_FWD_BWD_ARGS                                                                                            \
+  tab_u, tab_i, edges, n_edges, hist_rowptr, hist_col, num_user, (uint32_t)num_item, seed, step, step_dev, in_users, in_pos,    \
+      in_neg, out_users, out_pos, out_neg, B, D, variant, reg_weight, coef, workspace, perm, perm_pos,                          \
+      ordered ? (float *)nullptr : g_u, g_i, adam_step, beta1, beta2, adam_bc, pos_offset, row_bits, bits_item_offset
+#define CHAOREC_BPR_FWD_BWD_LAUNCH(NT, M)                                                                                   \
+  hipLaunchKernelGGL(bpr_fwd_bwd_drawn_kernel<NT>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream,                        \
+                     CHAOREC_BPR_FWD_BWD_ARGS, M)
+  static_assert(kMeanMaxTabs == 4, "one instantiation per table count below");
+  if (!mean) CHAOREC_BPR_FWD_BWD_LAUNCH(0, MeanSrc{});
+  else if (mean->n == 1) CHAOREC_BPR_FWD_BWD_LAUNCH(1, *mean);
+  else if (mean->n == 2) CHAOREC_BPR_FWD_BWD_LAUNCH(2, *mean);
+  else if (mean->n == 3) CHAOREC_BPR_FWD_BWD_LAUNCH(3, *mean);
+  else CHAOREC_BPR_FWD_BWD_LAUNCH(4, *mean);
+#undef CHAOREC_BPR_FWD_BWD_LAUNCH
+#undef CHAOREC_BPR_FWD_BWD_ARGS
   int rc = check_launch("bpr_fwd_bwd_drawn_kernel");
   if (rc || !ordered) return rc;
-  return chaorec_bpr_bwd_ordered_f32(tab_u, tab_i, ids_u, ids_p, ids_n, B, D, coef, reg_weight, nullptr, g_u, g_i, stream);
+  return bpr_bwd_ordered(tab_u, tab_i, mean ? mean->rows : nullptr, ids_u, ids_p, ids_n, B, D, coef, reg_weight, nullptr, g_u,
+                         g_i, stream);
+}
+
+extern "C" int chaorec_bpr_fwd_bwd_at_f32(const float *tab_u, const float *tab_i, const int64_t *edges, int64_t n_edges,
+                                          const int64_t *hist_rowptr, const int32_t *hist_col, int64_t num_user,
+                                          int32_t num_item, uint64_t seed, uint64_t step, const int64_t *step_dev,
+                                          const int64_t *in_users, const int64_t *in_pos, const int64_t *in_neg,
+                                          int32_t B, int32_t D, int32_t variant, float reg_weight, int64_t *out_users,
+                                          int64_t *out_pos, int64_t *out_neg, float *coef, float *workspace,
+                                          const int64_t *perm, const int64_t *perm_pos, int64_t pos_offset, float *g_u,
+                                          float *g_i, int32_t *adam_step, float beta1, float beta2, float *adam_bc,
+                                          uint32_t *row_bits, int64_t bits_item_offset, void *stream) {
+  return bpr_fwd_bwd(tab_u, tab_i, nullptr, edges, n_edges, hist_rowptr, hist_col, num_user, num_item, seed, step, step_dev,
+                     in_users, in_pos, in_neg, B, D, variant, reg_weight, out_users, out_pos, out_neg, coef, workspace, perm,
+                     perm_pos, pos_offset, g_u, g_i, adam_step, beta1, beta2, adam_bc, row_bits, bits_item_offset, stream);
+}
+
+extern "C" int chaorec_bpr_fwd_bwd_layers_f32(const float *const *tabs, int32_t n_tabs, float w, int64_t item_offset, float *rows,
+                                              const int64_t *edges, int64_t n_edges, const int64_t *hist_rowptr,
+                                              const int32_t *hist_col, int64_t num_user, int32_t num_item, uint64_t seed,
+                                              uint64_t step, const int64_t *step_dev, const int64_t *in_users,
+                                              const int64_t *in_pos, const int64_t *in_neg, int32_t B, int32_t D, int32_t variant,
+                                              float reg_weight, int64_t *out_users, int64_t *out_pos, int64_t *out_neg,
+                                              float *coef, float *workspace, const int64_t *perm, const int64_t *perm_pos,
+                                              int64_t pos_offset, float *g_u, float *g_i, int32_t *adam_step, float beta1,
+                                              float beta2, float *adam_bc, uint32_t *row_bits, int64_t bits_item_offset,
+                                              void *stream) {
+  if (!tabs || n_tabs < 1 || n_tabs > kMeanMaxTabs)
+    return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd_layers: %d layer tables (1 .. %d)", n_tabs, kMeanMaxTabs);
+  if (!rows || item_offset < 0) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd_layers: NULL rows buffer or a negative item offset");
+  if (D > 64 * kMeanMaxQ) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd_layers: D=%d > %d not built", D, 64 * kMeanMaxQ);
+  MeanSrc M;
+  for (int k = 0; k < kMeanMaxTabs; ++k) {
+    M.t[k] = k < n_tabs ? tabs[k] : nullptr;
+    if (k < n_tabs && !tabs[k]) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd_layers: NULL table %d", k);
+  }
+  M.n = n_tabs, M.w = w, M.item_offset = item_offset, M.rows = rows;
+  return bpr_fwd_bwd(nullptr, nullptr, &M, edges, n_edges, hist_rowptr, hist_col, num_user, num_item, seed, step, step_dev,
+                     in_users, in_pos, in_neg, B, D, variant, reg_weight, out_users, out_pos, out_neg, coef, workspace, perm,
+                     perm_pos, pos_offset, g_u, g_i, adam_step, beta1, beta2, adam_bc, row_bits, bits_item_offset, stream);
 }
 
 extern "C" int chaorec_bpr_finalize_steps_f32(const float *workspace, int64_t ws_stride, int32_t n_steps, int32_t B,
@@ -884,20 +1007,29 @@ extern "C" int chaorec_bpr_bwd_ordered_f32(const float *tab_u, const float *tab_
                                            const int64_t *pos, const int64_t *neg, int32_t B, int32_t D,
                                            const float *coef, float reg_weight, const float *grad_out,
                                            float *g_u, float *g_i, void *stream) {
-  if (!tab_u || !tab_i || !users || !pos || !neg || !coef || !g_u || !g_i)
+  return bpr_bwd_ordered(tab_u, tab_i, nullptr, users, pos, neg, B, D, coef, reg_weight, grad_out, g_u, g_i, stream);
+}
+
+// (rows: NULL = the table rows users[b] / pos[b] / neg[b] of tab_u / tab_i; else MeanSrc::rows, the tables unused)
+static int bpr_bwd_ordered(const float *tab_u, const float *tab_i, const float *rows, const int64_t *users, const int64_t *pos,
+                           const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight, const float *grad_out,
+                           float *g_u, float *g_i, void *stream) {
+  if ((!rows && (!tab_u || !tab_i)) || !users || !pos || !neg || !coef || !g_u || !g_i)
     return fail(CHAOREC_E_INVALID, "bpr_bwd_ordered: NULL argument");
   if (B <= 0 || D <= 0) return fail(CHAOREC_E_INVALID, "bpr_bwd_ordered: B=%d D=%d", B, D);
   OrdArgs P;
   P.tab_u = tab_u, P.users = users, P.coef = coef, P.wvec = nullptr, P.grad_out = grad_out, P.g_u = g_u;
   P.r2_unit = 2.0f * reg_weight / ((float)B * (float)D);
-  P.B = B, P.D = D, P.T = 1, P.joined = 1;
+  P.B = B, P.D = D, P.T = 1, P.joined = 1, P.rows = rows;
   for (int k = 0; k < kBprMaxTerms; ++k) {
     P.A.tab_i[k] = tab_i, P.A.pos[k] = pos, P.A.neg[k] = neg, P.A.g_i[k] = g_i;
     P.A.scatter_rows[k] = nullptr, P.A.scatter_out[k] = nullptr;
   }
   P.A.T = 1;
-  if (!launch_bpr_ordered(P, 1, (hipStream_t)stream))     // (too many slots for the key table / D > 256: atomics)
+  if (!launch_bpr_ordered(P, 1, (hipStream_t)stream)) {   // (too many slots for the key table / D > 256: atomics)
+    if (rows) return fail(CHAOREC_E_INVALID, "bpr_bwd_ordered: a compact row source needs 3 B <= %d and D <= 256", kOrdMaxSlots);
     return chaorec_bpr_bwd_f32(tab_u, tab_i, users, pos, neg, B, D, coef, reg_weight, grad_out, g_u, g_i, stream);
+  }
   return check_launch("bpr_bwd_ordered_kernel");
 }
 
@@ -980,7 +1112,7 @@ extern "C" int chaorec_bpr_multi_bwd_ordered_f32(const float *tab_u, const int64
   }
   P.tab_u = tab_u, P.users = users, P.coef = coef, P.wvec = wvec, P.grad_out = grad_out, P.g_u = g_u;
   P.r2_unit = 0.f;
-  P.B = B, P.D = D, P.T = T, P.joined = 0;
+  P.B = B, P.D = D, P.T = T, P.joined = 0, P.rows = nullptr;
   if (!launch_bpr_ordered(P, 1 + 2 * T, (hipStream_t)stream))
     return chaorec_bpr_multi_bwd_f32(tab_u, users, T, tabs, pos, neg, B, D, coef, wvec, grad_out, g_u, g_i, scatter_rows,
                                      scatter_out, stream);

@@ -41,6 +41,12 @@ constexpr int kDescDwords = 16;  // 64-B descriptor: row, deg|flag, e0 lo/hi, 6 
 #ifndef CHAOREC_SPMM_MINW
 #define CHAOREC_SPMM_MINW 1
 #endif
+// The ticket of a gated Adam launch (AdamEpi): 0 = relaxed atomics -- nothing is PUBLISHED through the ticket, it only counts
+// workgroups whose bitmap loads have returned --, 1 = acquire-release ones at agent scope, which on this chip write back and
+// invalidate an L2 per workgroup (profiles/gated_z_sports_step.json has both).
+#ifndef CHAOREC_SPMM_TICKET_ACQ_REL
+#define CHAOREC_SPMM_TICKET_ACQ_REL 0
+#endif
 // The GATED instantiations at D >= 128 (SP, the backward launches of a light step over a large graph) trade gathers in flight
 // per wave for WAVES in flight: 4 instead of 8 source rows per group and step, a quarter of the long-row tile, and a register
 // budget of SEVEN waves per SIMD instead of the four the compiler settles at when left alone (126 VGPRs; 72 with two spilled).
@@ -76,6 +82,19 @@ constexpr int spmm_min_waves() { return spmm_hi_occ<LPR, SP>() ? CHAOREC_SPMM_SP
 // step.  `bc` holds the step's two bias corrections (device memory: the step counter lives there too).  clear_z:
 // rows of z that were non-zero are zeroed after use (z = the batch gradient G, kept all-zero between steps
 // instead of being zero-filled every step; only legal when this launch does not GATHER from z).
+// With RowSparse::z_bits the Adam instantiation reads z through that bitmap like the SP ones (a row whose bit is clear is
+// not loaded: +0, so beta * (+0) is added as before and clear_z has nothing to zero there).  The same launch is the one that
+// CLEARS the step's bitmaps, z's among them: with a gate the clear moves from kernel entry to the launch's last act --
+// RowSparse::ticket, device counters (zero between launches): every workgroup takes a ticket when its rows are stored, the
+// one that draws the last ticket knows every other's bitmap reads are done, clears and leaves the counters at zero.  Returning
+// atomics on ONE address are served one after the other (~27 ns each, see expand_row_bits_kernel: 2 760 workgroups of a sports
+// launch would take three times the launch), so the ticket has two levels: workgroup i counts on sub-counter i % kTicketFan
+// (a 128-byte line each), the last arrival of a sub-counter counts on the top one (word 0).  Why no fence: a wave's bitmap
+// words are in its registers before it stores its row (they decided what it loaded), the workgroup barrier comes after every
+// wave's stores were issued, the ticket after the barrier, the clear after the last ticket -- a store cannot change a load that
+// has returned, and no workgroup reads anything another one wrote.
+constexpr unsigned kTicketFan = 64;
+static_assert(CHAOREC_SPMM_TICKET_WORDS == (kTicketFan + 1) * 32, "include/chaorec_hip.h: CHAOREC_SPMM_TICKET_WORDS");
 struct AdamEpi {
   float *p, *m, *v;
   const float *bc;
@@ -104,10 +123,13 @@ struct RowSparse {
   int write_zeros;
   uint32_t *clear[2];
   int64_t n_clear[2];
+  uint32_t *ticket;     // ADAM with z_bits: see AdamEpi
 };
 __device__ __forceinline__ bool row_bit(const uint32_t *bits, int64_t r) { return (bits[r >> 5] >> (r & 31)) & 1u; }
 
-template <int LPR, int CPL, bool ADAM, bool SP = false>
+// (ZG: the ADAM instantiation that reads z through its bitmap and clears by ticket -- one of its own, so that the ungated
+//  Adam launch keeps its code: with the gate as a kernel-uniform branch that launch ran 0.4 us slower on sports)
+template <int LPR, int CPL, bool ADAM, bool SP = false, bool ZG = false>
 __global__ __launch_bounds__(256, (spmm_min_waves<LPR, SP>())) void spmm_csr_ordered_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, float *__restrict__ y,
@@ -115,7 +137,7 @@ __global__ __launch_bounds__(256, (spmm_min_waves<LPR, SP>())) void spmm_csr_ord
     float *acc, const float *__restrict__ acc_init, float acc_w,
     const int32_t *__restrict__ sched, int64_t n_groups, int dyn_val, const AdamEpi ae,
     const float *__restrict__ mean_t1, const float *__restrict__ mean_t2, const RowSparse sa) {
-  if (sa.clear[0] || sa.clear[1]) {        // (kernel-uniform; two short bitmaps: a few words per thread at most)
+  if (!ZG && (sa.clear[0] || sa.clear[1])) {   // (kernel-uniform; two short bitmaps: a few words per thread at most)
     const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (int64_t)gridDim.x * blockDim.x;
 #pragma unroll
     for (int w = 0; w < 2; ++w)
@@ -211,7 +233,7 @@ __global__ __launch_bounds__(256, (spmm_min_waves<LPR, SP>())) void spmm_csr_ord
   float4 *acc4 = reinterpret_cast<float4 *>(acc);
   bool zflag = true;            // SP: is this row of z worth reading?
   bool any_src = !SP;           // SP: did this row gather anything (group-uniform)?
-  if constexpr (SP) {
+  if constexpr (SP || ZG) {
     if (z && sa.z_bits && row_ok) zflag = row_bit(sa.z_bits, r);
   }
   float4 zpre[CPL], apre[CPL];
@@ -590,7 +612,10 @@ __global__ __launch_bounds__(256, (spmm_min_waves<LPR, SP>())) void spmm_csr_ord
     }
   }
 
-  if (!row_ok) return;
+  if constexpr (!ZG) {
+    if (!row_ok) return;
+  }
+  if (row_ok) {       // (ZG: the surplus waves of the last block stay for the ticket below)
   if constexpr (SP) {
     if (sa.out_bits && li == 0 && (any_src || (z && zflag))) atomicOr(sa.out_bits + (r >> 5), 1u << (r & 31));
   }
@@ -629,6 +654,33 @@ __global__ __launch_bounds__(256, (spmm_min_waves<LPR, SP>())) void spmm_csr_ord
         reinterpret_cast<float4 *>(const_cast<float *>(z))[o] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
+  }
+  if constexpr (ZG) {
+    {                             // the clear a gated launch could not do at entry: by the last workgroup
+      __shared__ int last_s;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        constexpr int order = CHAOREC_SPMM_TICKET_ACQ_REL ? __ATOMIC_ACQ_REL : __ATOMIC_RELAXED;
+        const unsigned fan = gridDim.x < kTicketFan ? gridDim.x : kTicketFan, s = blockIdx.x % fan;
+        const unsigned mine = (gridDim.x - s + fan - 1u) / fan;     // workgroups that count on sub-counter s
+        uint32_t *sub = sa.ticket + 32u * (1u + s);
+        bool last = false;
+        if (__hip_atomic_fetch_add(sub, 1u, order, __HIP_MEMORY_SCOPE_AGENT) == mine - 1u) {
+          __hip_atomic_store(sub, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          last = __hip_atomic_fetch_add(sa.ticket, 1u, order, __HIP_MEMORY_SCOPE_AGENT) == fan - 1u;
+        }
+        last_s = last;
+      }
+      __syncthreads();
+      if (last_s) {
+#pragma unroll
+        for (int w = 0; w < 2; ++w)
+          if (sa.clear[w])
+            for (int64_t i = threadIdx.x; i < sa.n_clear[w]; i += blockDim.x) sa.clear[w][i] = 0u;
+        if (threadIdx.x == 0) *sa.ticket = 0u;
+      }
+    }
+  }
 }
 
 template <int LPR, int CPL>
@@ -648,10 +700,16 @@ static int launch_spmm(const int64_t *rowptr, const int32_t *col, const float *v
   if (mean_t2 && LPR > 16) return fail(CHAOREC_E_INVALID, "spmm: three mean terms need D <= 64");
   if (adam) {
     if constexpr (CPL == 1) {
-      if (sparse) return fail(CHAOREC_E_INVALID, "spmm+adam: no row-sparse form (bitmaps can only be cleared here)");
-      hipLaunchKernelGGL((spmm_csr_ordered_kernel<LPR, CPL, true>), dim3((unsigned)blocks), dim3(256), 0, st,
-                         rowptr, col, val, x, y, n_rows, D4, alpha, z, beta, acc, acc_init, acc_w, sched,
-                         waves, dyn_val, *adam, (const float *)nullptr, (const float *)nullptr, sa);
+      if (sa.src_bits || sa.out_bits || sa.row_bits)
+        return fail(CHAOREC_E_INVALID, "spmm+adam: only z is read through a bitmap (the others can only be cleared here)");
+      if (sa.z_bits)
+        hipLaunchKernelGGL((spmm_csr_ordered_kernel<LPR, CPL, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           rowptr, col, val, x, y, n_rows, D4, alpha, z, beta, acc, acc_init, acc_w, sched,
+                           waves, dyn_val, *adam, (const float *)nullptr, (const float *)nullptr, sa);
+      else
+        hipLaunchKernelGGL((spmm_csr_ordered_kernel<LPR, CPL, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+                           rowptr, col, val, x, y, n_rows, D4, alpha, z, beta, acc, acc_init, acc_w, sched,
+                           waves, dyn_val, *adam, (const float *)nullptr, (const float *)nullptr, sa);
     } else {
       return fail(CHAOREC_E_INVALID, "spmm+adam: D > 256 not built");
     }
@@ -750,13 +808,13 @@ extern "C" int chaorec_spmm_csr_mean_f32(const int64_t *rowptr, const int32_t *c
                        stream, nullptr, n_terms > 1 ? terms[1] : nullptr, n_terms > 2 ? terms[2] : nullptr);
 }
 
-extern "C" int chaorec_spmm_csr_adam_f32(const int64_t *rowptr, const int32_t *col, const float *val, const float *x,
-                                         float *grad_out, int64_t n_rows, int64_t n_cols, int32_t D, float alpha,
-                                         float *z, float beta, const int32_t *schedule, int32_t mode, float *param,
-                                         float *exp_avg, float *exp_avg_sq, const float *bias_corr, float lr,
-                                         float beta1, float beta2, float eps, float weight_decay, int32_t clear_z,
-                                         uint32_t *clear_bits_a, int64_t n_words_a, uint32_t *clear_bits_b, int64_t n_words_b,
-                                         void *stream) {
+// (both Adam exports: z_bits / ticket NULL = the ungated launch, bitmaps cleared at entry)
+static int spmm_adam(const int64_t *rowptr, const int32_t *col, const float *val, const float *x, float *grad_out,
+                     int64_t n_rows, int64_t n_cols, int32_t D, float alpha, float *z, float beta, const int32_t *schedule,
+                     int32_t mode, float *param, float *exp_avg, float *exp_avg_sq, const float *bias_corr, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, int32_t clear_z, uint32_t *clear_bits_a,
+                     int64_t n_words_a, uint32_t *clear_bits_b, int64_t n_words_b, const uint32_t *z_bits, uint32_t *ticket,
+                     void *stream) {
   if (!param || !exp_avg || !exp_avg_sq || !bias_corr) return fail(CHAOREC_E_INVALID, "spmm+adam: NULL argument");
   if (n_words_a < 0 || n_words_b < 0) return fail(CHAOREC_E_INVALID, "spmm+adam: negative bitmap length");
   if (D > 256) return fail(CHAOREC_E_INVALID, "spmm+adam: D=%d > 256 not built", D);
@@ -772,8 +830,39 @@ extern "C" int chaorec_spmm_csr_adam_f32(const int64_t *rowptr, const int32_t *c
   std::memset(&rs, 0, sizeof(rs));
   rs.clear[0] = clear_bits_a, rs.n_clear[0] = clear_bits_a ? n_words_a : 0;
   rs.clear[1] = clear_bits_b, rs.n_clear[1] = clear_bits_b ? n_words_b : 0;
+  rs.z_bits = z_bits;
+  rs.ticket = ticket;
   return spmm_dispatch(rowptr, col, val, x, grad_out, n_rows, n_cols, D, alpha, z, beta, nullptr, nullptr, 0.f, schedule,
                        mode, stream, &ae, nullptr, nullptr, &rs);
+}
+
+extern "C" int chaorec_spmm_csr_adam_f32(const int64_t *rowptr, const int32_t *col, const float *val, const float *x,
+                                         float *grad_out, int64_t n_rows, int64_t n_cols, int32_t D, float alpha,
+                                         float *z, float beta, const int32_t *schedule, int32_t mode, float *param,
+                                         float *exp_avg, float *exp_avg_sq, const float *bias_corr, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, int32_t clear_z,
+                                         uint32_t *clear_bits_a, int64_t n_words_a, uint32_t *clear_bits_b, int64_t n_words_b,
+                                         void *stream) {
+  return spmm_adam(rowptr, col, val, x, grad_out, n_rows, n_cols, D, alpha, z, beta, schedule, mode, param, exp_avg,
+                   exp_avg_sq, bias_corr, lr, beta1, beta2, eps, weight_decay, clear_z, clear_bits_a, n_words_a, clear_bits_b,
+                   n_words_b, nullptr, nullptr, stream);
+}
+
+extern "C" int chaorec_spmm_csr_adam_gated_f32(const int64_t *rowptr, const int32_t *col, const float *val, const float *x,
+                                               float *grad_out, int64_t n_rows, int64_t n_cols, int32_t D, float alpha,
+                                               float *z, float beta, const int32_t *schedule, int32_t mode, float *param,
+                                               float *exp_avg, float *exp_avg_sq, const float *bias_corr, float lr,
+                                               float beta1, float beta2, float eps, float weight_decay, int32_t clear_z,
+                                               uint32_t *clear_bits_a, int64_t n_words_a, uint32_t *clear_bits_b,
+                                               int64_t n_words_b, const uint32_t *z_bits, int64_t n_words_z,
+                                               uint32_t *ticket, int64_t n_words_ticket, void *stream) {
+  if (!z || !z_bits) return fail(CHAOREC_E_INVALID, "spmm+adam (gated): z and z_bits come together");
+  if (n_words_z < 0 || n_words_z * 32 < n_rows) return fail(CHAOREC_E_INVALID, "spmm+adam (gated): z_bits shorter than the rows");
+  if (!ticket || n_words_ticket < CHAOREC_SPMM_TICKET_WORDS)
+    return fail(CHAOREC_E_INVALID, "spmm+adam (gated): ticket of at least %d words", CHAOREC_SPMM_TICKET_WORDS);
+  return spmm_adam(rowptr, col, val, x, grad_out, n_rows, n_cols, D, alpha, z, beta, schedule, mode, param, exp_avg,
+                   exp_avg_sq, bias_corr, lr, beta1, beta2, eps, weight_decay, clear_z, clear_bits_a, n_words_a, clear_bits_b,
+                   n_words_b, z_bits, ticket, stream);
 }
 
 namespace chaorec {

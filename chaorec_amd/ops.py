@@ -305,10 +305,13 @@ def spmm_fewsrc_raw(csr, x, y, bits, alpha=1.0, z=None, beta=0.0, z_bits=None):
 
 
 def spmm_adam_raw(csr, x, param, exp_avg, exp_avg_sq, bias_corr, lr, betas, eps, weight_decay, alpha=1.0, z=None,
-                  beta=0.0, clear_z=False, grad_out=None, clear_bits=()):
+                  beta=0.0, clear_z=False, grad_out=None, clear_bits=(), z_bits=None, ticket=None):
     """g = alpha * (A x) [+ beta z] and the Adam update of `param` with that gradient, row by row, in ONE launch
     (chaorec_spmm_csr_adam_f32): the last backward propagate of a LightGCN step with optimizer.step() in its epilogue.
-    `bias_corr`: device float[2] written by bpr_finalize().  clear_z: zero the non-zero rows of z after use."""
+    `bias_corr`: device float[2] written by bpr_finalize().  clear_z: zero the non-zero rows of z after use.
+    z_bits (with `ticket`, spmm_adam_ticket(): zero between launches): z is read through that row bitmap
+    (chaorec_spmm_csr_adam_gated_f32) -- same results bit for bit, rows whose bit is clear are not touched; the bitmaps in
+    clear_bits (z_bits may be one of them) are then cleared by the launch's last workgroup instead of at its entry."""
     _need_cuda(csr.rowptr, x, z, param, exp_avg, exp_avg_sq, bias_corr, grad_out)
     x = _f32c(x)
     D = x.shape[1]
@@ -320,12 +323,24 @@ def spmm_adam_raw(csr, x, param, exp_avg, exp_avg_sq, bias_corr, lr, betas, eps,
     mode = 1 if getattr(csr, "dynamic_values", False) else 0
     cb = (list(clear_bits) + [None, None])[:2]         # row bitmaps this (the step's last) launch zeroes as a side job
     _need_cuda(*cb)
-    _lib.load().chaorec_spmm_csr_adam_f32(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(x), _ptr(grad_out),
-                                          csr.n_rows, csr.n_cols, D, alpha, _ptr(z), beta, _ptr(csr.schedule(D)),
-                                          mode, _ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(bias_corr),
-                                          lr, betas[0], betas[1], eps, weight_decay, int(bool(clear_z)),
-                                          _ptr(cb[0]), cb[0].numel() if cb[0] is not None else 0,
-                                          _ptr(cb[1]), cb[1].numel() if cb[1] is not None else 0, _stream())
+    args = (_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(x), _ptr(grad_out), csr.n_rows, csr.n_cols, D, alpha,
+            _ptr(z), beta, _ptr(csr.schedule(D)), mode, _ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(bias_corr),
+            lr, betas[0], betas[1], eps, weight_decay, int(bool(clear_z)),
+            _ptr(cb[0]), cb[0].numel() if cb[0] is not None else 0, _ptr(cb[1]), cb[1].numel() if cb[1] is not None else 0)
+    if z_bits is None and ticket is None:
+        _lib.load().chaorec_spmm_csr_adam_f32(*args, _stream())
+    else:
+        _need_cuda(z_bits, ticket)
+        _lib.load().chaorec_spmm_csr_adam_gated_f32(*args, _ptr(z_bits), z_bits.numel() if z_bits is not None else 0,
+                                                    _ptr(ticket), ticket.numel() if ticket is not None else 0, _stream())
+
+
+SPMM_TICKET_WORDS = 2080              # CHAOREC_SPMM_TICKET_WORDS (include/chaorec_hip.h)
+
+
+def spmm_adam_ticket(device):
+    """The all-zero counters a gated spmm_adam_raw launch counts its workgroups on (and leaves all-zero)."""
+    return torch.zeros(SPMM_TICKET_WORDS, dtype=torch.int32, device=device)
 
 
 class _SpMM(torch.autograd.Function):
@@ -690,7 +705,7 @@ def bpr_loss(tab_u, tab_i, users, pos, neg, variant, reg_weight=0.0, item_offset
 
 def bpr_fwd_bwd(tab, item_offset, grad, B, variant, reg_weight, coef, ws, ids, edges=None, hist=None, num_user=0,
                 num_item=0, seed=0, step=0, step_dev=None, perm=None, perm_pos=None, adam_step=None, betas=(0.9, 0.999),
-                adam_bc=None, pos_offset=0, row_bits=None, bits_item_offset=None):
+                adam_bc=None, pos_offset=0, row_bits=None, bits_item_offset=None, layer_tabs=None, layer_w=0.0, rows=None):
     """BPR(+L2) forward terms and backward row adds in one launch (chaorec_bpr_fwd_bwd_f32) over ONE [N, D] table
     (items from row item_offset on) and its gradient buffer `grad` (same shape, zero where no sample lands).
     edges given: the batch is drawn in the launch and written to ids = (users, pos, neg); else ids are the batch
@@ -699,20 +714,36 @@ def bpr_fwd_bwd(tab, item_offset, grad, B, variant, reg_weight, coef, ws, ids, e
     replay whose finalize runs once, after its last step: step = j, pos_offset = j * B).  row_bits (optional, ops.row_bitmap
     over the table's rows): the rows of `grad` the launch touched are flagged for the row-sparse backward propagates; item
     row i is bit bits_item_offset + i (default item_offset: one bitmap over the joined table; a word-aligned offset gives
-    the item rows a bitmap of their own)."""
-    _need_cuda(tab, grad, coef, ws, edges, step_dev, perm, perm_pos, adam_step, adam_bc, row_bits, *ids)
-    D = tab.shape[1]
+    the item rows a bitmap of their own).
+    layer_tabs (tab=None; with layer_w and `rows`, float32 [3 B, D]): the table is never formed -- the launch reads the batch's
+    rows of the [N, D] tables x_0 .. x_L and forms layer_w x_0 + layer_w x_1 + ... for them, with spmm_mean_raw's roundings
+    (chaorec_bpr_fwd_bwd_layers_f32); `rows` receives them, triple b's user / positive / negative at 3 b, 3 b + 1, 3 b + 2."""
+    _need_cuda(tab, grad, coef, ws, edges, step_dev, perm, perm_pos, adam_step, adam_bc, row_bits, rows, *ids)
+    D = grad.shape[1]
     off = item_offset * D * 4
-    ti, gi = ctypes.c_void_p(tab.data_ptr() + off), ctypes.c_void_p(grad.data_ptr() + off)
+    gi = ctypes.c_void_p(grad.data_ptr() + off)
     draw = edges is not None
     rowptr, col = hist if hist is not None else (None, None)
-    _lib.load().chaorec_bpr_fwd_bwd_at_f32(
-        _ptr(tab), ti, _ptr(edges), edges.shape[0] if draw else 0, _ptr(rowptr), _ptr(col), int(num_user), int(num_item),
-        int(seed) & (2**64 - 1), int(step), _ptr(step_dev), _ptr(None if draw else ids[0]), _ptr(None if draw else ids[1]),
-        _ptr(None if draw else ids[2]), int(B), D, int(variant), float(reg_weight), _ptr(ids[0] if draw else None),
-        _ptr(ids[1] if draw else None), _ptr(ids[2] if draw else None), _ptr(coef), _ptr(ws), _ptr(perm), _ptr(perm_pos),
-        int(pos_offset), _ptr(grad), gi, _ptr(adam_step), betas[0], betas[1], _ptr(adam_bc), _ptr(row_bits),
-        int(item_offset if bits_item_offset is None else bits_item_offset), _stream())
+    args = (_ptr(edges), edges.shape[0] if draw else 0, _ptr(rowptr), _ptr(col), int(num_user), int(num_item),
+            int(seed) & (2**64 - 1), int(step), _ptr(step_dev), _ptr(None if draw else ids[0]), _ptr(None if draw else ids[1]),
+            _ptr(None if draw else ids[2]), int(B), D, int(variant), float(reg_weight), _ptr(ids[0] if draw else None),
+            _ptr(ids[1] if draw else None), _ptr(ids[2] if draw else None), _ptr(coef), _ptr(ws), _ptr(perm), _ptr(perm_pos),
+            int(pos_offset), _ptr(grad), gi, _ptr(adam_step), betas[0], betas[1], _ptr(adam_bc), _ptr(row_bits),
+            int(item_offset if bits_item_offset is None else bits_item_offset), _stream())
+    if layer_tabs is None:
+        _lib.load().chaorec_bpr_fwd_bwd_at_f32(_ptr(tab), ctypes.c_void_p(tab.data_ptr() + off), *args)
+        return
+    if tab is not None:
+        raise ValueError("bpr_fwd_bwd: either one table or layer_tabs")
+    _need_cuda(*layer_tabs)
+    for t in layer_tabs:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != grad.shape:
+            raise TypeError("bpr_fwd_bwd: layer_tabs must be contiguous float32 tables of grad's shape")
+    if rows is not None and (rows.dtype != torch.float32 or not rows.is_contiguous() or rows.numel() < 3 * int(B) * D):
+        raise TypeError("bpr_fwd_bwd: rows must be a contiguous float32 buffer of 3 B rows")
+    ptrs = (ctypes.c_void_p * len(layer_tabs))(*[t.data_ptr() for t in layer_tabs])
+    _lib.load().chaorec_bpr_fwd_bwd_layers_f32(ctypes.cast(ptrs, ctypes.c_void_p), len(layer_tabs), float(layer_w),
+                                               int(item_offset), _ptr(rows), *args)
 
 
 def bpr_finalize(ws, B, D, reg_weight, out_loss, out_total=None, loss_accum=None, advance=None, perm_pos=None,

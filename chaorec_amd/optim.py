@@ -480,6 +480,26 @@ def _few_source_mode(n_rows, n_layers, D, batch_size, sparse_bwd):
     return bool(built and mode != "0" and (mode == "1" or 12 * batch_size <= n_rows))
 
 
+def _gated_z_mode(few_src, sparse_bwd):
+    """-> whether the Adam launch of a fused step reads G through R0's bitmap (ops.spmm_adam_raw with z_bits; G is zero
+    outside it by construction).  On with the row-sparse backward, i.e. by size: there G is a table far larger than the
+    caches and reading it is HBM time; on a cache-resident table (sports, the few-source backward) the skipped stream is
+    worth less than the launch's closing ticket costs.  CHAOREC_GATED_Z = auto / 0 / 1: by that rule / off / on wherever the
+    step keeps R0's bitmap.  (The middle backward launches read G densely: gated, they leave the Adam launch a cold G.)"""
+    mode = os.environ.get("CHAOREC_GATED_Z", "auto")
+    return bool((few_src or sparse_bwd) and mode != "0" and (mode == "1" or sparse_bwd))
+
+
+def _inner_mean_rows_mode(k, light, n_layers, D):
+    """-> whether the INNER steps (j < k - 1) of a k-step replay form the layer mean in their batch's rows only: the last
+    forward propagate is then a plain one and the BPR launch reads the L + 1 layer tables (ops.bpr_fwd_bwd with layer_tabs).
+    Nothing can see an inner step's `final` -- the next step of the same replay overwrites it before the graph returns --, so
+    this holds for every non-light step whose mean the last propagate's epilogue would form (n_layers <= the epilogue's
+    operand slots).  CHAOREC_INNER_MEAN_ROWS = auto / 0 / 1: by that rule / off / the same as auto."""
+    built = k > 1 and not light and 1 <= n_layers <= ops.mean_terms_limit(D)
+    return bool(built and os.environ.get("CHAOREC_INNER_MEAN_ROWS", "auto") != "0")
+
+
 class _FusedStep:
     """What FusedLightGCNStep and dist_lightgcn.FusedShardedLightGCNStep share around their launch sequences: the
     constructor checks, the moment views, state save / restore, the capture protocol and replay.  A subclass supplies
@@ -692,6 +712,11 @@ class FusedLightGCNStep(_FusedStep):
         self.few_src = _few_source_mode(N, L, D, self.B, self.sparse_bwd)
         self._few_bits = ops.row_bitmap(N, dev) if self.few_src else None     # R0: set by the BPR launch, cleared by Adam's
         self.bits = None
+        # The Adam launch can read G through R0's bitmap too (6 GB of zeros per step at 12 M rows and D = 128): see
+        # _gated_z_mode.  It both reads that bitmap and clears it -- by its last workgroup, counted in _ticket (zero between
+        # launches).
+        self.gate_z = _gated_z_mode(self.few_src, self.sparse_bwd)
+        self._ticket = ops.spmm_adam_ticket(dev) if self.gate_z else None
         if self.sparse_bwd:
             words = (N + 31) // 32 + 1
             self._bits_all = torch.zeros(2 * words + 2, dtype=torch.int32, device=dev)      # (+ the two row lists' lengths)
@@ -708,6 +733,9 @@ class FusedLightGCNStep(_FusedStep):
             k = self.steps_per_replay
             self.ws_steps = torch.empty((k, 4 * self.B), dtype=torch.float32, device=dev)
             self._fin_scratch = torch.zeros(2 * k + 1, dtype=torch.float32, device=dev)    # (+ the launch's ticket)
+        # (inner steps of a replay: see _inner_mean_rows_mode; _mean_rows holds the batch's 3 B rows of the mean)
+        self.inner_mean_rows = _inner_mean_rows_mode(self.steps_per_replay, self.light, L, D)
+        self._mean_rows = torch.empty((3 * self.B, D), dtype=torch.float32, device=dev) if self.inner_mean_rows else None
         if capture:
             model.graph.schedule(D)             # (lazily built by the first SpMM call: must exist before capture)
             self._capture(dev)
@@ -715,6 +743,7 @@ class FusedLightGCNStep(_FusedStep):
     def _state_tensors(self):
         counters = [t for t in (self.step_dev, self.perm_pos, self.loss_accum, self.optimizer._step_dev) if t is not None]
         scratch = [self.G] + ([self._bits_all] if self.sparse_bwd else []) + ([self._few_bits] if self.few_src else [])
+        scratch += [self._ticket] if self.gate_z else []
         return [self.model._flat, self.m, self.v] + counters, scratch
 
     @staticmethod
@@ -752,12 +781,21 @@ class FusedLightGCNStep(_FusedStep):
                             ws, self.ids, num_user=model.num_user, num_item=model.num_item, adam_step=opt._step_dev,
                             betas=group["betas"], adam_bc=self.bc)
         else:
-            ops.forward_layers(csr, x0, L, self.final, self.fbuf)
-            ops.bpr_fwd_bwd(self.final, model.num_user, self.G, B, ops.VARIANT_LOG_SIGMOID_EPS, model.reg_weight, self.coef,
-                            ws, self.ids, edges=self.edges, hist=model.hist if draw else None, num_user=model.num_user,
-                            num_item=model.num_item, seed=self.seed, step=j, step_dev=self.step_dev, perm=self.perm,
-                            perm_pos=self.perm_pos, adam_step=opt._step_dev, betas=group["betas"], adam_bc=self.bc,
-                            pos_offset=j * B, row_bits=r0_bits)
+            src = dict(tab=self.final)
+            if self.inner_mean_rows and j < k - 1:
+                # an inner step: x_L goes where the mean would (nothing reads `final` as a mean in such a step), the BPR
+                # launch forms the mean's rows it reads
+                xs = [x0]
+                for l in range(L):
+                    xs.append(ops.spmm_raw(csr, xs[-1], y=self.fbuf[l] if l < L - 1 else self.final))
+                src = dict(tab=None, layer_tabs=xs, layer_w=w, rows=self._mean_rows)
+            else:
+                ops.forward_layers(csr, x0, L, self.final, self.fbuf)
+            ops.bpr_fwd_bwd(src.pop("tab"), model.num_user, self.G, B, ops.VARIANT_LOG_SIGMOID_EPS, model.reg_weight,
+                            self.coef, ws, self.ids, edges=self.edges, hist=model.hist if draw else None,
+                            num_user=model.num_user, num_item=model.num_item, seed=self.seed, step=j, step_dev=self.step_dev,
+                            perm=self.perm, perm_pos=self.perm_pos, adam_step=opt._step_dev, betas=group["betas"],
+                            adam_bc=self.bc, pos_offset=j * B, row_bits=r0_bits, **src)
         book = dict(out_total=self.static_loss, loss_accum=self.loss_accum, advance=self.step_dev if draw else None,
                     perm_pos=self.perm_pos if (draw and self.perm is not None) else None)
         if k == 1:
@@ -785,7 +823,8 @@ class FusedLightGCNStep(_FusedStep):
             g, alpha = y, 1.0
         ops.spmm_adam_raw(csr, g, x0, self.m, self.v, self.bc, group["lr"], group["betas"], group["eps"],
                           group["weight_decay"], alpha=alpha, z=self.G, beta=w, clear_z=L >= 2,
-                          clear_bits=(self._bits_all,) if self.sparse_bwd else (self._few_bits,) if self.few_src else ())
+                          clear_bits=(self._bits_all,) if self.sparse_bwd else (self._few_bits,) if self.few_src else (),
+                          z_bits=r0_bits if self.gate_z else None, ticket=self._ticket)
         if L < 2:
             self.G.zero_()                      # (the single backward SpMM gathers from G: it cannot clear it)
         self._publish(not light)

@@ -130,6 +130,24 @@ int chaorec_spmm_csr_adam_f32(const int64_t *rowptr, const int32_t *col, const f
                               uint32_t *clear_bits_a, int64_t n_words_a, uint32_t *clear_bits_b, int64_t n_words_b,
                               void *stream);
 
+/* The same launch with z read THROUGH A BITMAP (z = the batch gradient G: 3 B non-zero rows out of N): a row of z whose bit
+ * in z_bits (n_words_z uint32 words, bit r & 31 of word r >> 5; a superset of z's non-zero rows) is clear is not loaded and
+ * counts as +0, so param / moments / grad_out are chaorec_spmm_csr_adam_f32's bit for bit; clear_z zeroes exactly the flagged
+ * rows that were non-zero, an unflagged row of z is neither read nor written.  z_bits may lie inside clear_bits_a / _b: a
+ * gated launch clears them as its LAST act instead of at entry -- every workgroup takes a ticket from `ticket`
+ * (CHAOREC_SPMM_TICKET_WORDS device uint32, zero on entry and zero again when the launch is done) after its rows are stored,
+ * the workgroup that draws the last one clears.  z, z_bits (at least n_rows bits) and ticket are all required:
+ * CHAOREC_E_INVALID otherwise. */
+#define CHAOREC_SPMM_TICKET_WORDS 2080
+int chaorec_spmm_csr_adam_gated_f32(const int64_t *rowptr, const int32_t *col, const float *val, const float *x,
+                                    float *grad_out, int64_t n_rows, int64_t n_cols, int32_t D, float alpha,
+                                    float *z, float beta, const int32_t *schedule, int32_t mode, float *param,
+                                    float *exp_avg, float *exp_avg_sq, const float *bias_corr, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int32_t clear_z,
+                                    uint32_t *clear_bits_a, int64_t n_words_a, uint32_t *clear_bits_b, int64_t n_words_b,
+                                    const uint32_t *z_bits, int64_t n_words_z, uint32_t *ticket, int64_t n_words_ticket,
+                                    void *stream);
+
 /* A backward propagate whose operands are ROW-SPARSE (train_and_evaluate.py:46 loss.backward() through
  * Model/LightGCN.py:81-83 for a BPR batch): the batch gradient G has 3 B non-zero rows out of N, the first backward
  * propagate's result is non-zero in their neighbours only.  Same arithmetic, entry order and result as
@@ -388,6 +406,26 @@ int chaorec_bpr_fwd_bwd_at_f32(const float *tab_u, const float *tab_i, const int
                                uint32_t *row_bits, int64_t bits_item_offset, void *stream);
 /* (row_bits, optional: bit u, bit bits_item_offset + pos, bit bits_item_offset + neg of every sample are set -- the
  *  rows of the gradient buffer the launch touched, for chaorec_spmm_csr_rowsparse_f32) */
+
+/* chaorec_bpr_fwd_bwd_at_f32 over a table that is never formed (an INNER step of a k-step replay: Model/LightGCN.py:95's
+ * layer mean is read in the batch's rows only, and the next step overwrites it before anything else could look):
+ *     tab[r] = w * tabs[0][r] + w * tabs[1][r] + ... + w * tabs[n_tabs - 1][r]
+ * for the 3 B rows of the batch, accumulated left to right with separately rounded multiplies and adds -- bit for bit the
+ * table chaorec_spmm_csr_mean_f32 writes when tabs[n_tabs - 1] is its propagate's result.  tabs: a HOST array of 1 .. 4 device
+ * tables, [N, D] each with the users first and item i at row item_offset + i; rows: device float [3 B, D], receives triple b's
+ * user / positive / negative row of the mean at 3 b, 3 b + 1, 3 b + 2 (the ordered gradient launch of
+ * CHAOREC_BPR_ORDERED=2 reads them there).  Everything else -- draw, terms, coefficient, gradient rows into g_u / g_i,
+ * counters, row_bits -- is the _at_ launch's. */
+int chaorec_bpr_fwd_bwd_layers_f32(const float *const *tabs, int32_t n_tabs, float w, int64_t item_offset, float *rows,
+                                   const int64_t *edges, int64_t n_edges, const int64_t *hist_rowptr,
+                                   const int32_t *hist_col, int64_t num_user, int32_t num_item, uint64_t seed,
+                                   uint64_t step, const int64_t *step_dev, const int64_t *in_users,
+                                   const int64_t *in_pos, const int64_t *in_neg, int32_t B, int32_t D, int32_t variant,
+                                   float reg_weight, int64_t *out_users, int64_t *out_pos, int64_t *out_neg,
+                                   float *coef, float *workspace, const int64_t *perm, const int64_t *perm_pos,
+                                   int64_t pos_offset, float *g_u, float *g_i, int32_t *adam_step, float beta1,
+                                   float beta2, float *adam_bc, uint32_t *row_bits, int64_t bits_item_offset,
+                                   void *stream);
 int chaorec_bpr_finalize_steps_f32(const float *workspace, int64_t ws_stride, int32_t n_steps, int32_t B,
                                    int32_t D, float reg_weight, float *out_loss, float *out_total,
                                    float *loss_accum, int64_t *advance, int64_t *perm_pos, float *scratch, void *stream);
