@@ -146,6 +146,16 @@ struct PrefArgs {
   int n_sample_tiles, sample_phase;
 };
 
+// The call's scalar block: kPfScalarBytes at the head of the region the pack launch clears (scalars | tau_sum | fb_done).
+// One device-side queue length each, at its byte position in the block, 32 bytes apart at the least:
+constexpr int kPfScalarBytes = 256;
+constexpr int kPfScalarReth = 32;     // reth_cnt: users queued for a raised threshold
+constexpr int kPfScalarRetry = 64;    // retry_cnt / retry_list_cnt: users pass A could not certify
+constexpr int kPfScalarRt2 = 96;      // rt2_cnt: users that got a raised threshold (pass C)
+constexpr int kPfScalarFb = 128;      // fb_cnt: users queued for the exact routes
+constexpr int kPfScalarWide = 192;    // wide_cnt: users with more candidates than the narrow selection holds
+static_assert(kPfScalarWide + (int)sizeof(int) <= kPfScalarBytes, "the last counter ends inside the block plan_score reserves");
+
 // ---- pack ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pack_items_bf16_kernel(const float *__restrict__ item_emb,
                                                               uint4 *__restrict__ packed, int64_t n_items, int D,

@@ -19,6 +19,7 @@
 #include "common.h"
 #include <limits.h>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 namespace chaorec {
@@ -838,6 +839,44 @@ struct ScorePlan {
 #ifndef CHAOREC_PF_UB128
 #define CHAOREC_PF_UB128 2
 #endif
+#ifndef CHAOREC_PF_RANK
+#define CHAOREC_PF_RANK 8
+#endif
+
+// ---- the prefilter's kernels by row width ------------------------------------------------------------------------
+// The prefilter's kernels exist for rows of 64 and of 128 floats.  with_pf_width() calls f with the width as a
+// compile-time constant (any width but 64 counts as 128: the plan also computes its prefilter numbers for widths that
+// never take the route); every launch and the occupancy query pick their instantiation below, nowhere else.
+template <class F>
+static auto with_pf_width(int D, F &&f) {
+  return D == 64 ? f(std::integral_constant<int, 64>{}) : f(std::integral_constant<int, 128>{});
+}
+template <int D>
+constexpr int pf_ub() { return D == 64 ? CHAOREC_PF_UB64 : CHAOREC_PF_UB128; }   // user blocks of 32 per sweep wave
+
+typedef void (*PrefKernel)(const PrefArgs);
+static PrefKernel sweep_kernel(int D, bool cls) {
+  return with_pf_width(D, [cls](auto w) -> PrefKernel {
+    constexpr int W = decltype(w)::value;
+    return cls ? score_sweep_bf16_kernel<W, pf_ub<W>(), true> : score_sweep_bf16_kernel<W, pf_ub<W>(), false>;
+  });
+}
+static PrefKernel select_kernel(int D, bool wide) {
+  return with_pf_width(D, [wide](auto w) -> PrefKernel {
+    constexpr int W = decltype(w)::value;
+    return wide ? score_select_kernel_pf<W, kPfMaxCandWide> : score_select_kernel_pf<W, kPfMaxCand>;
+  });
+}
+// (sorted table: its own sample table; long item ranges: the streaming top-r of four waves; else one wave's 24-slot lists)
+static PrefKernel sample_kernel(int D, bool cls, bool sample_long) {
+  return with_pf_width(D, [cls, sample_long](auto w) -> PrefKernel {
+    constexpr int W = decltype(w)::value;
+    if (cls) return score_sample_bf16_kernel<W, 32, true, 4, true>;
+    if (sample_long) return score_sample_bf16_kernel<W, 32, true, 4, false>;
+    return score_sample_bf16_kernel<W, 24, false, 1, false>;
+  });
+}
+
 // Workgroup slots of the sweep kernel THAT IS LAUNCHED on this device (workgroups per CU x CUs), queried once; without a
 // device (the CPU-side workspace query) the gfx950 defaults.
 static int sweep_wave_slots(int D, bool cls) {
@@ -847,12 +886,7 @@ static int sweep_wave_slots(int D, bool cls) {
   int per_cu = 0, cus = 0, dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) {
-    if (D == 64 && !cls) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, score_sweep_bf16_kernel<64, CHAOREC_PF_UB64, false>, 64 * kSweepWaves, 0);
-    else if (D == 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, score_sweep_bf16_kernel<64, CHAOREC_PF_UB64, true>, 64 * kSweepWaves, 0);
-    else if (!cls) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, score_sweep_bf16_kernel<128, CHAOREC_PF_UB128, false>, 64 * kSweepWaves, 0);
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, score_sweep_bf16_kernel<128, CHAOREC_PF_UB128, true>, 64 * kSweepWaves, 0);
-  }
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweep_kernel(D, cls), 64 * kSweepWaves, 0);
   if (e != hipSuccess || per_cu <= 0 || cus <= 0) {
     (void)hipGetLastError();
     return 1024;   // (4 workgroups x 256 CUs) not cached: a later call with a device asks again
@@ -901,9 +935,8 @@ static int recall_layout(const void *ws) {       // -1: unknown workspace
   return it == g_layout_cls.end() ? -1 : it->second;
 }
 
-// force_cls: -1 = decide (use_sorted_table), 0 / 1 = the layout a workspace already holds
-static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int force_cls = -1) {
-  ScorePlan p;
+// plan_score, step 1: the fp32 routes' splits and their sampled threshold
+static void plan_exact_routes(ScorePlan &p, int64_t n_users, int64_t n_items, int K, int D) {
   const int64_t n_tiles = (n_items + 31) / 32;
   const int64_t groups = (n_users + 31) / 32;
   int64_t s = (2048 + groups - 1) / groups;  // aim for >= 2 waves per SIMD over 256 CUs
@@ -936,9 +969,15 @@ static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int 
       p.splits = (int)((n_tiles + p.tiles_per_split - 1) / p.tiles_per_split);
     }
   }
+}
+
+// plan_score, step 2: the bf16 prefilter's parameters.  force_cls: see plan_score
+static void plan_prefilter(ScorePlan &p, int64_t n_users, int64_t n_items, int K, int D, int force_cls) {
+  const int64_t n_tiles = (n_items + 31) / 32;
+  const int64_t groups = (n_users + 31) / 32;
   // bf16 prefilter + exact re-score: D in {64, 128}, enough tiles for the sampler's statistics
   p.prefilter = (D == 64 || D == 128) && K <= 64 && n_tiles >= 128 && n_tiles <= (int64_t)65535 * kPfMaxSplits;
-  p.pf_ub = D == 64 ? CHAOREC_PF_UB64 : CHAOREC_PF_UB128;
+  p.pf_ub = with_pf_width(D, [](auto w) { return pf_ub<decltype(w)::value>(); });
   // very long item ranges: every 8th tile still samples >= 64 k items per user, and the sampler streams the packed
   // table once per 32 users
   p.pf_sample_stride = n_tiles > 32768 ? 16 : (n_tiles > 16384 ? 8 : 4);
@@ -968,11 +1007,22 @@ static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int 
     p.pf_splits = (int)sp;
   }
   p.pf_sample_splits = p.pf_sample_long ? 3 : 4;
-  #ifndef CHAOREC_PF_RANK
-#define CHAOREC_PF_RANK 8
-#endif
   p.pf_sample_rank = p.pf_sample_long ? (p.pf_sample_stride >= 16 ? 7 : (p.pf_sample_stride == 8 ? 10 : 14)) : CHAOREC_PF_RANK;
   if (p.pf_cls) p.pf_sample_rank = std::max(1, env_int("CHAOREC_PF_CLS_RANK", p.pf_sample_stride >= 32 ? 4 : (p.pf_sample_stride >= 16 ? 6 : 8)));
+  p.pf_sample_tiles = (n_tiles + p.pf_sample_stride - 1) / p.pf_sample_stride;
+  // The exact route costs a pass over the whole item table per user: from 128 k items on, a user whose lists overflowed
+  // (threshold too low) is first given a raised threshold and one more compact pass (pass C, score_rethreshold_kernel)
+  p.pf_reth = p.prefilter && n_items >= 131072;
+  // The per-user exact route streams the whole item table once per queued user (1 GB per user at 2 M x 128): past
+  // 128 k items the queued users are instead swept 32 at a time on the f32 MFMA pipe (the route-1 kernel over a
+  // compact user set), the item range cut into enough splits to fill the chip with 1..16 user groups
+  p.pf_group_fb = p.prefilter && n_items >= 131072;
+  p.pf_group_fb_splits = (int)std::min<int64_t>(256, std::max<int64_t>(1, n_tiles / 64));
+}
+
+// plan_score, step 3: the workspace's byte layout, every region 256-byte aligned (an unused one is empty)
+static void plan_layout(ScorePlan &p, int64_t n_users, int64_t n_items, int K, int D) {
+  const int64_t n_tiles = (n_items + 31) / 32;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
   p.off_pf_packed = take(p.prefilter ? (size_t)n_tiles * 64 * (size_t)(D / 16 + 1) * 16 : 0);
@@ -984,10 +1034,9 @@ static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int 
   p.off_pf_bhist = take(p.pf_cls ? (size_t)256 * p.pf_cls_blocks * 4 : 0);
   p.off_pf_bmax = take(p.pf_cls ? (size_t)p.pf_cls_blocks * 4 : 0);
   p.off_pf_segb = take(p.pf_cls ? (size_t)256 * 4 : 0);
-  p.pf_sample_tiles = (n_tiles + p.pf_sample_stride - 1) / p.pf_sample_stride;
   p.off_pf_spacked = take(p.pf_cls ? (size_t)p.pf_sample_tiles * 64 * (size_t)(D / 16) * 16 : 0);
   // scalars | tau_sum | fb_done sit back to back: cleared together by the pack launch
-  p.off_pf_scalars = take(p.prefilter ? 256 : 0);
+  p.off_pf_scalars = take(p.prefilter ? kPfScalarBytes : 0);
   p.off_pf_tau = take(p.prefilter ? (size_t)n_users * 4 : 0);
   p.off_pf_fbdone = take(p.prefilter ? (size_t)n_users * 4 : 0);
   p.pf_zero_bytes = o - p.off_pf_scalars;
@@ -995,17 +1044,9 @@ static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int 
   p.off_pf_wide = take(p.prefilter ? (size_t)n_users * 4 : 0);
   p.off_pf_ncand = take(p.prefilter ? (size_t)n_users * 4 : 0);
   p.off_pf_fb = take(p.prefilter ? (size_t)n_users * 4 : 0);
-  // The exact route costs a pass over the whole item table per user: from 128 k items on, a user whose lists overflowed
-  // (threshold too low) is first given a raised threshold and one more compact pass (pass C, score_rethreshold_kernel)
-  p.pf_reth = p.prefilter && n_items >= 131072;
   p.off_pf_reth = take(p.pf_reth ? (size_t)n_users * 4 : 0);
   p.off_pf_rt2 = take(p.pf_reth ? (size_t)n_users * 4 : 0);
   p.off_pf_fbpart = take(p.prefilter ? (size_t)n_users * kExSlices * kMaxK * 8 : 0);
-  // The per-user exact route streams the whole item table once per queued user (1 GB per user at 2 M x 128): past
-  // 128 k items the queued users are instead swept 32 at a time on the f32 MFMA pipe (the route-1 kernel over a
-  // compact user set), the item range cut into enough splits to fill the chip with 1..16 user groups
-  p.pf_group_fb = p.prefilter && n_items >= 131072;
-  p.pf_group_fb_splits = (int)std::min<int64_t>(256, std::max<int64_t>(1, n_tiles / 64));
   p.off_pf_fbgroup = take(p.pf_group_fb ? (size_t)p.pf_group_fb_splits * kPfFbGroupCap * (size_t)K * 8 : 0);
   p.off_pf_theta = take(p.prefilter ? (size_t)n_users * 4 : 0);
   // (sized for the most splits any device plan uses, so that the CPU-side query and the device plan agree)
@@ -1019,6 +1060,14 @@ static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int 
   p.off_cand = take(p.sample ? (size_t)p.splits * (size_t)n_users * 2 * kCandCap * 8 : 0);
   p.off_cnt = take(p.sample ? (size_t)p.splits * (size_t)n_users * 2 * 4 : 0);
   p.total = o;
+}
+
+// force_cls: -1 = decide (use_sorted_table), 0 / 1 = the layout a workspace already holds
+static ScorePlan plan_score(int64_t n_users, int64_t n_items, int K, int D, int force_cls = -1) {
+  ScorePlan p;
+  plan_exact_routes(p, n_users, n_items, K, D);
+  plan_prefilter(p, n_users, n_items, K, D, force_cls);
+  plan_layout(p, n_users, n_items, K, D);
   return p;
 }
 
@@ -1048,13 +1097,6 @@ static int dispatch_score(int D, const ScoreArgs &a, dim3 grid, hipStream_t st) 
 
 using namespace chaorec;
 
-extern "C" int chaorec_score_topk_f32(const float *user_emb, const float *item_emb, int64_t n_users,
-                                      int64_t n_items, int32_t D, const int64_t *hist_rowptr,
-                                      const int32_t *hist_col, float mask_value, int32_t K,
-                                      int64_t id_offset, int64_t *out_idx, float *out_val,
-                                      void *workspace, size_t workspace_bytes, int32_t precision,
-                                      void *stream);
-
 extern "C" size_t chaorec_score_topk_workspace_bytes(int64_t n_users, int64_t n_items, int32_t K, int32_t D) {
   if (n_users <= 0 || n_items <= 0 || K <= 0 || D <= 0) return 0;
   return plan_score(n_users, n_items, K, D).total;
@@ -1062,68 +1104,299 @@ extern "C" size_t chaorec_score_topk_workspace_bytes(int64_t n_users, int64_t n_
 
 extern "C" int chaorec_score_topk_stats(const void *workspace, int64_t n_users, int64_t n_items, int32_t K, int32_t D,
                                         uint64_t *out10, void *stream) {
-  uint64_t *out9 = out10;
-  if (!workspace || !out9) return fail(CHAOREC_E_INVALID, "score_topk_stats: NULL argument");
+  if (!workspace || !out10) return fail(CHAOREC_E_INVALID, "score_topk_stats: NULL argument");
   if (n_users <= 0 || n_items <= 0 || K <= 0 || D <= 0) return fail(CHAOREC_E_INVALID, "score_topk_stats: bad sizes");
   const ScorePlan p = plan_score(n_users, n_items, K, D, recall_layout(workspace));   // (the layout the last call left there)
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(out9, 0, 10 * sizeof(uint64_t), st) != hipSuccess) return fail(CHAOREC_E_LAUNCH, "stats: memset");
+  if (hipMemsetAsync(out10, 0, 10 * sizeof(uint64_t), st) != hipSuccess) return fail(CHAOREC_E_LAUNCH, "stats: memset");
   if (!p.prefilter) return CHAOREC_OK;   // all zeros: the call did not take the prefilter route
   const char *ws = (const char *)workspace;
   hipLaunchKernelGGL(score_prefilter_stats_kernel, dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, st,
                      (const int *)(ws + p.off_fail), (const int *)(ws + p.off_pf_cnt),
-                     (const int *)(ws + p.off_pf_ncand), n_users, p.pf_splits, (unsigned long long *)out9,
-                     p.pf_reth ? (const int *)(ws + p.off_pf_scalars + 96) : (const int *)nullptr);
+                     (const int *)(ws + p.off_pf_ncand), n_users, p.pf_splits, (unsigned long long *)out10,
+                     p.pf_reth ? (const int *)(ws + p.off_pf_scalars + kPfScalarRt2) : (const int *)nullptr);
   return check_launch("score_prefilter_stats_kernel");
 }
 
-static int score_topk_impl(const float *user_emb, const float *item_emb, int64_t n_users,
-                           int64_t n_items, int32_t D, const int64_t *hist_rowptr,
-                           const int32_t *hist_col, float mask_value, int32_t K,
-                           int64_t id_offset, int64_t *out_idx, float *out_val,
-                           void *workspace, size_t workspace_bytes, int32_t precision,
-                           const float *hint_in, float *hint_out, int32_t hint_rank, int32_t flags,
-                           int32_t *counters_out, void *stream) {
-  if (!user_emb || !item_emb || !out_idx || !out_val) return fail(CHAOREC_E_INVALID, "score_topk: NULL argument");
-  if (n_users < 0 || n_items <= 0) return fail(CHAOREC_E_INVALID, "score_topk: bad sizes");
-  if (K < 1 || K > kMaxK) return fail(CHAOREC_E_INVALID, "score_topk: K=%d must be in [1,%d]", K, kMaxK);
-  if (n_items < K) return fail(CHAOREC_E_INVALID, "score_topk: n_items=%lld < K=%d (torch.topk would raise)", (long long)n_items, K);
-  if (n_items > 0xFFFFFFF0ll) return fail(CHAOREC_E_INVALID, "score_topk: n_items too large");
-  if (precision < 0 || precision > 2) return fail(CHAOREC_E_INVALID, "score_topk: precision %d not built", precision);
-  if (hist_rowptr && !hist_col) return fail(CHAOREC_E_INVALID, "score_topk: hist_rowptr without hist_col");
-  if (!((D == 8 || D == 16 || D == 32 || D == 64 || D == 128) || (D > 128 && D % 64 == 0)))
-    return fail(CHAOREC_E_INVALID, "score_topk: D=%d not in {8,16,32,64,128} and not a multiple of 64 above 128", D);
-  if (n_users == 0) return CHAOREC_OK;
-  // a BACK-only call continues what a FRONT call began in this workspace: same layout, whatever the environment says now
-  const bool back_only = (flags & CHAOREC_SCORE_BACK) && !(flags & CHAOREC_SCORE_FRONT);
-  ScorePlan p = plan_score(n_users, n_items, K, D, back_only ? recall_layout(workspace) : -1);
-  if (!back_only && workspace) remember_layout(workspace, p.pf_cls);
-  if (precision == 1) p.sample = false;  // precision 1: single exact pass, no sampled threshold (A/B + tests)
-  if (precision != 0) p.prefilter = false;  // precision 2: fp32 sweep with sampled thresholds (the pre-bf16 path)
-  if (p.total > workspace_bytes || (p.total && !workspace))
-    return fail(CHAOREC_E_WORKSPACE, "score_topk: workspace %zu < %zu", workspace_bytes, p.total);
-  if (reinterpret_cast<uintptr_t>(workspace) & 255)
-    return fail(CHAOREC_E_INVALID, "score_topk: workspace must be 256-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  char *ws = (char *)workspace;
-  const int64_t n_tiles = (n_items + 31) / 32;
-  const unsigned groups = (unsigned)((n_users + 31) / 32);
+// ---- one ranking call ------------------------------------------------------------------------------------------------
+// The arguments of a ranking call as the exports received them (chaorec_score_topk_f32 / _hinted_f32, chaorec_hip.h)
+struct ScoreCall {
+  const float *user_emb, *item_emb;
+  int64_t n_users, n_items;
+  int32_t D;
+  const int64_t *hist_rowptr;
+  const int32_t *hist_col;
+  float mask_value;
+  int32_t K;
+  int64_t id_offset;
+  int64_t *out_idx;
+  float *out_val;
+  void *workspace;
+  size_t workspace_bytes;
+  int32_t precision;
+  const float *hint_in;
+  float *hint_out;
+  int32_t hint_rank, flags;
+  int32_t *counters_out;
+  hipStream_t stream;
+  char *ws() const { return (char *)workspace; }
+  int64_t n_tiles() const { return (n_items + 31) / 32; }
+  unsigned groups() const { return (unsigned)((n_users + 31) / 32); }   // user blocks of one wave
+};
 
+// ---- bf16 prefilter route ------------------------------------------------------------------------------------------
+static int *pf_scalar(const ScoreCall &c, const ScorePlan &p, int at) {   // a counter of the scalar block (kPfScalar*)
+  return (int *)(c.ws() + p.off_pf_scalars + at);
+}
+
+static PrefArgs pref_args(const ScoreCall &c, const ScorePlan &p) {
+  char *ws = c.ws();
+  PrefArgs P;
+  P.user_emb = c.user_emb;
+  P.item_emb = c.item_emb;
+  P.packed = (const uint4 *)(ws + p.off_pf_packed);
+  P.n_users = c.n_users;
+  P.n_items = c.n_items;
+  P.hist_rowptr = c.hist_rowptr;
+  P.hist_col = c.hist_col;
+  P.mask_value = c.mask_value;
+  P.K = c.K;
+  P.id_offset = c.id_offset;
+  P.item_norm = (float *)(ws + p.off_pf_inorm);
+  P.perm = p.pf_cls ? (const int32_t *)(ws + p.off_pf_perm) : nullptr;
+  P.inv = p.pf_cls ? (const int32_t *)(ws + p.off_pf_inv) : nullptr;
+  P.tile_bound = p.pf_cls ? (const float *)(ws + p.off_pf_tbound) : nullptr;
+  P.sample_packed = p.pf_cls ? (const uint4 *)(ws + p.off_pf_spacked) : nullptr;
+  P.n_sample_tiles = (int)p.pf_sample_tiles;
+  P.sample_phase = p.pf_sample_stride / 2;
+  P.retry_cnt = nullptr;
+  P.retry_list = (int *)(ws + p.off_pf_retry);
+  P.wide_cnt = nullptr;
+  P.wide_list = (int *)(ws + p.off_pf_wide);
+  P.n_cand = (int *)(ws + p.off_pf_ncand);
+  P.fb_cnt = pf_scalar(c, p, kPfScalarFb);
+  P.fb_list = (int *)(ws + p.off_pf_fb);
+  P.fb_done = (int *)(ws + p.off_pf_fbdone);
+  P.fb_partial = (uint64_t *)(ws + p.off_pf_fbpart);
+  P.fb_skip = 0;
+  P.tau_sum = (float *)(ws + p.off_pf_tau);
+  P.theta = (float *)(ws + p.off_pf_theta);
+  P.cand = (uint32_t *)(ws + p.off_pf_cand);
+  P.cand_cnt = (int *)(ws + p.off_pf_cnt);
+  P.splits = p.pf_splits;
+  P.xcd_group = env_int("CHAOREC_SWEEP_XCD", 1);
+  P.sample_stride = p.pf_sample_stride;
+  P.sample_splits = p.pf_sample_splits;
+  P.sample_rank = p.pf_sample_rank;
+  P.out_idx = c.out_idx;
+  P.out_val = c.out_val;
+  P.user_map = nullptr;
+  P.n_active = nullptr;
+  P.min_active = 0;
+  P.small_retry = -1;
+  P.retry_list_cnt = pf_scalar(c, p, kPfScalarRetry);
+  P.counters_out = c.counters_out;
+  P.hint_in = nullptr;
+  P.hint_out = c.hint_out;
+  P.hint_rank = c.hint_rank > c.K ? (c.hint_rank > 128 ? 128 : c.hint_rank) : c.K;
+  P.fail = (int *)(ws + p.off_fail);
+  P.reth_cnt = nullptr;
+  P.reth_list = p.pf_reth ? (int *)(ws + p.off_pf_reth) : nullptr;
+  P.rt2_cnt = p.pf_reth ? pf_scalar(c, p, kPfScalarRt2) : nullptr;
+  P.rt2_list = p.pf_reth ? (int *)(ws + p.off_pf_rt2) : nullptr;
+  return P;
+}
+
+// The pack of the bf16 table, in the table's own order or norm-sorted; either launch also clears the call's counters
+static int pref_pack_front(const ScoreCall &c, const ScorePlan &p, const PrefArgs &P) {
+  char *ws = c.ws();
+  hipStream_t st = c.stream;
+  const int64_t n_tiles = c.n_tiles();
+  if (p.pf_cls) {
+    // norm classes -> stable counting sort -> the pack of the sorted table (which also clears the call's counters)
+    const int NB = p.pf_cls_blocks;
+    const int64_t n_pad = n_tiles * 32;
+    const int min_seg = (int)std::max<int64_t>(1, c.n_items / kClsSegments);
+    hipLaunchKernelGGL(score_norm_class_kernel, dim3((unsigned)NB), dim3(256), 0, st, c.item_emb, c.n_items, (int)c.D, n_pad,
+                       (uint8_t *)(ws + p.off_pf_key), (int *)(ws + p.off_pf_bhist), NB, (int *)(ws + p.off_pf_bmax));
+    // (runs a walk can afford: one per ~128 tiles of a workgroup's walk, score_class_scan_kernel)
+    const int max_runs = (int)std::min<int64_t>(kClsSegments, std::max<int64_t>(8, n_tiles / p.pf_splits / 128));
+    hipLaunchKernelGGL(score_class_scan_kernel, dim3(1), dim3(1024), 0, st, (int *)(ws + p.off_pf_bhist), NB,
+                       (const int *)(ws + p.off_pf_bmax), (float *)(ws + p.off_pf_segb), n_pad, min_seg, max_runs);
+    hipLaunchKernelGGL(score_class_scatter_kernel, dim3((unsigned)NB), dim3(64), 0, st, (const uint8_t *)(ws + p.off_pf_key),
+                       (const int *)(ws + p.off_pf_bhist), NB, n_pad, c.n_items, (int32_t *)(ws + p.off_pf_perm),
+                       (int32_t *)(ws + p.off_pf_inv), (const float *)(ws + p.off_pf_segb), (float *)(ws + p.off_pf_tbound));
+    const int64_t nfrag_s = (n_tiles + p.pf_sample_tiles) * (c.D / 16) * 64;
+    hipLaunchKernelGGL(pack_items_bf16_sorted_kernel, dim3((unsigned)((nfrag_s + 255) / 256)), dim3(256), 0, st, c.item_emb,
+                       (uint4 *)(ws + p.off_pf_packed), c.n_items, (int)c.D, n_tiles, P.perm,
+                       (uint4 *)(ws + p.off_pf_spacked), p.pf_sample_tiles, p.pf_sample_stride, P.sample_phase,
+                       (uint4 *)(ws + p.off_pf_scalars), (int64_t)(p.pf_zero_bytes / 16));
+    return check_launch("pack_items_bf16_sorted_kernel");
+  }
+  const int64_t nfrag = n_tiles * (c.D / 16) * 64;
+  hipLaunchKernelGGL(pack_items_bf16_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, st, c.item_emb,
+                     (uint4 *)(ws + p.off_pf_packed), c.n_items, (int)c.D, n_tiles, P.item_norm,
+                     (uint4 *)(ws + p.off_pf_scalars), (int64_t)(p.pf_zero_bytes / 16));
+  return check_launch("pack_items_bf16_kernel");
+}
+
+static void pref_sample(const ScoreCall &c, const ScorePlan &p, const PrefArgs &A) {
+  const bool four_waves = p.pf_cls || p.pf_sample_long;     // (four user blocks per workgroup, one wave each)
+  const dim3 grid(four_waves ? (c.groups() + 3) / 4 : c.groups(), (unsigned)p.pf_sample_splits);
+  hipLaunchKernelGGL(sample_kernel(c.D, p.pf_cls, p.pf_sample_long), grid, dim3(four_waves ? 256 : 64), 0, c.stream, A);
+}
+static void pref_sweep(const ScoreCall &c, const ScorePlan &p, const PrefArgs &A) {
+  const dim3 grid((unsigned)((c.groups() + p.pf_ub * kSweepWaves - 1) / (p.pf_ub * kSweepWaves)), (unsigned)p.pf_splits);
+  hipLaunchKernelGGL(sweep_kernel(c.D, p.pf_cls), grid, dim3(64 * kSweepWaves), 0, c.stream, A);
+}
+static void pref_select(const ScoreCall &c, const PrefArgs &A, unsigned grid, bool wide = false) {
+  hipLaunchKernelGGL(select_kernel(c.D, wide), dim3(grid), dim3(64), 0, c.stream, A);
+}
+// grids of the narrow selection: one wave per user ...
+static unsigned sel_all(const ScoreCall &c) {
+  return (unsigned)c.n_users;    // (a fixed grid walking the users is slower: 4 096 workgroups +10 %, 16 384 the same)
+}
+static unsigned sel_queue(const ScoreCall &c) {
+  return (unsigned)std::min<int64_t>(c.n_users, 8192);    // ... or a pass over a device-side queue
+}
+// a queue this short goes to the exact per-user route, not through another pass
+static int pref_small_queue(const ScorePlan &p) {
+  return p.pf_group_fb ? -1 : 16;        // (the exact route costs ~6 us per user, a retry pass ~120 us)   // (very long item ranges: the per-user exact route streams the table per user)
+}
+
+// pass A: the carried thresholds
+static void pref_pass_a(const ScoreCall &c, const ScorePlan &p, const PrefArgs &P, bool do_front, bool do_back) {
+  PrefArgs A = P;
+  A.hint_in = c.hint_in;
+  A.retry_cnt = pf_scalar(c, p, kPfScalarRetry);
+  if (do_front) pref_sweep(c, p, A);
+  if (do_back) pref_select(c, A, sel_all(c));
+}
+
+// pass C: lists that overflowed / more candidates than the wide selection holds = a threshold that was too low.
+// A raised one from the exact scores of the candidates the lists did keep, one more compact sweep, the wide
+// selection; what that cannot certify either goes to the exact routes
+static void pref_pass_c(const ScoreCall &c, const ScorePlan &p, const PrefArgs &P) {
+  PrefArgs R = P;
+  R.reth_cnt = pf_scalar(c, p, kPfScalarReth);
+  with_pf_width(c.D, [&](auto w) { hipLaunchKernelGGL(score_rethreshold_kernel<decltype(w)::value>, dim3(1024), dim3(64), 0, c.stream, R); });
+  PrefArgs C = P;
+  C.user_map = P.rt2_list;
+  C.n_active = P.rt2_cnt;
+  pref_sweep(c, p, C);
+  pref_select(c, C, 1024u, true);
+}
+
+// pass B: sampled thresholds; over the users pass A queued, or over everybody.  Then the wide selection, then pass C
+static void pref_pass_b(const ScoreCall &c, const ScorePlan &p, const PrefArgs &P, bool do_front, bool do_back) {
+  const bool queued = c.hint_in != nullptr;      // pass A went first: its front was the call's first whole sweep
+  int *reth_cnt = p.pf_reth ? pf_scalar(c, p, kPfScalarReth) : nullptr;
+  PrefArgs B = P;
+  if (queued) {
+    B.user_map = P.retry_list;
+    B.n_active = pf_scalar(c, p, kPfScalarRetry);
+    B.min_active = pref_small_queue(p);
+  }
+  B.wide_cnt = pf_scalar(c, p, kPfScalarWide);
+  B.reth_cnt = reth_cnt;
+  if (queued ? do_back : do_front) {
+    pref_sample(c, p, B);
+    pref_sweep(c, p, B);
+  }
+  if (!do_back) return;
+  pref_select(c, B, queued ? sel_queue(c) : sel_all(c));
+  // the users with more candidates than the narrow selection holds (coarse samples of very long item ranges)
+  PrefArgs W = P;
+  W.user_map = P.wide_list;
+  W.n_active = B.wide_cnt;
+  W.reth_cnt = reth_cnt;
+  // (coarse samples of very long item ranges put a large part of the users above the narrow selection's 512 candidates:
+  //  the wide selection is then a main pass, not a tail -- 256 one-wave workgroups took 106 ms per 1.1 M users at 2 M items)
+  const unsigned sel_wide = p.pf_sample_stride >= 8 ? sel_queue(c) : 256u;
+  pref_select(c, W, sel_wide, true);
+  if (p.pf_reth) pref_pass_c(c, p, P);
+}
+
+// The users no pass certified (list overflow, fewer than K above the threshold, band wider than the re-score slots) were
+// queued on the device.  `a`: the call's fp32 arguments (the grouped route runs the route-1 kernel)
+static int pref_exact_routes(const ScoreCall &c, const ScorePlan &p, PrefArgs P, const ScoreArgs &a) {
+  hipStream_t st = c.stream;
+  // Large item ranges: the first kPfFbGroupCap of them as a compact user set through the
+  // unthresholded f32 MFMA sweep (32 users share each pass over the items), results written to their own rows.
+  if (p.pf_group_fb) {
+    ScoreArgs f = a;
+    f.n_users = kPfFbGroupCap;
+    f.user_map = P.fb_list;
+    f.n_users_dev = P.fb_cnt;
+    f.splits = p.pf_group_fb_splits;
+    f.tiles_per_split = (c.n_tiles() + f.splits - 1) / f.splits;
+    f.partial = (uint64_t *)(c.ws() + p.off_pf_fbgroup);
+    int rc = dispatch_score(c.D, f, dim3(kPfFbGroupCap / 32, (unsigned)f.splits), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(score_topk_merge_kernel, dim3(kPfFbGroupCap), dim3(64), 0, st, f.partial,
+                       (int64_t)kPfFbGroupCap, c.K, f.splits, c.id_offset, c.out_idx, c.out_val, (const float *)nullptr,
+                       (int *)nullptr, (const int *)nullptr, (const int *)P.fb_list, (const int *)P.fb_cnt, c.hint_out);
+    rc = check_launch("score_topk_merge_kernel (grouped fallback)");
+    if (rc) return rc;
+    P.fb_skip = kPfFbGroupCap;
+  }
+  // ... and exact fp32 scores of all items for each remaining one, one block per (user, item slice)
+  // The queue is nearly always EMPTY (steady sports calls: no user at all) or a handful of users; the launch walks it
+  // with a grid stride, so the grid only bounds how many (user, slice) pairs run at once.  Short item ranges: 16 users
+  // x kExSlices -- 512 workgroups of 1024 threads (one per CU at a time: two dispatch rounds) cost 19 us on an empty
+  // queue, as much as ranking 3 users.  Long ranges keep the wide grid: their queue is what 512 grouped users left over.
+  const unsigned ex_grid = p.pf_group_fb ? (c.D == 64 ? 512u : 1024u) : 16u * kExSlices;
+  with_pf_width(c.D, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    hipLaunchKernelGGL(score_exact_user_kernel<W>, dim3(ex_grid), dim3(ex_threads<W>()), 0, st, P);
+  });
+  return check_launch("score_exact_user_kernel");
+}
+
+static int prefilter_route(const ScoreCall &c, const ScorePlan &p, const ScoreArgs &a, bool do_front, bool do_back) {
+  PrefArgs P = pref_args(c, p);
+  int rc;
+  if (do_front) {
+    rc = pref_pack_front(c, p, P);
+    if (rc) return rc;
+  }
+  // Pass A (carried thresholds) certifies nearly everybody in steady state.  What is left goes to pass B (sampled
+  // thresholds over the device-side queue) -- unless it is a handful: then the exact per-user route is cheaper than
+  // three more launches whose critical path is a whole item sweep by one wave, and pass B returns at once.  With
+  // CHAOREC_SCORE_LIGHT the caller (who has seen the previous call's queue lengths) asks for no pass B at all.
+  // Phases (CHAOREC_SCORE_FRONT / _BACK): the front is everything up to and including the call's FIRST whole sweep.
+  const bool light = c.hint_in && (c.flags & CHAOREC_SCORE_LIGHT) && !p.pf_group_fb;
+  if (c.hint_in) {
+    pref_pass_a(c, p, P, do_front, do_back);
+    P.small_retry = light ? INT_MAX : pref_small_queue(p);
+  }
+  if (!light) {
+    pref_pass_b(c, p, P, do_front, do_back);
+    P.wide_cnt = pf_scalar(c, p, kPfScalarWide);     // (for the counters the exact-route launch reports)
+  }
+  rc = check_launch("score prefilter kernels");
+  if (rc) return rc;
+  if (!do_back) return CHAOREC_OK;
+  return pref_exact_routes(c, p, P, a);
+}
+
+// ---- fp32 routes -----------------------------------------------------------------------------------------------------
+static ScoreArgs f32_args(const ScoreCall &c, const ScorePlan &p) {
   ScoreArgs a;
-  a.user_emb = user_emb;
-  a.item_emb = item_emb;
+  a.user_emb = c.user_emb;
+  a.item_emb = c.item_emb;
   a.packed = nullptr;
-  a.n_users = n_users;
-  a.n_items = n_items;
-  a.Dk = D;
-  a.hist_rowptr = hist_rowptr;
-  a.hist_col = hist_col;
-  a.mask_value = mask_value;
-  a.K = K;
-  a.id_offset = id_offset;
-  a.out_idx = out_idx;
-  a.out_val = out_val;
-  a.partial = p.splits > 1 ? (uint64_t *)(ws + p.off_partial) : nullptr;
+  a.n_users = c.n_users;
+  a.n_items = c.n_items;
+  a.Dk = c.D;
+  a.hist_rowptr = c.hist_rowptr;
+  a.hist_col = c.hist_col;
+  a.mask_value = c.mask_value;
+  a.K = c.K;
+  a.id_offset = c.id_offset;
+  a.out_idx = c.out_idx;
+  a.out_val = c.out_val;
+  a.partial = p.splits > 1 ? (uint64_t *)(c.ws() + p.off_partial) : nullptr;
   a.splits = p.splits;
   a.tiles_per_split = p.tiles_per_split;
   a.mode = kModeMain;
@@ -1134,313 +1407,148 @@ static int score_topk_impl(const float *user_emb, const float *item_emb, int64_t
   a.fail = nullptr;
   a.user_map = nullptr;
   a.n_users_dev = nullptr;
+  return a;
+}
 
-  int rc;
-  // phases of one call split over two calls (same arguments, same workspace; a caller that ranks several user ranges can
-  // run range k's back phase beside range k + 1's front phase on another stream): neither flag = the whole call
-  const bool do_front = !(flags & CHAOREC_SCORE_BACK) || (flags & CHAOREC_SCORE_FRONT);
-  const bool do_back = !(flags & CHAOREC_SCORE_FRONT) || (flags & CHAOREC_SCORE_BACK);
-  if (p.prefilter) {
-    PrefArgs P;
-    P.user_emb = user_emb;
-    P.item_emb = item_emb;
-    P.packed = (const uint4 *)(ws + p.off_pf_packed);
-    P.n_users = n_users;
-    P.n_items = n_items;
-    P.hist_rowptr = hist_rowptr;
-    P.hist_col = hist_col;
-    P.mask_value = mask_value;
-    P.K = K;
-    P.id_offset = id_offset;
-    P.item_norm = (float *)(ws + p.off_pf_inorm);
-    P.perm = p.pf_cls ? (const int32_t *)(ws + p.off_pf_perm) : nullptr;
-    P.inv = p.pf_cls ? (const int32_t *)(ws + p.off_pf_inv) : nullptr;
-    P.tile_bound = p.pf_cls ? (const float *)(ws + p.off_pf_tbound) : nullptr;
-    P.sample_packed = p.pf_cls ? (const uint4 *)(ws + p.off_pf_spacked) : nullptr;
-    P.n_sample_tiles = (int)p.pf_sample_tiles;
-    P.sample_phase = p.pf_sample_stride / 2;
-    P.retry_cnt = nullptr;
-    P.retry_list = (int *)(ws + p.off_pf_retry);
-    P.wide_cnt = nullptr;
-    P.wide_list = (int *)(ws + p.off_pf_wide);
-    P.n_cand = (int *)(ws + p.off_pf_ncand);
-    P.fb_cnt = (int *)(ws + p.off_pf_scalars + 128);
-    P.fb_list = (int *)(ws + p.off_pf_fb);
-    P.fb_done = (int *)(ws + p.off_pf_fbdone);
-    P.fb_partial = (uint64_t *)(ws + p.off_pf_fbpart);
-    P.tau_sum = (float *)(ws + p.off_pf_tau);
-    P.theta = (float *)(ws + p.off_pf_theta);
-    P.cand = (uint32_t *)(ws + p.off_pf_cand);
-    P.cand_cnt = (int *)(ws + p.off_pf_cnt);
-    P.splits = p.pf_splits;
-    P.xcd_group = env_int("CHAOREC_SWEEP_XCD", 1);
-    P.sample_stride = p.pf_sample_stride;
-    P.sample_splits = p.pf_sample_splits;
-    P.sample_rank = p.pf_sample_rank;
-    P.out_idx = out_idx;
-    P.out_val = out_val;
-    P.user_map = nullptr;
-    P.n_active = nullptr;
-    P.min_active = 0;
-    P.small_retry = -1;
-    P.retry_list_cnt = (const int *)(ws + p.off_pf_scalars + 64);
-    P.counters_out = counters_out;
-    P.hint_in = nullptr;
-    P.hint_out = hint_out;
-    P.hint_rank = hint_rank > K ? (hint_rank > 128 ? 128 : hint_rank) : K;
-    int *failf = (int *)(ws + p.off_fail);
-    P.fail = failf;
-    P.reth_cnt = nullptr;
-    P.reth_list = p.pf_reth ? (int *)(ws + p.off_pf_reth) : nullptr;
-    P.rt2_cnt = p.pf_reth ? (int *)(ws + p.off_pf_scalars + 96) : nullptr;
-    P.rt2_list = p.pf_reth ? (int *)(ws + p.off_pf_rt2) : nullptr;
-    int *reth_cnt = (int *)(ws + p.off_pf_scalars + 32);
-    int *retry_cnt = (int *)(ws + p.off_pf_scalars + 64);
-    const int64_t nfrag = n_tiles * (D / 16) * 64;
-    if (do_front && p.pf_cls) {
-      // norm classes -> stable counting sort -> the pack of the sorted table (which also clears the call's counters)
-      const int NB = p.pf_cls_blocks;
-      const int64_t n_pad = n_tiles * 32;
-      const int min_seg = (int)std::max<int64_t>(1, n_items / kClsSegments);
-      hipLaunchKernelGGL(score_norm_class_kernel, dim3((unsigned)NB), dim3(256), 0, st, item_emb, n_items, (int)D, n_pad,
-                         (uint8_t *)(ws + p.off_pf_key), (int *)(ws + p.off_pf_bhist), NB, (int *)(ws + p.off_pf_bmax));
-      // (runs a walk can afford: one per ~128 tiles of a workgroup's walk, score_class_scan_kernel)
-      const int max_runs = (int)std::min<int64_t>(kClsSegments, std::max<int64_t>(8, n_tiles / p.pf_splits / 128));
-      hipLaunchKernelGGL(score_class_scan_kernel, dim3(1), dim3(1024), 0, st, (int *)(ws + p.off_pf_bhist), NB,
-                         (const int *)(ws + p.off_pf_bmax), (float *)(ws + p.off_pf_segb), n_pad, min_seg, max_runs);
-      hipLaunchKernelGGL(score_class_scatter_kernel, dim3((unsigned)NB), dim3(64), 0, st, (const uint8_t *)(ws + p.off_pf_key),
-                         (const int *)(ws + p.off_pf_bhist), NB, n_pad, n_items, (int32_t *)(ws + p.off_pf_perm),
-                         (int32_t *)(ws + p.off_pf_inv), (const float *)(ws + p.off_pf_segb), (float *)(ws + p.off_pf_tbound));
-      const int64_t nfrag_s = (n_tiles + p.pf_sample_tiles) * (D / 16) * 64;
-      hipLaunchKernelGGL(pack_items_bf16_sorted_kernel, dim3((unsigned)((nfrag_s + 255) / 256)), dim3(256), 0, st, item_emb,
-                         (uint4 *)(ws + p.off_pf_packed), n_items, (int)D, n_tiles, P.perm,
-                         (uint4 *)(ws + p.off_pf_spacked), p.pf_sample_tiles, p.pf_sample_stride, P.sample_phase,
-                         (uint4 *)(ws + p.off_pf_scalars), (int64_t)(p.pf_zero_bytes / 16));
-      rc = check_launch("pack_items_bf16_sorted_kernel");
-      if (rc) return rc;
-    } else if (do_front) {
-      hipLaunchKernelGGL(pack_items_bf16_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, st, item_emb,
-                         (uint4 *)(ws + p.off_pf_packed), n_items, (int)D, n_tiles, P.item_norm,
-                         (uint4 *)(ws + p.off_pf_scalars), (int64_t)(p.pf_zero_bytes / 16));
-      rc = check_launch("pack_items_bf16_kernel");
-      if (rc) return rc;
-    }
-    const dim3 gs(groups, (unsigned)p.pf_sample_splits);
-    const dim3 gs4((groups + 3) / 4, (unsigned)p.pf_sample_splits);
-    const dim3 gw((unsigned)((groups + p.pf_ub * kSweepWaves - 1) / (p.pf_ub * kSweepWaves)), (unsigned)p.pf_splits);
-    const unsigned sel_all = (unsigned)n_users;    // (a fixed grid walking the users is slower: 4 096 workgroups +10 %, 16 384 the same)
-    const unsigned sel_queue = (unsigned)std::min<int64_t>(n_users, 8192);    // a pass over a device-side queue
-    // (coarse samples of very long item ranges put a large part of the users above the narrow selection's 512 candidates:
-    //  the wide selection is then a main pass, not a tail -- 256 one-wave workgroups took 106 ms per 1.1 M users at 2 M items)
-    const unsigned sel_wide = p.pf_sample_stride >= 8 ? sel_queue : 256u;
-    auto sweep = [&](const PrefArgs &A) {
-      if (p.pf_cls) {
-        if (D == 64) hipLaunchKernelGGL((score_sweep_bf16_kernel<64, CHAOREC_PF_UB64, true>), gw, dim3(64 * kSweepWaves), 0, st, A);
-        else hipLaunchKernelGGL((score_sweep_bf16_kernel<128, CHAOREC_PF_UB128, true>), gw, dim3(64 * kSweepWaves), 0, st, A);
-      } else {
-        if (D == 64) hipLaunchKernelGGL((score_sweep_bf16_kernel<64, CHAOREC_PF_UB64, false>), gw, dim3(64 * kSweepWaves), 0, st, A);
-        else hipLaunchKernelGGL((score_sweep_bf16_kernel<128, CHAOREC_PF_UB128, false>), gw, dim3(64 * kSweepWaves), 0, st, A);
-      }
-    };
-    auto select = [&](const PrefArgs &A, unsigned grid) {
-      if (D == 64) hipLaunchKernelGGL((score_select_kernel_pf<64, kPfMaxCand>), dim3(grid), dim3(64), 0, st, A);
-      else hipLaunchKernelGGL((score_select_kernel_pf<128, kPfMaxCand>), dim3(grid), dim3(64), 0, st, A);
-    };
-    auto select_wide = [&](const PrefArgs &A, unsigned grid) {
-      if (D == 64) hipLaunchKernelGGL((score_select_kernel_pf<64, kPfMaxCandWide>), dim3(grid), dim3(64), 0, st, A);
-      else hipLaunchKernelGGL((score_select_kernel_pf<128, kPfMaxCandWide>), dim3(grid), dim3(64), 0, st, A);
-    };
-    auto sample = [&](const PrefArgs &A) {
-      if (D == 64) {
-        if (p.pf_cls) hipLaunchKernelGGL((score_sample_bf16_kernel<64, 32, true, 4, true>), gs4, dim3(256), 0, st, A);
-        else if (p.pf_sample_long) hipLaunchKernelGGL((score_sample_bf16_kernel<64, 32, true, 4, false>), gs4, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((score_sample_bf16_kernel<64, 24, false, 1, false>), gs, dim3(64), 0, st, A);
-      } else {
-        if (p.pf_cls) hipLaunchKernelGGL((score_sample_bf16_kernel<128, 32, true, 4, true>), gs4, dim3(256), 0, st, A);
-        else if (p.pf_sample_long) hipLaunchKernelGGL((score_sample_bf16_kernel<128, 32, true, 4, false>), gs4, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((score_sample_bf16_kernel<128, 24, false, 1, false>), gs, dim3(64), 0, st, A);
-      }
-    };
-    // Pass A (carried thresholds) certifies nearly everybody in steady state.  What is left goes to pass B (sampled
-    // thresholds over the device-side queue) -- unless it is a handful: then the exact per-user route is cheaper than
-    // three more launches whose critical path is a whole item sweep by one wave, and pass B returns at once.  With
-    // CHAOREC_SCORE_LIGHT the caller (who has seen the previous call's queue lengths) asks for no pass B at all.
-    // Phases (CHAOREC_SCORE_FRONT / _BACK): the front is everything up to and including the call's FIRST whole sweep.
-    const bool light = hint_in && (flags & CHAOREC_SCORE_LIGHT) && !p.pf_group_fb;
-    const int small_queue = p.pf_group_fb ? -1 : 16;        // (the exact route costs ~6 us per user, a retry pass ~120 us)   // (very long item ranges: the per-user exact route streams the table per user)
-    int *wide_cnt = (int *)(ws + p.off_pf_scalars + 192);
-    if (hint_in) {
-      PrefArgs A = P;            // pass A: the carried thresholds
-      A.hint_in = hint_in;
-      A.retry_cnt = retry_cnt;
-      if (do_front) sweep(A);
-      if (do_back) select(A, sel_all);
-      P.small_retry = light ? INT_MAX : small_queue;
-    }
-    if (!light) {
-      PrefArgs B = P;            // pass B: sampled thresholds; over the users pass A queued, or over everybody
-      if (hint_in) {
-        B.user_map = P.retry_list;
-        B.n_active = retry_cnt;
-        B.min_active = small_queue;
-      }
-      B.wide_cnt = wide_cnt;
-      if (p.pf_reth) B.reth_cnt = reth_cnt;
-      if (hint_in ? do_back : do_front) {
-        sample(B);
-        sweep(B);
-      }
-      if (do_back) {
-        select(B, hint_in ? sel_queue : sel_all);
-        // the users with more candidates than the narrow selection holds (coarse samples of very long item ranges)
-        PrefArgs W = P;
-        W.user_map = P.wide_list;
-        W.n_active = wide_cnt;
-        if (p.pf_reth) W.reth_cnt = reth_cnt;
-        select_wide(W, sel_wide);
-        if (p.pf_reth) {
-          // pass C: lists that overflowed / more candidates than the wide selection holds = a threshold that was too low.
-          // A raised one from the exact scores of the candidates the lists did keep, one more compact sweep, the wide
-          // selection; what that cannot certify either goes to the exact routes below
-          PrefArgs R = P;
-          R.reth_cnt = reth_cnt;
-          if (D == 64) hipLaunchKernelGGL(score_rethreshold_kernel<64>, dim3(1024), dim3(64), 0, st, R);
-          else hipLaunchKernelGGL(score_rethreshold_kernel<128>, dim3(1024), dim3(64), 0, st, R);
-          PrefArgs C = P;
-          C.user_map = P.rt2_list;
-          C.n_active = P.rt2_cnt;
-          sweep(C);
-          select_wide(C, 1024u);
-        }
-      }
-      P.wide_cnt = wide_cnt;     // (for the counters the exact-route launch reports)
-    }
-    rc = check_launch("score prefilter kernels");
-    if (rc) return rc;
-    if (!do_back) return CHAOREC_OK;
-    // uncertified users (list overflow, fewer than K above the threshold, band wider than the re-score slots) were
-    // queued on the device.  Large item ranges: the first kPfFbGroupCap of them as a compact user set through the
-    // unthresholded f32 MFMA sweep (32 users share each pass over the items), results written to their own rows.
-    P.fb_skip = 0;
-    if (p.pf_group_fb) {
-      ScoreArgs f = a;
-      f.n_users = kPfFbGroupCap;
-      f.user_map = P.fb_list;
-      f.n_users_dev = P.fb_cnt;
-      f.splits = p.pf_group_fb_splits;
-      f.tiles_per_split = (n_tiles + f.splits - 1) / f.splits;
-      f.partial = (uint64_t *)(ws + p.off_pf_fbgroup);
-      rc = dispatch_score(D, f, dim3(kPfFbGroupCap / 32, (unsigned)f.splits), st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(score_topk_merge_kernel, dim3(kPfFbGroupCap), dim3(64), 0, st, f.partial,
-                         (int64_t)kPfFbGroupCap, K, f.splits, id_offset, out_idx, out_val, (const float *)nullptr,
-                         (int *)nullptr, (const int *)nullptr, (const int *)P.fb_list, (const int *)P.fb_cnt, hint_out);
-      rc = check_launch("score_topk_merge_kernel (grouped fallback)");
-      if (rc) return rc;
-      P.fb_skip = kPfFbGroupCap;
-    }
-    // ... and exact fp32 scores of all items for each remaining one, one block per (user, item slice)
-    // The queue is nearly always EMPTY (steady sports calls: no user at all) or a handful of users; the launch walks it
-    // with a grid stride, so the grid only bounds how many (user, slice) pairs run at once.  Short item ranges: 16 users
-    // x kExSlices -- 512 workgroups of 1024 threads (one per CU at a time: two dispatch rounds) cost 19 us on an empty
-    // queue, as much as ranking 3 users.  Long ranges keep the wide grid: their queue is what 512 grouped users left over.
-    const unsigned ex_grid = p.pf_group_fb ? (D == 64 ? 512u : 1024u) : 16u * kExSlices;
-    if (D == 64) hipLaunchKernelGGL(score_exact_user_kernel<64>, dim3(ex_grid), dim3(ex_threads<64>()), 0, st, P);
-    else hipLaunchKernelGGL(score_exact_user_kernel<128>, dim3(ex_grid), dim3(ex_threads<128>()), 0, st, P);
-    return check_launch("score_exact_user_kernel");
+// the packed fp32 item table of the register-resident kernels
+static int pack_f32_table(const ScoreCall &c, const ScorePlan &p, ScoreArgs &a) {
+  float4 *packed = (float4 *)(c.ws() + p.off_packed);
+  const int64_t n4 = c.n_tiles() * (c.D / 8) * 64;
+  hipLaunchKernelGGL(pack_items_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, c.stream, c.item_emb,
+                     packed, c.n_items, (int)c.D, c.n_tiles());
+  a.packed = packed;
+  return check_launch("pack_items_kernel");
+}
+
+// one candidate sweep of x over `sp` item splits into the call's candidate lists
+static int launch_candidates(const ScoreCall &c, const ScorePlan &p, const ScoreArgs &x, unsigned sp) {
+  uint64_t *cand_buf = (uint64_t *)(c.ws() + p.off_cand);
+  int *cand_cnt = (int *)(c.ws() + p.off_cnt);
+  const dim3 g(c.groups(), sp);
+  hipStream_t st = c.stream;
+  switch (c.D) {
+    case 8: hipLaunchKernelGGL(score_candidates_kernel<8>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
+    case 16: hipLaunchKernelGGL(score_candidates_kernel<16>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
+    case 32: hipLaunchKernelGGL(score_candidates_kernel<32>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
+    case 64: hipLaunchKernelGGL(score_candidates_kernel<64>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
+    default: hipLaunchKernelGGL(score_candidates_kernel<128>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
   }
-  if (!do_back) return CHAOREC_OK;   // (the other routes have no front phase: the back-phase call does everything)
-  if (p.pack) {
-    float4 *packed = (float4 *)(ws + p.off_packed);
-    const int64_t n4 = n_tiles * (D / 8) * 64;
-    hipLaunchKernelGGL(pack_items_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, item_emb,
-                       packed, n_items, (int)D, n_tiles);
-    rc = check_launch("pack_items_kernel");
-    if (rc) return rc;
-    a.packed = packed;
-  }
-  if (p.sample) {
-    // sampled threshold -> sort-free candidate sweep -> exact selection + certification -> fallback
-    float *tau = (float *)(ws + p.off_tau);
-    int *failf = (int *)(ws + p.off_fail);
-    uint64_t *cand_buf = (uint64_t *)(ws + p.off_cand);
-    int *cand_cnt = (int *)(ws + p.off_cnt);
-    // Sampling: two sort-free candidate sweeps + two selections instead of one prune-heavy streaming top-r:
-    //  S1  candidate sweep of the first 4 sampled tiles with no threshold (128 scores per user);
-    //      tau1 = their 6th best
-    //  S2  candidate sweep of ALL sampled tiles against tau1 (~5 % pass), item range in 4 splits;
-    //      tau0 = the r-th best of those
-    float *tau1 = (float *)(ws + p.off_tau1);
-    auto launch_cand = [&](const ScoreArgs &x, unsigned sp) -> int {
-      const dim3 g(groups, sp);
-      switch (D) {
-        case 8: hipLaunchKernelGGL(score_candidates_kernel<8>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
-        case 16: hipLaunchKernelGGL(score_candidates_kernel<16>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
-        case 32: hipLaunchKernelGGL(score_candidates_kernel<32>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
-        case 64: hipLaunchKernelGGL(score_candidates_kernel<64>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
-        default: hipLaunchKernelGGL(score_candidates_kernel<128>, g, dim3(64), 0, st, x, cand_buf, cand_cnt); break;
-      }
-      return check_launch("score_candidates_kernel");
-    };
-    ScoreArgs s1 = a;
-    s1.K = 6;
-    s1.tile_stride = p.tile_stride;
-    s1.max_tiles = 4;
-    s1.tiles_per_split = 4;
-    s1.tau = nullptr;
-    rc = launch_cand(s1, 1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users, 6,
-                       1, id_offset, (const float *)nullptr, out_idx, out_val, failf, tau1);
-    rc = check_launch("score_select_kernel(S1)");
-    if (rc) return rc;
-    const int n_samp = (int)((n_tiles + p.tile_stride - 1) / p.tile_stride);
-    const int samp_splits = (n_samp >= 16 && p.splits >= 4) ? 4 : 1;  // (the candidate region holds p.splits lists)
-    ScoreArgs s2 = a;
-    s2.K = p.sample_rank;
-    s2.tile_stride = p.tile_stride;
-    s2.tiles_per_split = (n_samp + samp_splits - 1) / samp_splits;
-    s2.tau = tau1;
-    rc = launch_cand(s2, (unsigned)samp_splits);
-    if (rc) return rc;
-    hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users,
-                       p.sample_rank, samp_splits, id_offset, (const float *)tau1, out_idx, out_val, failf, tau);
-    rc = check_launch("score_select_kernel(S2)");
-    if (rc) return rc;
-    a.tau = tau;
-    rc = launch_cand(a, (unsigned)p.splits);
-    if (rc) return rc;
-    hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users,
-                       K, p.splits, id_offset, (const float *)tau, out_idx, out_val, failf, (float *)nullptr);
-    rc = check_launch("score_select_kernel");
-    if (rc) return rc;
-    // users with fewer than K scores above their sampled threshold (expected: a handful per million) re-run
-    // unthresholded: their groups sweep the same item splits with the LDS-list kernel, then a merge
-    ScoreArgs f = a;
-    f.mode = kModeFallback;
-    f.tau = nullptr;
-    f.certify = nullptr;
-    f.fail = failf;
-    rc = dispatch_score(D, f, dim3(groups, (unsigned)p.splits), st);
-    if (rc) return rc;
-    if (p.splits > 1) {
-      hipLaunchKernelGGL(score_topk_merge_kernel, dim3((unsigned)n_users), dim3(64), 0, st, a.partial, n_users, K,
-                         p.splits, id_offset, out_idx, out_val, (const float *)nullptr, (int *)nullptr,
-                         (const int *)failf, (const int *)nullptr, (const int *)nullptr);
-      rc = check_launch("score_topk_merge_kernel");
-    }
-    return rc;
-  }
-  rc = dispatch_score(D, a, dim3(groups, (unsigned)p.splits), st);
+  return check_launch("score_candidates_kernel");
+}
+
+// sampled threshold -> sort-free candidate sweep -> exact selection + certification -> fallback
+static int sampled_route(const ScoreCall &c, const ScorePlan &p, ScoreArgs a) {
+  hipStream_t st = c.stream;
+  const int64_t n_users = c.n_users;
+  float *tau = (float *)(c.ws() + p.off_tau);
+  int *failf = (int *)(c.ws() + p.off_fail);
+  uint64_t *cand_buf = (uint64_t *)(c.ws() + p.off_cand);
+  int *cand_cnt = (int *)(c.ws() + p.off_cnt);
+  // Sampling: two sort-free candidate sweeps + two selections instead of one prune-heavy streaming top-r:
+  //  S1  candidate sweep of the first 4 sampled tiles with no threshold (128 scores per user);
+  //      tau1 = their 6th best
+  //  S2  candidate sweep of ALL sampled tiles against tau1 (~5 % pass), item range in 4 splits;
+  //      tau0 = the r-th best of those
+  float *tau1 = (float *)(c.ws() + p.off_tau1);
+  ScoreArgs s1 = a;
+  s1.K = 6;
+  s1.tile_stride = p.tile_stride;
+  s1.max_tiles = 4;
+  s1.tiles_per_split = 4;
+  s1.tau = nullptr;
+  int rc = launch_candidates(c, p, s1, 1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users, 6,
+                     1, c.id_offset, (const float *)nullptr, c.out_idx, c.out_val, failf, tau1);
+  rc = check_launch("score_select_kernel(S1)");
+  if (rc) return rc;
+  const int n_samp = (int)((c.n_tiles() + p.tile_stride - 1) / p.tile_stride);
+  const int samp_splits = (n_samp >= 16 && p.splits >= 4) ? 4 : 1;  // (the candidate region holds p.splits lists)
+  ScoreArgs s2 = a;
+  s2.K = p.sample_rank;
+  s2.tile_stride = p.tile_stride;
+  s2.tiles_per_split = (n_samp + samp_splits - 1) / samp_splits;
+  s2.tau = tau1;
+  rc = launch_candidates(c, p, s2, (unsigned)samp_splits);
+  if (rc) return rc;
+  hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users,
+                     p.sample_rank, samp_splits, c.id_offset, (const float *)tau1, c.out_idx, c.out_val, failf, tau);
+  rc = check_launch("score_select_kernel(S2)");
+  if (rc) return rc;
+  a.tau = tau;
+  rc = launch_candidates(c, p, a, (unsigned)p.splits);
+  if (rc) return rc;
+  hipLaunchKernelGGL(score_select_kernel, dim3((unsigned)n_users), dim3(64), 0, st, cand_buf, cand_cnt, n_users,
+                     c.K, p.splits, c.id_offset, (const float *)tau, c.out_idx, c.out_val, failf, (float *)nullptr);
+  rc = check_launch("score_select_kernel");
+  if (rc) return rc;
+  // users with fewer than K scores above their sampled threshold (expected: a handful per million) re-run
+  // unthresholded: their groups sweep the same item splits with the LDS-list kernel, then a merge
+  ScoreArgs f = a;
+  f.mode = kModeFallback;
+  f.tau = nullptr;
+  f.certify = nullptr;
+  f.fail = failf;
+  rc = dispatch_score(c.D, f, dim3(c.groups(), (unsigned)p.splits), st);
   if (rc) return rc;
   if (p.splits > 1) {
-    hipLaunchKernelGGL(score_topk_merge_kernel, dim3((unsigned)n_users), dim3(64), 0, st, a.partial, n_users,
-                       K, p.splits, id_offset, out_idx, out_val, (const float *)nullptr, (int *)nullptr,
+    hipLaunchKernelGGL(score_topk_merge_kernel, dim3((unsigned)n_users), dim3(64), 0, st, a.partial, n_users, c.K,
+                       p.splits, c.id_offset, c.out_idx, c.out_val, (const float *)nullptr, (int *)nullptr,
+                       (const int *)failf, (const int *)nullptr, (const int *)nullptr);
+    rc = check_launch("score_topk_merge_kernel");
+  }
+  return rc;
+}
+
+// one unthresholded fp32 pass over the item splits, then their merge
+static int single_pass_route(const ScoreCall &c, const ScorePlan &p, const ScoreArgs &a) {
+  int rc = dispatch_score(c.D, a, dim3(c.groups(), (unsigned)p.splits), c.stream);
+  if (rc) return rc;
+  if (p.splits > 1) {
+    hipLaunchKernelGGL(score_topk_merge_kernel, dim3((unsigned)c.n_users), dim3(64), 0, c.stream, a.partial, c.n_users,
+                       c.K, p.splits, c.id_offset, c.out_idx, c.out_val, (const float *)nullptr, (int *)nullptr,
                        (const int *)nullptr, (const int *)nullptr, (const int *)nullptr);
     rc = check_launch("score_topk_merge_kernel");
     if (rc) return rc;
   }
   return CHAOREC_OK;
+}
+
+// ---- checks, plan, route -----------------------------------------------------------------------------------------------
+static int score_topk_impl(const ScoreCall &c) {
+  const int32_t D = c.D, K = c.K;
+  if (!c.user_emb || !c.item_emb || !c.out_idx || !c.out_val) return fail(CHAOREC_E_INVALID, "score_topk: NULL argument");
+  if (c.n_users < 0 || c.n_items <= 0) return fail(CHAOREC_E_INVALID, "score_topk: bad sizes");
+  if (K < 1 || K > kMaxK) return fail(CHAOREC_E_INVALID, "score_topk: K=%d must be in [1,%d]", K, kMaxK);
+  if (c.n_items < K) return fail(CHAOREC_E_INVALID, "score_topk: n_items=%lld < K=%d (torch.topk would raise)", (long long)c.n_items, K);
+  if (c.n_items > 0xFFFFFFF0ll) return fail(CHAOREC_E_INVALID, "score_topk: n_items too large");
+  if (c.precision < 0 || c.precision > 2) return fail(CHAOREC_E_INVALID, "score_topk: precision %d not built", c.precision);
+  if (c.hist_rowptr && !c.hist_col) return fail(CHAOREC_E_INVALID, "score_topk: hist_rowptr without hist_col");
+  if (!((D == 8 || D == 16 || D == 32 || D == 64 || D == 128) || (D > 128 && D % 64 == 0)))
+    return fail(CHAOREC_E_INVALID, "score_topk: D=%d not in {8,16,32,64,128} and not a multiple of 64 above 128", D);
+  if (c.n_users == 0) return CHAOREC_OK;
+  // a BACK-only call continues what a FRONT call began in this workspace: same layout, whatever the environment says now
+  const bool back_only = (c.flags & CHAOREC_SCORE_BACK) && !(c.flags & CHAOREC_SCORE_FRONT);
+  ScorePlan p = plan_score(c.n_users, c.n_items, K, D, back_only ? recall_layout(c.workspace) : -1);
+  if (!back_only && c.workspace) remember_layout(c.workspace, p.pf_cls);
+  if (c.precision == 1) p.sample = false;  // precision 1: single exact pass, no sampled threshold (A/B + tests)
+  if (c.precision != 0) p.prefilter = false;  // precision 2: fp32 sweep with sampled thresholds (the pre-bf16 path)
+  if (p.total > c.workspace_bytes || (p.total && !c.workspace))
+    return fail(CHAOREC_E_WORKSPACE, "score_topk: workspace %zu < %zu", c.workspace_bytes, p.total);
+  if (reinterpret_cast<uintptr_t>(c.workspace) & 255)
+    return fail(CHAOREC_E_INVALID, "score_topk: workspace must be 256-byte aligned");
+  // phases of one call split over two calls (same arguments, same workspace; a caller that ranks several user ranges can
+  // run range k's back phase beside range k + 1's front phase on another stream): neither flag = the whole call
+  const bool do_front = !(c.flags & CHAOREC_SCORE_BACK) || (c.flags & CHAOREC_SCORE_FRONT);
+  const bool do_back = !(c.flags & CHAOREC_SCORE_FRONT) || (c.flags & CHAOREC_SCORE_BACK);
+  ScoreArgs a = f32_args(c, p);
+  if (p.prefilter) return prefilter_route(c, p, a, do_front, do_back);
+  if (!do_back) return CHAOREC_OK;   // (the other routes have no front phase: the back-phase call does everything)
+  if (p.pack) {
+    const int rc = pack_f32_table(c, p, a);
+    if (rc) return rc;
+  }
+  return p.sample ? sampled_route(c, p, a) : single_pass_route(c, p, a);
 }
 
 extern "C" int chaorec_score_topk_f32(const float *user_emb, const float *item_emb, int64_t n_users,
@@ -1449,8 +1557,9 @@ extern "C" int chaorec_score_topk_f32(const float *user_emb, const float *item_e
                                       int64_t id_offset, int64_t *out_idx, float *out_val,
                                       void *workspace, size_t workspace_bytes, int32_t precision,
                                       void *stream) {
-  return score_topk_impl(user_emb, item_emb, n_users, n_items, D, hist_rowptr, hist_col, mask_value, K, id_offset, out_idx,
-                         out_val, workspace, workspace_bytes, precision, nullptr, nullptr, 0, 0, nullptr, stream);
+  const ScoreCall c = {user_emb, item_emb, n_users, n_items, D, hist_rowptr, hist_col, mask_value, K, id_offset, out_idx,
+                       out_val, workspace, workspace_bytes, precision, nullptr, nullptr, 0, 0, nullptr, (hipStream_t)stream};
+  return score_topk_impl(c);
 }
 
 extern "C" int chaorec_score_topk_hinted_f32(const float *user_emb, const float *item_emb, int64_t n_users,
@@ -1460,6 +1569,9 @@ extern "C" int chaorec_score_topk_hinted_f32(const float *user_emb, const float 
                                              void *workspace, size_t workspace_bytes, const float *hint_in,
                                              float *hint_out, int32_t hint_rank, int32_t flags,
                                              int32_t *counters_out, void *stream) {
-  return score_topk_impl(user_emb, item_emb, n_users, n_items, D, hist_rowptr, hist_col, mask_value, K, id_offset, out_idx,
-                         out_val, workspace, workspace_bytes, 0, hint_in, hint_out, hint_rank, flags, counters_out, stream);
+  const ScoreCall c = {user_emb, item_emb, n_users, n_items, D, hist_rowptr, hist_col, mask_value, K, id_offset, out_idx,
+                       out_val, workspace, workspace_bytes, 0, hint_in, hint_out, hint_rank, flags, counters_out,
+                       (hipStream_t)stream};
+  return score_topk_impl(c);
 }
+

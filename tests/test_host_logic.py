@@ -28,6 +28,26 @@ def test_abi_exports_every_declared_symbol():
     assert _lib.load().chaorec_score_topk_workspace_bytes(28940, 15207, 50, 64) > 0
 
 
+def test_score_workspace_bytes_are_the_recorded_ones(monkeypatch):
+    """The ranking workspace's size over a grid that flips every condition of plan_score (tests/golden/
+    gen_score_workspace.py) equals what the library answered before its host code was restructured (feb0de9).  ops.score_topk
+    and benchlib cut users into ranges by this number; it does not depend on the device."""
+    import json
+    from chaorec_amd import _lib
+    _lib.build()
+    query = _lib.load().chaorec_score_topk_workspace_bytes
+    with open(os.path.join(ROOT, "tests", "golden", "score_workspace_bytes.json")) as f:
+        rows = json.load(f)
+    assert len(rows) == 25
+    for row in rows:
+        for name in ("CHAOREC_PF_CLS_MIN_ITEMS", "CHAOREC_PF_CLS_STRIDE", "CHAOREC_PF_CLS_RANK"):
+            monkeypatch.delenv(name, raising=False)
+        for name, value in row["env"].items():
+            monkeypatch.setenv(name, value)      # (the library reads them per call)
+        got = query(row["users"], row["items"], row["K"], row["D"])
+        assert got == row["bytes"], (row, got)
+
+
 _MINI_HEADER = """
 /* a comment with ( and ) and ; in it: int chaorec_not_a_function(int x); */
 #ifndef MINI_H
