@@ -28,6 +28,8 @@ def build_parser():
     parser.add_argument('--mm_layers', type=int, default=2, help='the number of multimodal layer.')
     parser.add_argument('--ssl_temp', type=float, default=0.9, help='temperature coefficient.')
     parser.add_argument('--ssl_alpha', type=float, default=0.9, help='ssl coefficient.')
+    parser.add_argument('--noise_alpha', type=float, default=0.3, help='Grade noise weight')   # (arg_parser.py:64 says type=int with this default: a slip)
+    parser.add_argument('--ssl_temp2', type=float, default=0.2, help='Grade temperature coefficient.')
     parser.add_argument('--e_loss', type=float, default=0.1, help='DiffMM e_loss(lamba0).')
     parser.add_argument('--ris_lambda', type=float, default=0.5, help='DiffMM (eq23 omega).')
     parser.add_argument('--rebuild_k', type=int, default=1, help='DiffMM rebuild top-k.')

@@ -3,9 +3,8 @@
 // The structure is the model's one symmetric-pattern CSR over N = U + I nodes (rowptr int64 [N + 1], col int32 [E],
 // entry_row int32 [E], tentry int32 [E]: entry tentry[e] is the stored entry (col e, row e)).
 //
-// Row ownership, everywhere a row is summed: a wave holds AG_RW = 8 rows, 8 lanes each (lane j of a row takes its entries
-// j, j + 8, ..., then a butterfly xor 4, 2, 1); a row with more than AG_LONG = 64 entries is taken by its whole wave
-// afterwards (lane j: entries j, j + 64, ...; butterfly xor 32 .. 1).  A sum's order depends on the row's length alone:
+// Row ownership, everywhere a row is summed, and the MLP tile of (c) are edge_mlp.h's (shared with grade.hip): 8 lanes per
+// row, a row with more than AG_LONG = 64 entries taken by its whole wave; a sum's order depends on the row's length alone:
 // two runs give the same bits.  No atomics on floats; the one atomic is the integer count of kept entries in (c).
 //
 // (a) edge gate, DenoisingNet.generate (evaluation form) / DenoisingNet.call (training form), per layer:
@@ -33,53 +32,12 @@
 //   one instruction sit in different halves of the 64 banks), B = the gathered rows' product, formed in registers.  The
 //   features are the accumulator's rows, so the w2 dot is a per-lane sum over 32 registers and one xor-32 exchange.
 //   Workgroups stride over the tiles of 256 entries; the tail is masked.
-#include "vae_common.h"
+#include "edge_mlp.h"
 
 namespace chaorec {
 
-constexpr int AG_D = 64;
-constexpr int AG_RW = 8;           // rows per wave
-constexpr int AG_RB = kRowsPerBlock8;      // rows per workgroup
-constexpr int AG_LONG = 64;        // a longer row is taken by the whole wave
 constexpr float AG_GAMMA = -0.45f, AG_STRETCH = 1.5f;      // zeta - gamma = 1.05 + 0.45
 constexpr float AG_U_LO = 1e-7f, AG_U_HI = 0.99999988f;    // fl32(1 - 1e-7)
-
-struct ag2 {
-  float a, b;
-};
-
-// every lane of the wave calls; n / [beg, end): the lane group's row (beg = end for none).  f(e, row) -> ag2, called once per
-// entry.  -> the row's two sums, on every lane of its group
-template <class F>
-__device__ __forceinline__ ag2 ag_row_reduce(int64_t n, int64_t beg, int64_t end, int lane, F f) {
-  const int sub = lane & 7;
-  const bool is_long = end - beg > AG_LONG;
-  ag2 acc = {0.f, 0.f};
-  if (!is_long)
-    for (int64_t e = beg + sub; e < end; e += 8) {
-      const ag2 t = f(e, n);
-      acc.a += t.a;
-      acc.b += t.b;
-    }
-  acc.a = group_sum<8>(acc.a);
-  acc.b = group_sum<8>(acc.b);
-  unsigned long long mask = __ballot(is_long && sub == 0);
-  while (mask) {
-    const int src = __ffsll((long long)mask) - 1;
-    mask &= mask - 1;
-    const int64_t n_s = __shfl(n, src, 64), b_s = __shfl(beg, src, 64), e_s = __shfl(end, src, 64);
-    ag2 t = {0.f, 0.f};
-    for (int64_t e = b_s + lane; e < e_s; e += 64) {
-      const ag2 x = f(e, n_s);
-      t.a += x.a;
-      t.b += x.b;
-    }
-    t.a = wave_sum(t.a);
-    t.b = wave_sum(t.b);
-    if ((lane >> 3) == (src >> 3)) acc = t;
-  }
-  return acc;
-}
 
 // part[blockIdx.x] = the sum of the group leaders' v over the workgroup: butterfly per wave, then waves 0..3 in order
 __device__ __forceinline__ void ag_block_partial(float v, int lane, int wave, float *__restrict__ part) {
@@ -215,53 +173,18 @@ __global__ __launch_bounds__(256) void ag_keep_kernel(const float *__restrict__ 
                                                       const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
                                                       const float *__restrict__ vals, uint8_t *__restrict__ keep, float *__restrict__ out,
                                                       unsigned long long *__restrict__ kept, float *__restrict__ logit_out) {
-  __shared__ float Ws[AG_D * AG_D];      // Ws[k][f ^ 32 (k & 1)] = W1[f][k]
-  __shared__ float b1s[AG_D], w2s[AG_D];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int p = 0; p < AG_D * AG_D / 256; ++p) {
-    const int idx = t + 256 * p, k = idx >> 6, f = idx & 63;
-    Ws[AG_D * k + (f ^ ((k & 1) << 5))] = W1[f * AG_D + k];
-  }
-  if (t < AG_D) {
-    b1s[t] = b1[t];
-    w2s[t] = w2[t];
-  }
-  __syncthreads();
+  __shared__ EdgeMlpLds lds;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  edge_mlp_stage(lds, W1, b1, w2, t);
   const float bias2 = b2[0];
   const int64_t n_tiles = (E + 255) / 256;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t e0 = tile * 256 + wave * 64;
     if (e0 >= E) continue;
-    float mine = 0.f;
-#pragma unroll
-    for (int et = 0; et < 2; ++et) {
-      const int64_t e = e0 + 32 * et + r, ee = e < E ? e : E - 1;
-      const float4 *zr = reinterpret_cast<const float4 *>(z + (int64_t)clamp_index(entry_row[ee], N) * AG_D);
-      const float4 *zc = reinterpret_cast<const float4 *>(z + (int64_t)clamp_index(col[ee], N) * AG_D);
-      float bf[AG_D / 2];                // P[entry r][k = 2 s + h]
-#pragma unroll
-      for (int q = 0; q < AG_D / 4; ++q) {
-        const float4 a = zr[q], c = zc[q];
-        bf[2 * q] = fmaxf(h ? a.y * c.y : a.x * c.x, 0.f);
-        bf[2 * q + 1] = fmaxf(h ? a.w * c.w : a.z * c.z, 0.f);
-      }
-      float tsum = 0.f;
-#pragma unroll
-      for (int jt = 0; jt < 2; ++jt) {
-        f32x16 acc = vae_zero();
-#pragma unroll
-        for (int s = 0; s < AG_D / 2; ++s)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[AG_D * (2 * s + h) + ((32 * jt + r) ^ (h << 5))], bf[s], acc, 0, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int f = 32 * jt + vae_row(q, h);
-          tsum += w2s[f] * fmaxf(acc[q] + b1s[f], 0.f);
-        }
-      }
-      tsum += __shfl_xor(tsum, 32, 64);
-      if (h == et) mine = tsum + bias2;
-    }
+    const float mine = edge_mlp_tile(lds, z, bias2, lane, [&](int slot) -> EdgeNodes {
+      const int64_t e = e0 + slot, ee = e < E ? e : E - 1;
+      return {clamp_index(entry_row[ee], N), clamp_index(col[ee], N)};
+    });
     const int64_t e = e0 + lane;
     const bool valid = e < E;
     const bool kp = valid && floorf(sigmoidf_acc(mine) + 0.5f) != 0.f;

@@ -1756,6 +1756,59 @@ def adagcl_edge_keep(structure, z, W1, b1, w2, b2, vals, return_logits=False):
 
 
 # --------------------------------------------------------------------------------------------
+# Grade (csrc/grade.hip): the views of its G generators over one graph.DropoutStructure, three launches
+# --------------------------------------------------------------------------------------------
+GRADE_DIM = 64               # the row width the kernels tile
+
+
+def grade_check_shape(D):
+    if int(D) != GRADE_DIM:
+        raise ValueError(f"Grade: dim_E={D}; the kernels tile D={GRADE_DIM}")
+
+
+def grade_pair_owner(structure):
+    """The entries with entry_row[e] <= col[e], ascending, int32 [P]: every stored entry is e or transpose_entry[e] of exactly
+    one of them.  Built once per structure (one host round trip for P) and cached on the structure object."""
+    owner = getattr(structure, "pair_owner", None)
+    if owner is None:
+        owner = torch.nonzero(structure.entry_row <= structure.col).reshape(-1).to(torch.int32).contiguous()
+        structure.pair_owner = owner
+    return owner
+
+
+def grade_views(structure, z, W1, b1, w2, b2, return_parts=False):
+    """The normalised views of G generators (vgae.generate, Model/Grade.py:119-151) per stored entry of `structure` (a
+    graph.DropoutStructure); no gradient, no host synchronisation (the owner list is cached by grade_pair_owner).
+    z [G, N, 64] or [N, 64] (G = 1), W1 [G, 64, 64], b1 [G, 64], w2 [G, 64] or [G, 1, 64], b2 [G] or [G, 1] -> val [G, E];
+    return_parts adds (keep bool [G, E], kept int64 [G] on the device, logits [G, E], d [G, N])."""
+    _need_cuda(z, W1, b1, w2, b2, structure.rowptr)
+    N, E = structure.n_rows, structure.nnz
+    with torch.no_grad():
+        if z.dim() == 2:
+            z = z.unsqueeze(0)
+        if z.dim() != 3:
+            raise ValueError(f"grade: z is {tuple(z.shape)}, expected [G, N, {GRADE_DIM}]")
+        grade_check_shape(z.shape[2])
+        G = int(z.shape[0])
+        z = _vae_f32("grade", z.detach().contiguous(), "z", (G, N, GRADE_DIM))
+        W1 = _vae_f32("grade", W1.detach().contiguous().reshape(-1, GRADE_DIM, GRADE_DIM), "W1", (G, GRADE_DIM, GRADE_DIM))
+        b1 = _vae_f32("grade", b1.detach().contiguous().reshape(-1, GRADE_DIM), "b1", (G, GRADE_DIM))
+        w2 = _vae_f32("grade", w2.detach().contiguous().reshape(-1, GRADE_DIM), "w2", (G, GRADE_DIM))
+        b2 = _vae_f32("grade", b2.detach().contiguous().reshape(-1), "b2", (G,))
+        owner = grade_pair_owner(structure)
+        val = torch.empty(G, E, dtype=torch.float32, device=z.device)
+        keep = torch.empty(G, E, dtype=torch.uint8, device=z.device)
+        kept = torch.empty(G, dtype=torch.int64, device=z.device)
+        d = torch.empty(G, N, dtype=torch.float32, device=z.device)
+        logits = torch.empty(G, E, dtype=torch.float32, device=z.device) if return_parts else None
+        _lib.load().chaorec_grade_views_f32(_ptr(z), _ptr(W1), _ptr(b1), _ptr(w2), _ptr(b2), G, N, _ptr(structure.rowptr),
+                                            _ptr(structure.col), _ptr(structure.entry_row), _ptr(structure.transpose_entry), E,
+                                            _ptr(owner), int(owner.numel()), _ptr(val), _ptr(keep), _ptr(kept), _ptr(logits), _ptr(d),
+                                            _stream())
+    return (val, keep.to(torch.bool), kept, logits, d) if return_parts else val
+
+
+# --------------------------------------------------------------------------------------------
 # GraphAug (csrc/graphaug.hip): the view learner's edge sampler, the contrastive loss's whole-table log-sum-exp, the
 # propagate's random-entry term
 # --------------------------------------------------------------------------------------------

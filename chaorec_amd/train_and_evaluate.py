@@ -22,7 +22,8 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 # they are captured (round 5: 2 x the eager epoch rate at baby size, tools/capture_family_probe.py).
 # DiffMM: three phases per epoch, the graphs its loss() multiplies with are rebuilt in the second.
 NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL",    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
-              "GraphAug")             # (its views' structure -- the random entries -- changes every step; the plain loss() loop below)
+              "GraphAug",             # (its views' structure -- the random entries -- changes every step; the plain loss() loop below)
+              "Grade")                # (four optimizers per batch, its own loop)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):
@@ -111,6 +112,39 @@ def _train_epoch_adagcl(model, train_loader, optimizer):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_grade(model, train_loader, optimizer):
+    """reference train_and_evaluate.py:259-284: four Adam optimizers created anew every epoch (their moments restart) -- `opt` over
+    ALL parameters, one per generator -- and per batch three losses: loss_1 and bpr_reg_loss each stepped by `opt`, gen_loss
+    stepped by the three generators' optimizers (the gradients it leaves on the embeddings are dropped by the next
+    opt.zero_grad()).  The optimizer main() built only gives the learning rate."""
+    lr = optimizer.param_groups[0]['lr']
+    opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=0)
+    opt_gen_1 = torch.optim.Adam(model.generator_1.parameters(), lr=lr, weight_decay=0)
+    opt_gen_2 = torch.optim.Adam(model.generator_2.parameters(), lr=lr, weight_decay=0)
+    opt_gen_3 = torch.optim.Adam(model.generator_3.parameters(), lr=lr, weight_decay=0)
+    sum_loss = None
+    for users, pos_items, neg_items in train_loader:
+        opt.zero_grad()
+        loss_1 = model.loss_1(users, pos_items, neg_items)
+        loss_1.backward()
+        opt.step()
+        opt.zero_grad()
+        bpr_reg_loss = model.bpr_reg_loss(users, pos_items, neg_items)
+        bpr_reg_loss.backward()
+        opt.step()
+        opt_gen_1.zero_grad()
+        opt_gen_2.zero_grad()
+        opt_gen_3.zero_grad()
+        gen_loss = model.gen_loss(users, pos_items, neg_items)
+        gen_loss.backward()
+        opt_gen_1.step()
+        opt_gen_2.step()
+        opt_gen_3.step()
+        d = (loss_1 + gen_loss + bpr_reg_loss).detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    return float(sum_loss.item()) if sum_loss is not None else 0.0
+
+
 def _train_epoch_diffmm(model, train_loader, optimizer, diffusion_loader=None):
     """reference train_and_evaluate.py:140-244 in its three phases: (1) one pass of the diffusion loader, per batch a step of
     each denoiser under two Adam optimizers created anew every epoch (:142-145: their moments restart); (2) the two modal
@@ -162,6 +196,8 @@ def train(model, train_loader, optimizer, model_name="LightGCN", graphed=None):
         return _train_epoch_diffmm(model, train_loader, optimizer)
     if model_name == "AdaGCL":
         return _train_epoch_adagcl(model, train_loader, optimizer)
+    if model_name == "Grade":
+        return _train_epoch_grade(model, train_loader, optimizer)
     if graphed is not None and getattr(graphed, "draws_in_launch", False):
         return _train_epoch_in_launch(model, train_loader, optimizer, graphed)
     sum_loss = None

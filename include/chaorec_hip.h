@@ -1340,6 +1340,24 @@ int chaorec_adagcl_keep_f32(const float *z, int64_t N, const int32_t *entry_row,
                             int64_t *kept, float *logit_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Grade (Model/Grade.py) -- csrc/grade.hip.  Additive to ABI 16: new names only.  D = 64 is what the kernels tile
+ * (chaorec_grade_check_shape: CHAOREC_E_INVALID otherwise).
+ * The views of G independent generators (vgae.generate + normalize_adjacency_matrix) over AdaGCL's structure, three launches
+ * with the generators in gridDim.y: z [G, N, 64], W1 [G, 64, 64], b1 [G, 64], w2 [G, 64], b2 [G]; owner int32 [P]: the
+ * entries with entry_row[e] <= col[e] (each undirected pair once; every entry is e or tentry[e] of exactly one of them).
+ *   logit = w2 . relu(W1 relu(z[row] * z[col]) + b1) + b2, p = sigmoid(logit), keep = floor(p + 0.5) != 0, computed once per
+ *   pair and written to both of its entries; S[n] = sum_row (keep ? p : 0) + 1e-7f, d[n] = S^-1/2;
+ *   val[e] = val[tentry[e]] = (d[row e] p[e]) d[col e] at the owner e, +0 where dropped.
+ * -> val fp32 [G, E], keep uint8 [G, E], kept int64 [G] (stored entries kept; zeroed here), d fp32 [G, N], logit_out fp32
+ * [G, E] or NULL.  No float atomics: two runs give the same bits, and val[tentry[e]] has the bits of val[e].
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_grade_check_shape(int32_t D);
+int chaorec_grade_views_f32(const float *z, const float *W1, const float *b1, const float *w2, const float *b2, int32_t G,
+                            int64_t N, const int64_t *rowptr, const int32_t *col, const int32_t *entry_row,
+                            const int32_t *tentry, int64_t E, const int32_t *owner, int64_t P, float *val, uint8_t *keep,
+                            int64_t *kept, float *logit_out, float *d, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * GraphAug (Model/GraphAug.py) -- csrc/graphaug.hip.  Additive to ABI 16: new names only.  D = 64 is what the kernels
  * tile (chaorec_graphaug_check_shape: CHAOREC_E_INVALID otherwise).  No float atomics: every output has one owner and
  * every sum a fixed order, so two runs on the same inputs give the same bits.

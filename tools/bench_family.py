@@ -21,7 +21,7 @@ from chaorec_amd.optim import FusedAdam  # noqa: E402
 
 ALL = ["LightGCN", "NGCF", "LayerGCN", "BPR", "VBPR", "MGCN", "FREEDOM", "MMGCN", "SimGCL", "XSimGCL", "NCL", "SelfCF", "SLMRec", "MCLN",
        "DHCF", "LGMRec", "POWERec", "SMORE", "GUME", "MMGCL", "FKAN_GCF", "VGCL", "DDRec", "DCCF", "MICRO", "LATTICE", "MENTOR", "HCCF",
-       "LightGCL", "SGL", "BM3", "MGCL", "MMSSL", "GRCN", "MGAT", "DGCF", "MultVAE", "MacridVAE", "DualVAE", "MVGAE", "DiffMM", "AdaGCL", "GraphAug"]
+       "LightGCL", "SGL", "BM3", "MGCL", "MMSSL", "GRCN", "MGAT", "DGCF", "MultVAE", "MacridVAE", "DualVAE", "MVGAE", "DiffMM", "AdaGCL", "GraphAug", "Grade"]
 models = sys.argv[1:] or ALL
 os.chdir(tempfile.mkdtemp())
 logging.disable(logging.CRITICAL)
