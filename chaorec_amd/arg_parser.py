@@ -33,6 +33,10 @@ def build_parser():
     parser.add_argument('--e_loss', type=float, default=0.1, help='DiffMM e_loss(lamba0).')
     parser.add_argument('--ris_lambda', type=float, default=0.5, help='DiffMM (eq23 omega).')
     parser.add_argument('--rebuild_k', type=int, default=1, help='DiffMM rebuild top-k.')
+    parser.add_argument('--h_layers', type=int, default=2, help='MHRec hypergraph layers.')
+    parser.add_argument('--num_hypernodes', type=int, default=10, help='MHRec: nodes per rebuilt hyperedge.')
+    parser.add_argument('--beta1', type=float, default=0.5, help='MHRec beta1')
+    parser.add_argument('--beta2', type=float, default=0.5, help='MHRec beta2')
     parser.add_argument('--n_mca', type=int, default=2, help='MCLN counterfactual layer.')
     parser.add_argument('--prompt_num', type=float, default=0.1, help='prompt modal numbers.')
     parser.add_argument('--neg_weight', type=float, default=0.1, help='weak modal weight.')

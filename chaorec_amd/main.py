@@ -12,7 +12,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import dataload
-from .Model import (AdaGCL, BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, Grade, GraphAug, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
+from .Model import (AdaGCL, BM3, BPRMF, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, Grade, GraphAug, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MHRec, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
                     SMORE, VBPR, VGCL, XSimGCL)
 from .arg_parser import load_yaml_config, parse_args
 from .train_and_evaluate import train_and_evaluate
@@ -166,7 +166,14 @@ def build_model(args, num_user, num_item, train_data, user_item_dict, v_feat, t_
         # sampler and the contrastive terms' whole-table log-sum-exp on kernels of their own, csrc/graphaug.hip
         'GraphAug': lambda: GraphAug(num_user, num_item, train_data, user_item_dict, dim_E, args.reg_weight, args.n_layers,
                                      args.ssl_temp, args.ssl_alpha, device),
+        # (main.py:374-376) two hypergraphs rebuilt every epoch from denoised hyperedge rows; the hypergraph attention layer with
+        # its residual and dropout is one autograd node, csrc/mhrec.hip; three phases per epoch (train_and_evaluate.py:331-512)
+        'MHRec': lambda: MHRec(num_user, num_item, train_data, user_item_dict, v_feat, t_feat, dim_E, args.reg_weight,
+                               args.ii_topk, args.uu_topk, args.num_hypernodes, args.n_layers, args.h_layers, args.ssl_temp,
+                               args.ssl_alpha, args.beta1, args.beta2, device),
     }
+    if args.Model == 'MHRec':      # Model/MHRec.py:578, :604-612 read user_graph_dict.npy and the hyperedge files there
+        MHRec.data_dir = os.path.join(args.data_root, args.data_path)
     if args.Model == 'COHESION':   # Model/COHESION.py:96-99 reads the same file
         COHESION.user_graph_path = os.path.join(args.data_root, args.data_path, 'user_graph_dict.npy')
     if args.Model == 'DualGNN':    # Model/DualGNN.py:166-170 reads the same file
@@ -190,7 +197,7 @@ def main(argv=None):
     if device.type != "cuda":
         raise SystemExit("chaorec_amd runs on the MI355X only: no GPU visible")
     config = load_yaml_config(args.Model)
-    needs_feat = args.Model in ("MMGCN", "FREEDOM", "MGCN", "VBPR", "SLMRec", "MCLN", "POWERec", "LGMRec", "SMORE", "MMGCL", "LightGT", "GUME", "DDRec", "MICRO", "MENTOR", "BM3", "MGCL", "LATTICE", "MMSSL", "GRCN", "MGAT", "DRAGON", "DualGNN", "COHESION", "MVGAE", "DiffMM", "Grade")
+    needs_feat = args.Model in ("MMGCN", "FREEDOM", "MGCN", "VBPR", "SLMRec", "MCLN", "POWERec", "LGMRec", "SMORE", "MMGCL", "LightGT", "GUME", "DDRec", "MICRO", "MENTOR", "BM3", "MGCL", "LATTICE", "MMSSL", "GRCN", "MGAT", "DRAGON", "DualGNN", "COHESION", "MVGAE", "DiffMM", "Grade", "MHRec")
     train_data, val_data, test_data, user_item_dict, num_user, num_item, v_feat, t_feat = dataload.data_load(
         args.data_path, has_v=needs_feat, has_t=needs_feat, data_root=args.data_root, synthetic=args.synthetic)
     if args.host_sampler:

@@ -23,7 +23,8 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 # DiffMM: three phases per epoch, the graphs its loss() multiplies with are rebuilt in the second.
 NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL",    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
               "GraphAug",             # (its views' structure -- the random entries -- changes every step; the plain loss() loop below)
-              "Grade")                # (four optimizers per batch, its own loop)
+              "Grade",                # (four optimizers per batch, its own loop)
+              "MHRec")                # (three phases per epoch, the hypergraphs its loss() reads are rebuilt in the second)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):
@@ -187,9 +188,66 @@ def _train_epoch_diffmm(model, train_loader, optimizer, diffusion_loader=None):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_mhrec(model, train_loader, optimizer, diffusion_loaders=None, times=None):
+    """reference train_and_evaluate.py:331-512 in its three phases: (1) one pass of the visual diffusion loader, then one of the
+    textual, each denoiser under an Adam optimizer created anew every epoch (:333-336: their moments restart); (2) the two
+    hypergraphs rebuilt from the denoised rows' top-k; (3) the BPR steps over them.  The returned sum is the BPR losses', as
+    there.  diffusion_loaders: a pair of iterables of input-hyperedge index batches; by default two dataload.DeviceUserBatches
+    over the interactions at the train loader's batch size, kept on the model between epochs.  times (optional dict): receives
+    the three phases' wall times in seconds (each ends with a device synchronisation)."""
+    import time
+    if diffusion_loaders is None:
+        diffusion_loaders = model.__dict__.get("_diffusion_loaders")
+        if diffusion_loaders is None:
+            from .dataload import DeviceUserBatches
+            n = model.diffusion_tables()[0].shape[0]
+            seed = getattr(train_loader, "seed", 42)
+            diffusion_loaders = model.__dict__["_diffusion_loaders"] = tuple(
+                DeviceUserBatches(n, train_loader.batch_size, model.device, seed + m) for m in range(2))
+
+    def mark(name, t0):
+        if times is not None:
+            torch.cuda.synchronize()
+            times[name] = time.perf_counter() - t0
+        return time.perf_counter()
+    t0 = time.perf_counter()
+    lr = optimizer.param_groups[0]['lr']
+    opts = (torch.optim.Adam(model.denoise_model_image.parameters(), lr=lr, weight_decay=0),
+            torch.optim.Adam(model.denoise_model_text.parameters(), lr=lr, weight_decay=0))
+    for m, (opt, loader) in enumerate(zip(opts, diffusion_loaders)):
+        diff_sum = None
+        for batch in loader:
+            opt.zero_grad()
+            loss = model.diffusion_step(batch, m)
+            loss.backward()
+            opt.step()
+            d = loss.detach()
+            diff_sum = d.clone() if diff_sum is None else diff_sum.add_(d)
+        if diff_sum is not None:
+            logging.info('%s hyperedges: Diffusion Loss (sum over %d steps) %.6f' % (("visual", "textual")[m], len(loader), float(diff_sum.item())))
+    t0 = mark("diffusion", t0)
+    logging.info('Start to re-build hypergraph matrix')
+    G_visual, G_textual = model.rebuild_hypergraphs(*diffusion_loaders)
+    logging.info('hypergraph matrix built!')
+    t0 = mark("rebuild", t0)
+    sum_loss = None
+    for users, pos_items, neg_items in train_loader:
+        optimizer.zero_grad()
+        loss = model.loss(users, pos_items, neg_items, G_visual, G_textual)
+        loss.backward()
+        optimizer.step()
+        d = loss.detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    out = float(sum_loss.item()) if sum_loss is not None else 0.0
+    mark("bpr", t0)
+    return out
+
+
 def train(model, train_loader, optimizer, model_name="LightGCN", graphed=None):
     """One epoch.  `graphed` (optim.GraphedTrainStep) replays the captured step for full-size batches."""
     model.train()
+    if model_name == "MHRec":
+        return _train_epoch_mhrec(model, train_loader, optimizer)
     if model_name == "MMSSL":
         return _train_epoch_mmssl(model, train_loader, optimizer)
     if model_name == "DiffMM":

@@ -1397,6 +1397,55 @@ int chaorec_graphaug_lse_bwd_f32(const float *A, const float *T, int64_t B, int6
 int chaorec_graphaug_rand_spmm_f32(const int64_t *rowptr, const int32_t *col, int64_t n_rows, int64_t n_cols, const float *x,
                                    const float *z, float alpha, float slope, float *y, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * MHRec (Model/MHRec.py) -- csrc/mhrec.hip.  Additive to ABI 16: new names only.  The hypergraph attention layer
+ * (HypergraphAttentionLayer.forward, :53-89) with the epilogue the model applies after it (:724-726), fp32, D = 64
+ * (chaorec_mhrec_check_shape: CHAOREC_E_INVALID otherwise).  No float atomics: every output has one owner and every sum
+ * a fixed order, so two runs on the same inputs give the same bits.
+ *
+ * The hypergraph: E hyperedges of exactly k distinct nodes, all values 1.  nodes int32 [E, k] (H^T as an ELL table) and the
+ * node-major CSR of the same pairs: rowptr int64 [N + 1], edge int32 [E k], a node's hyperedges ascending.  A node row of
+ * more than chaorec_mhrec_long_row() entries is cut into chunks of chaorec_mhrec_chunk() entries: long_node int32 [L],
+ * long_cptr int64 [L + 1] (a long row's chunks), chunk_node int32 [C], chunk_beg int64 [C] (a chunk's first CSR entry);
+ * L = 0: the four may be NULL.  A lane group of 16 lanes x float4 holds a row, chaorec_mhrec_rows_per_block() = 16 groups
+ * per workgroup.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_mhrec_check_shape(int32_t D);
+int64_t chaorec_mhrec_long_row(void);
+int64_t chaorec_mhrec_chunk(void);
+int64_t chaorec_mhrec_rows_per_block(void);
+/* Forward, X fp32 [N, 64], a fp32 [128] = [a1; a2]:
+ *   Eo[j] = sum_{n in j} X_n (table order), r[j] = <Eo_j, a2>                                       hyperedge launch
+ *   s_n = <X_n, a1>, alpha_nj = exp(s_n + r_j) / (sum_{j of n} exp(s_n + r_j) + 1e-16), out_n = sum_{j of n} alpha_nj Eo_j
+ *   y_n = keep ? 2 (out_n + X_n) : 0                                                               node launch
+ * evaluated with the exponent shifted by the row's maximum, the 1e-16 scaled alike.  stat fp32 [N, 4] =
+ * (-max_j r_j, 1 / denominator, scaled 1e-16 / denominator, s_n) is what the backward re-forms alpha from; a node in no
+ * hyperedge: out_n = 0, stat = (0, 0, 0, s_n).  keep: uint8 [N, 64] given flags, or NULL: with training != 0 element (n, d) is
+ * kept when draw_uniform<24>(key(seed, state[1], salt), n, d) >= 0.5 (state int64 [2] as the step tick keeps it), with
+ * training == 0 there is no dropout and y = out + X.  Sums over a row's entries and the dot products run in double and are
+ * rounded once.  Long rows: pacc double [C, 64], pz double [C, 2] receive the chunks' partials, a further launch adds them in
+ * chunk order.  Two launches, four with long rows; Eo [E, 64], r [E], out and y
+ * [N, 64] are written whole. */
+int chaorec_mhrec_layer_fwd_f32(const int32_t *nodes, int64_t E, int32_t k, const int64_t *rowptr, const int32_t *edge, int64_t N,
+                                const int32_t *long_node, const int64_t *long_cptr, int64_t L, const int32_t *chunk_node,
+                                const int64_t *chunk_beg, int64_t C, const float *X, const float *a, const uint8_t *keep,
+                                uint64_t seed, const int64_t *state, int32_t salt, int32_t training, float *Eo, float *r,
+                                float *stat, float *out, float *y, double *pacc, double *pz, void *stream);
+/* Backward for g = dL/dy fp32 [N, 64] with the forward's Eo, r, stat, out and the same mask / draw arguments:
+ *   gm_n = keep ? 2 g_n : 0, t_n = <gm_n, out_n>                                                    node prologue
+ *   de_nj = alpha_nj (<gm_n, Eo_j> - t_n), dE_j = sum_{n in j} alpha_nj gm_n + a2 sum_{n in j} de_nj  hyperedge launch
+ *   dX_n = gm_n + sum_{j of n} dE_j + a1 sde_n, sde_n = sum_{j of n} de_nj = t_n stat[n][2]                node launch
+ * pa2 fp32 [ceil(E / 16), 64] and pa1 fp32 [ceil(N / 16), 64] receive one partial row per workgroup of
+ * da2 = sum_j Eo_j sum_{n in j} de_nj and da1 = sum_n X_n sde_n: chaorec_colsum_f32 over each gives the gradient of a.
+ * gm [N, 64], tn [N], dE [E, 64] are workspaces written whole, pacc double [C, 64] as in the forward.  Three launches,
+ * five with long rows. */
+int chaorec_mhrec_layer_bwd_f32(const int32_t *nodes, int64_t E, int32_t k, const int64_t *rowptr, const int32_t *edge, int64_t N,
+                                const int32_t *long_node, const int64_t *long_cptr, int64_t L, const int32_t *chunk_node,
+                                const int64_t *chunk_beg, int64_t C, const float *g, const float *X, const float *a,
+                                const float *Eo, const float *r, const float *stat, const float *out, const uint8_t *keep,
+                                uint64_t seed, const int64_t *state, int32_t salt, int32_t training, float *gm, float *tn,
+                                float *dE, float *dX, float *pa1, float *pa2, double *pacc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
