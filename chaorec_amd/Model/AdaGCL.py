@@ -19,7 +19,7 @@ order of the reference's `_indices()`); a generated view is that structure with 
 entry stays in the pattern with the value +0 -- so all 18 propagates of a step share one SpMM schedule.  DenoisingNet's last
 Linear has ONE output: logit[e] = s_nb[row e] + s_self[col e] + b with two per-NODE scores (plain autograd ops on [N, 64]),
 and the gate, the row sums, the degree factors, the values and the l0 term are one autograd node over them
-(ops_extra.adagcl_edge_gate) -- no [E, 64] tensor exists.  vgae.generate's per-edge MLP is ops_extra.adagcl_edge_keep (f32
+(ops.adagcl_edge_gate) -- no [E, 64] tensor exists.  vgae.generate's per-edge MLP is ops.adagcl_edge_keep (f32
 MFMA, the kept count stays on the device).  The uniform draws of the training form come from a counter RNG keyed by a
 device-resident step counter; `feed_draws(randn=, u=)` queues GIVEN draws (parity tests), consumed in call order.
 fused_edges = False runs the reference's lines in plain torch on the same weights and the same structure (the
@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 
 GAMMA, ZETA = -0.45, 1.05
 
@@ -117,7 +117,7 @@ class vgae(nn.Module):
         x, _, _ = self.encoder(data, noise)
         lin1, lin2 = self.decoder.decoder[1], self.decoder.decoder[3]
         if fused:
-            got = ops_extra.adagcl_edge_keep(structure, x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, structure.val,
+            got = ops.adagcl_edge_keep(structure, x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, structure.val,
                                              return_logits=return_parts)
             new_vals, keep = got[0], got[1]
             logits = got[3] if return_parts else None
@@ -215,7 +215,7 @@ class DenoisingNet(nn.Module):
         if self.fused:
             s_nb, s_self, b = self.node_scores(x, layer)
             state, seed = self.owner_state if self.owner_state is not None else (None, 0)
-            out = ops_extra.adagcl_edge_gate(self.adj_mat, s_nb, s_self, b, beta, eps, training, state, seed, layer, u,
+            out = ops.adagcl_edge_gate(self.adj_mat, s_nb, s_self, b, beta, eps, training, state, seed, layer, u,
                                              return_parts=return_parts)
             return (out[0], out[1][0]) + tuple(out[2:])
         val, weight, mask, d = self._plain_values(x, layer, beta, training, eps, u)
@@ -285,7 +285,7 @@ class AdaGCL(nn.Module):
         self.ssl_temp = ssl_temp
         self.ssl_alpha = ssl_alpha
         self.ib_reg = 0.01
-        self._fusable = int(dim_E) == ops_extra.ADAGCL_DIM
+        self._fusable = int(dim_E) == ops.ADAGCL_DIM
 
         self.uEmbeds = nn.Parameter(nn.init.xavier_uniform_(torch.empty(num_user, dim_E)))
         self.iEmbeds = nn.Parameter(nn.init.xavier_uniform_(torch.empty(num_item, dim_E)))
@@ -423,7 +423,7 @@ class AdaGCL(nn.Module):
         self.generator_2.fused = self._fused()
         u = self._take("u", self.n_layers)
         if u is None and self.generator_2.fused:
-            ops_extra.adagcl_tick(self._state)
+            ops.adagcl_tick(self._state)
         loss_2 = self.generator_2(users, pos_items, neg_items, self.ssl_temp, u)
         return loss_1 + loss_2
 

@@ -4,13 +4,13 @@ Same constructor arguments (main.py:381-383), the same Parameters under the same
 (so the same seed gives the same weights), `forward()`, `loss()`, `pre_epoch_processing()`, `topk_sample()`,
 `adaptive_optimization()`, `gene_ranklist()`.  What changed underneath:
   * the user-user co-occurrence graph (`Data/<dataset>/user_graph_dict.npy`) is read when `COHESION.user_graph_path` names an
-    existing file and is otherwise BUILT on the device from the training edges (ops_extra.usergraph_build);
-  * `topk_sample` (:240-271, a Python loop over all users per epoch) is one launch (ops_extra.usergraph_sample); the urn that
+    existing file and is otherwise BUILT on the device from the training edges (ops.usergraph_build);
+  * `topk_sample` (:240-271, a Python loop over all users per epoch) is one launch (ops.usergraph_sample); the urn that
     pads short neighbour lists draws from the library's counter generator, keyed by (torch seed, epoch), not from numpy;
     `set_epoch_graph()` installs a given draw;
   * the tail of the model (:327-359: the [N, 192] concatenation of the three modality tables, user_rep, features[user_graph]
     [U, k, 192], the matmul with the weights, the residual, item_rep + h_i, the final cat) is one autograd node
-    (ops_extra.cohesion_fuse) over the three [N, 64] tables; its backward sums each user's reverse list in chunks of
+    (ops.cohesion_fuse) over the three [N, 64] tables; its backward sums each user's reverse list in chunks of
     `bwd_chunk` entries, so no lane group walks the longest list alone;
   * the item-graph term mm_adj^L item_rep is taken per 64-wide table (column-wise the same product) by `sparse.mm` over the
     kNN graph built as FREEDOM / DRAGON build it (no [I, I] similarity matrix);
@@ -35,7 +35,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 from .DRAGON import DRAGON, User_Graph_sample
 from .LayerGCN import LayerGCN
 
@@ -70,7 +70,7 @@ class GCNLayer(torch.nn.Module):
 class COHESION(nn.Module):
     user_graph_path = None        # Data/<dataset>/user_graph_dict.npy (main.py sets it); missing or None: built on the device
     fused_aggregation = True      # False: the reference's lines in plain torch (tools/bench_cohesion.py, the tests)
-    bwd_chunk = ops_extra.COHESION_CHUNK     # entries of a reverse list one lane group sums in the node's backward; 0: unchunked
+    bwd_chunk = ops.COHESION_CHUNK     # entries of a reverse list one lane group sums in the node's backward; 0: unchunked
 
     def __init__(self, num_user, num_item, edge_index, user_item_dict, v_feat, t_feat, dim_E, reg_weight,
                  dropout, n_layers, mm_layers, ii_topk, mm_image_weight, device):
@@ -93,7 +93,7 @@ class COHESION(nn.Module):
         self.t_feat = t_feat.clone().detach().to(device)
         self.v_rep = self.t_rep = self.id_rep = None
         self.v_preference = self.t_preference = self.id_preference = None
-        self.dim_latent = ops_extra.COHESION_DIM
+        self.dim_latent = ops.COHESION_DIM
 
         self.image_embedding = nn.Embedding.from_pretrained(v_feat.clone().detach(), freeze=False)
         self.text_embedding = nn.Embedding.from_pretrained(t_feat.clone().detach(), freeze=False)
@@ -152,7 +152,7 @@ class COHESION(nn.Module):
 
     # ---- per epoch ------------------------------------------------------------------------------------------------------------
     def topk_sample(self, k):
-        out = ops_extra.usergraph_sample(self.graph_structure, k, self._seed, self._epoch)
+        out = ops.usergraph_sample(self.graph_structure, k, self._seed, self._epoch)
         self._epoch += 1
         return out
 
@@ -163,14 +163,14 @@ class COHESION(nn.Module):
         self.graph_structure.set_epoch(idx, w)
         self.epoch_user_graph, self.user_weight_matrix = self.graph_structure.epoch_idx, self.graph_structure.epoch_w
         if self.fused_aggregation:
-            ops_extra.usergraph_rev_chunks(self.graph_structure, self.bwd_chunk)
+            ops.usergraph_rev_chunks(self.graph_structure, self.bwd_chunk)
 
     def pre_epoch_processing(self):
         """:273-289: this epoch's k neighbours and their weights (and the chunks of their reverse lists), then the pruned
         interaction graph: a degree-sensitive sample without replacement of int(E (1 - dropout)) interactions, renormalised."""
         self.epoch_user_graph, self.user_weight_matrix = self.topk_sample(self.k)
         if self.fused_aggregation:
-            ops_extra.usergraph_rev_chunks(self.graph_structure, self.bwd_chunk)
+            ops.usergraph_rev_chunks(self.graph_structure, self.bwd_chunk)
         if self.dropout <= .0:
             self.masked_adj = self.norm_adj
             return
@@ -202,7 +202,7 @@ class COHESION(nn.Module):
         U = self.num_user
         if self.fused_aggregation:
             h_id, h_v, h_t = self._item_graph(id_rep, False), self._item_graph(v_rep), self._item_graph(t_rep)
-            return ops_extra.cohesion_fuse(id_rep, v_rep, t_rep, h_id, h_v, h_t, self.graph_structure, U, self.bwd_chunk)
+            return ops.cohesion_fuse(id_rep, v_rep, t_rep, h_id, h_v, h_t, self.graph_structure, U, self.bwd_chunk)
         # :340-359 as written
         representation = torch.cat((id_rep, v_rep, t_rep), dim=1)
         user_rep = representation[:U]

@@ -5,10 +5,10 @@ the same seed gives the same weights), `forward()`, `loss()`, `pre_epoch_process
 underneath:
   * the user-user co-occurrence graph (`Data/<dataset>/user_graph_dict.npy`, which dualgnn-gen-u-u-matrix.py makes from a dense
     [U, U] matrix) is read when `DRAGON.user_graph_path` names an existing file and is otherwise BUILT on the device from the
-    training edges (ops_extra.usergraph_build: no [U, U] buffer);
-  * `topk_sample` (:231-270, a Python loop over all users per epoch) is one launch (ops_extra.usergraph_sample); the urn that
+    training edges (ops.usergraph_build: no [U, U] buffer);
+  * `topk_sample` (:231-270, a Python loop over all users per epoch) is one launch (ops.usergraph_sample); the urn that
     pads short neighbour lists draws from the library's counter generator, keyed by (torch seed, epoch), not from numpy;
-  * `User_Graph_sample.forward` and the lines around it (:289-302) are one autograd node (ops_extra.usergraph_aggregate):
+  * `User_Graph_sample.forward` and the lines around it (:289-302) are one autograd node (ops.usergraph_aggregate):
     neither user_rep, nor features[user_graph] [U, k, 2 D], nor h_u exists in memory, forward or backward;
   * the two GCNConv propagates per modality are the ordered SpMM over one shared normalised CSR, the item-item layers
     `sparse.mm` over the kNN graph built as FREEDOM builds it (no [I, I] similarity matrix), the Linears `ops.linear`, the BPR
@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import graph, ops, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 from ..BasicGCN import GCNConv, _sym_norm_csr
 
 
@@ -86,8 +86,8 @@ class DRAGON(torch.nn.Module):
         self.user_aggr_mode = 'softmax'
         self.n_layers = n_layers
         self.mm_image_weight = mm_image_weight
-        if dim_E not in ops_extra.USERGRAPH_DIMS:
-            raise ValueError(f"DRAGON: dim_E = {dim_E}, the aggregation kernels are built for {ops_extra.USERGRAPH_DIMS}")
+        if dim_E not in ops.USERGRAPH_DIMS:
+            raise ValueError(f"DRAGON: dim_E = {dim_E}, the aggregation kernels are built for {ops.USERGRAPH_DIMS}")
 
         self.MLP_v = nn.Linear(self.dim_latent, self.dim_latent, bias=False)
         self.MLP_t = nn.Linear(self.dim_latent, self.dim_latent, bias=False)
@@ -139,9 +139,9 @@ class DRAGON(torch.nn.Module):
         path = type(self).user_graph_path
         if path and os.path.exists(path):
             self.user_graph_dict = np.load(path, allow_pickle=True).item()
-            return ops_extra.UserGraphStructure.from_dict(self.user_graph_dict, self.num_user, device=self.device)
+            return ops.UserGraphStructure.from_dict(self.user_graph_dict, self.num_user, device=self.device)
         rowptr, col = self.hist
-        return ops_extra.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
+        return ops.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
 
     def get_knn_adj_mat(self, mm_embeddings, name=None):
         """Model/DRAGON.py:204-225 (the code of Model/FREEDOM.py:111-138): cosine kNN, the row itself among them, then
@@ -168,7 +168,7 @@ class DRAGON(torch.nn.Module):
         self.epoch_user_graph, self.user_weight_matrix = self.topk_sample(self.user_topk)
 
     def topk_sample(self, k):
-        out = ops_extra.usergraph_sample(self.graph_structure, k, self._seed, self._epoch)
+        out = ops.usergraph_sample(self.graph_structure, k, self._seed, self._epoch)
         self._epoch += 1
         return out
 
@@ -187,7 +187,7 @@ class DRAGON(torch.nn.Module):
         item_rep = torch.cat((self.v_rep[U:], self.t_rep[U:]), dim=1)
 
         if self.fused_aggregation:
-            user_rep = ops_extra.usergraph_aggregate(self.v_rep[:U], self.t_rep[:U], self.weight_u, self.graph_structure)
+            user_rep = ops.usergraph_aggregate(self.v_rep[:U], self.t_rep[:U], self.weight_u, self.graph_structure)
         else:   # :289-302 as written
             user_rep = torch.cat((self.v_rep[:U].unsqueeze(2), self.t_rep[:U].unsqueeze(2)), dim=2)
             user_rep = self.weight_u.transpose(1, 2) * user_rep

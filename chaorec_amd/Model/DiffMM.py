@@ -14,9 +14,9 @@ Kept as written, on purpose:
 
 What changed underneath.  The graph half (forward_MM, forward_cl_MM) is nine SpMMs through sparse.mm.  The diffusion half:
 no dense [U, I] interaction matrix exists; `diffusion_step(users)` writes the noised, dropped-out rows of a batch straight
-from the history CSR in one launch (ops_extra.diffmm_rows), runs the in-layer on the MFMA GEMMs with the time embedding as a
+from the history CSR in one launch (ops.diffmm_rows), runs the in-layer on the MFMA GEMMs with the time embedding as a
 second, 10-wide product (no concatenation), and the out-layer, both losses and d loss / d out in one pass
-(ops_extra.diffmm_denoise_loss): model_output never exists.  `rebuild_graphs(loader)` runs the five posterior-mean steps per
+(ops.diffmm_denoise_loss): model_output never exists.  `rebuild_graphs(loader)` runs the five posterior-mean steps per
 batch on the device, takes the top-rebuild_k with chaorec_macrid_topk_f32 and restates buildUIMatrix / edgeDropper as tensor
 operations on the device (the reference makes 2 U rebuild_k single-element host round trips and goes through scipy).
 fused_denoise = False runs the reference's own lines in plain torch on the device (the measurements' other side).
@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 from ..ops_dense import gemm_raw, gemm_tn_bf16x3, _linear_fwd_raw
 
 
@@ -452,7 +452,7 @@ class DiffMM(nn.Module):
     def batch_rows(self, users):
         """The multi-hot rows [B, I] of a batch of users, from the history CSR (dataload.DiffusionData's rows; no [U, I])."""
         if self.hist[0].is_cuda:
-            return ops_extra.diffmm_rows(users, self.hist[0], self.hist[1], self.num_item, plain=True)[0]
+            return ops.diffmm_rows(users, self.hist[0], self.hist[1], self.num_item, plain=True)[0]
         rowptr, col = self.hist
         n = rowptr[users + 1] - rowptr[users]
         rows = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), n)
@@ -469,7 +469,7 @@ class DiffMM(nn.Module):
         B, I, dm = users.numel(), self.num_item, self.diffusion_model
         iEmbeds = self.getItemEmbeds().detach()
         feats = (self.getImageFeats().detach(), self.getTextFeats().detach())
-        fused = self.fused_denoise and int(self.dim_E) == ops_extra.DIFFMM_D
+        fused = self.fused_denoise and int(self.dim_E) == ops.DIFFMM_D
         self._step += 1
         if fused:
             x0E = ops.spmm_raw(self._hist_csr, iEmbeds.contiguous())[users].contiguous()
@@ -483,10 +483,10 @@ class DiffMM(nn.Module):
             if fused:
                 a = dm.sqrt_alphas_cumprod[t].float().contiguous()
                 s = dm.sqrt_one_minus_alphas_cumprod[t].float().contiguous()
-                x_in, bits = ops_extra.diffmm_rows(users, self.hist[0], self.hist[1], I, a, s, n_m, k_m, self.seed, self._step, salt=m)
+                x_in, bits = ops.diffmm_rows(users, self.hist[0], self.hist[1], I, a, s, n_m, k_m, self.seed, self._step, salt=m)
                 h = dn.hidden(x_in, t)
                 out = dn.out_layers[0]
-                loss, diff_rows, gc_rows = ops_extra.diffmm_denoise_loss(h, out.weight, out.bias, bits, x0E, feat.contiguous(),
+                loss, diff_rows, gc_rows = ops.diffmm_denoise_loss(h, out.weight, out.bias, bits, x0E, feat.contiguous(),
                                                                          dm.weight(t), self.e_loss)
                 loss = loss.reshape(())
             else:
@@ -504,7 +504,7 @@ class DiffMM(nn.Module):
         x = self.batch_rows(users)
         if self.fused_denoise and x.is_cuda:
             x_t = dm.p_sample(lambda xx, t, _drop: dn.denoise(xx, t), x, 0, False).contiguous()
-            return ops_extra.macrid_topk(x_t, self.rebuild_k)[0], x_t
+            return ops.rows_topk(x_t, self.rebuild_k)[0], x_t
         x_t = dm.p_sample(dn, x, 0, False)
         return torch.topk(x_t, k=self.rebuild_k)[1], x_t
 

@@ -4,12 +4,12 @@ Same constructor arguments (main.py:280), the same Parameters under the same sta
 the same seed gives the same weights), `forward()`, `loss()`, `bpr_loss()`, `regularization_loss()`, `pre_epoch_processing()`,
 `topk_sample()`, `init_weight()`, `gene_ranklist()`.  What changed underneath:
   * the user-user co-occurrence graph (`Data/<dataset>/user_graph_dict.npy`) is read when `DualGNN.user_graph_path` names an
-    existing file and is otherwise BUILT on the device from the training edges (ops_extra.usergraph_build);
-  * `topk_sample` (:319-358, a Python loop over all users per epoch) is one launch (ops_extra.usergraph_sample); the urn that
+    existing file and is otherwise BUILT on the device from the training edges (ops.usergraph_build);
+  * `topk_sample` (:319-358, a Python loop over all users per epoch) is one launch (ops.usergraph_sample); the urn that
     pads short neighbour lists draws from the library's counter generator, keyed by (torch seed, epoch), not from numpy;
     `set_epoch_graph()` installs a given draw;
   * everything after the two modality encoders (:189-239: representation, the weighted sum, User_Graph_sample.forward, the
-    residual, the final cat) is one autograd node (ops_extra.dualgnn_fuse): none of cat(v_rep[:U], t_rep[:U]) [U, D, 2],
+    residual, the final cat) is one autograd node (ops.dualgnn_fuse): none of cat(v_rep[:U], t_rep[:U]) [U, D, 2],
     user_rep, features[user_graph] [U, k, D], h_u1 or representation exists in memory, forward or backward;
   * the two propagates per modality are the ordered SpMM over one shared normalised CSR, the Linears `ops.linear`, the BPR
     term the fused BPR kernel, the ranking `ranking.gene_ranklist`.
@@ -35,7 +35,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import ops, ops_extra, ranking
+from .. import ops, ranking
 from ..BasicGCN import GCNConv, _sym_norm_csr
 from .DRAGON import User_Graph_sample  # (Model/DualGNN.py:95-110 is the same class: the plain-torch gather + matmul)
 
@@ -79,8 +79,8 @@ class DualGNN(torch.nn.Module):
         self.device = device
         self.dim_latent, self.dim_feat = dim_E, feature_embedding
         self.user_aggr_mode = 'softmax'
-        if dim_E not in ops_extra.USERGRAPH_DIMS:
-            raise ValueError(f"DualGNN: dim_E = {dim_E}, the aggregation kernels are built for {ops_extra.USERGRAPH_DIMS}")
+        if dim_E not in ops.USERGRAPH_DIMS:
+            raise ValueError(f"DualGNN: dim_E = {dim_E}, the aggregation kernels are built for {ops.USERGRAPH_DIMS}")
         if feature_embedding != dim_E:
             raise ValueError(f"DualGNN: feature_embedding = {feature_embedding} but dim_E = {dim_E}: the [U, feature_embedding] "
                              "preference rows are concatenated with [I, dim_E] item rows, so the two must be equal")
@@ -123,9 +123,9 @@ class DualGNN(torch.nn.Module):
         path = type(self).user_graph_path
         if path and os.path.exists(path):
             self.user_graph_dict = np.load(path, allow_pickle=True).item()
-            return ops_extra.UserGraphStructure.from_dict(self.user_graph_dict, self.num_user, device=self.device)
+            return ops.UserGraphStructure.from_dict(self.user_graph_dict, self.num_user, device=self.device)
         rowptr, col = self.hist
-        return ops_extra.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
+        return ops.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
 
     def pre_epoch_processing(self):
         """:315-317: this epoch's k neighbours and their weights, written into the structure's fixed buffers."""
@@ -133,7 +133,7 @@ class DualGNN(torch.nn.Module):
 
     def topk_sample(self, k):
         s = self.graph_structure
-        idx, w = ops_extra.usergraph_sample(s, k, self._seed, self._epoch)
+        idx, w = ops.usergraph_sample(s, k, self._seed, self._epoch)
         self._epoch += 1
         if self.user_aggr_mode == 'mean':       # 1 / k wherever the user has a neighbour; the rows without stay zero
             w.copy_((s.nbr_len > 0).to(torch.float32).unsqueeze(1) * (torch.ones(k, device=w.device) / k))
@@ -156,7 +156,7 @@ class DualGNN(torch.nn.Module):
             if self.construction != 'weighted_sum':
                 raise ValueError(f"DualGNN: construction = '{self.construction}' exists on the plain-torch path only "
                                  "(fused_aggregation = False)")
-            self.result = ops_extra.dualgnn_fuse(self.v_rep, self.t_rep, self.weight_u, self.graph_structure, U)
+            self.result = ops.dualgnn_fuse(self.v_rep, self.t_rep, self.weight_u, self.graph_structure, U)
             return self.result
 
         # :189-239 as written

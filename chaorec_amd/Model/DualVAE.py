@@ -242,7 +242,7 @@ class DualVAE(nn.Module):
                 zu = self.mu_theta[u0:u1].contiguous()
                 zh = torch.tanh(ops.linear(zu.view((u1 - u0) * A, K), dec_u.weight, dec_u.bias)).view(u1 - u0, A, 20)
                 sc = ops.dualvae_scores(zu, zh, self.mu_beta, th, aspect_prob, u0, self.hist, 1e-6, out=staging[:u1 - u0])
-                out[u0:u1], _ = ops.macrid_topk(sc, topk, id_offset=U)
+                out[u0:u1], _ = ops.rows_topk(sc, topk, id_offset=U)
         return ranking._to_host(out) if to_cpu else out
 
     full_sort_predict = gene_ranklist

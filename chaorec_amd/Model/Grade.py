@@ -25,7 +25,7 @@ order of the reference's `_indices()`); a generated view is that structure with 
 entry stays in the pattern with the value +0 -- so every propagate of a step shares one SpMM schedule.  vgae.generate keeps
 the PROBABILITY as a kept entry's value and renormalises by the weighted row sums, d = (S + 1e-7)^-1/2, val = d[row] p d[col];
 the reference sends that through scipy on the host, three times per step.  Here loss_1 runs the three encoders in the
-reference's order (so the randn draws are consumed in that order), stacks their z and makes ONE ops_extra.grade_views call:
+reference's order (so the randn draws are consumed in that order), stacks their z and makes ONE ops.grade_views call:
 the MLP per undirected pair (f32 MFMA), the row sums and the values, three launches for the three generators, nothing on the
 host.  image_trs(v_feat) and text_trs(t_feat) are `ops.linear`, computed once per loss call and reused where the reference
 recomputes them with unchanged weights (same value, same summed gradient).  Noise stays torch.randn / torch.rand on the
@@ -37,7 +37,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 
 
 class vgae_encoder(nn.Module):
@@ -131,7 +131,7 @@ class vgae(nn.Module):
         return_parts: also (keep bool [E], logits [E], d [N])."""
         x, _, _ = self.encoder(data, noise)
         if fused:
-            got = ops_extra.grade_views(structure, x, *self.mlp(), return_parts=return_parts)
+            got = ops.grade_views(structure, x, *self.mlp(), return_parts=return_parts)
             val = got[0][0] if return_parts else got[0]
             view = sparse.DroppedAdj(structure, val, val[structure.transpose_entry.long()])
             return (view, got[1][0], got[3][0], got[4][0]) if return_parts else view
@@ -190,7 +190,7 @@ class Grade(nn.Module):
         self.mm_image_weight = 0.5
         self.mm_layers = 1
         self.noise_alpha = noise_alpha
-        self._fusable = int(dim_E) == ops_extra.GRADE_DIM
+        self._fusable = int(dim_E) == ops.GRADE_DIM
 
         self.uEmbeds = nn.Embedding(self.num_user, self.dim_E)
         nn.init.xavier_uniform_(self.uEmbeds.weight)
@@ -218,7 +218,7 @@ class Grade(nn.Module):
         e = torch.as_tensor(edge_index).long()
         csr = graph.binary_sym_norm_csr(e[:, 0], e[:, 1] - num_user, num_user, num_item)
         self.norm_adj_mat = sparse._dropout_structure(csr).to(device)       # Model/Grade.py:248-288, and the entry maps
-        ops_extra.grade_pair_owner(self.norm_adj_mat)                       # the owner list, once, cached on the structure
+        ops.grade_pair_owner(self.norm_adj_mat)                       # the owner list, once, cached on the structure
 
         encoder = vgae_encoder(self.dim_E, self.device, self.forward_graphcl)
         decoder = vgae_decoder(self.dim_E, self.device, num_user, num_item, reg_weight)
@@ -325,7 +325,7 @@ class Grade(nn.Module):
 
     def generate_views(self, return_parts=False):
         """The three generate calls of loss_1 in the reference's order -> three sparse.DroppedAdj.  Fused: the encoders run one
-        after the other (the randn draws in the reference's order), their z stacked into ONE ops_extra.grade_views call.
+        after the other (the randn draws in the reference's order), their z stacked into ONE ops.grade_views call.
         return_parts: also the node's (keep [3, E], kept [3], logits [3, E], d [3, N])."""
         gens = (self.generator_1, self.generator_2, self.generator_3)
         st = self.norm_adj_mat
@@ -339,7 +339,7 @@ class Grade(nn.Module):
             z = torch.stack([g.encoder(st, self._take("randn"))[0] for g in gens])
             mlps = [g.mlp() for g in gens]
             W1, b1, w2, b2 = (torch.stack([m[k].reshape(-1) for m in mlps]) for k in range(4))
-            got = ops_extra.grade_views(st, z, W1.reshape(3, self.dim_E, self.dim_E), b1, w2, b2.reshape(-1), return_parts=return_parts)
+            got = ops.grade_views(st, z, W1.reshape(3, self.dim_E, self.dim_E), b1, w2, b2.reshape(-1), return_parts=return_parts)
         val = got[0] if return_parts else got
         views = [sparse.DroppedAdj(st, val[g], val[g]) for g in range(3)]       # val[tentry] == val bit for bit: pairs decided once
         return (views, tuple(got[1:])) if return_parts else views

@@ -16,12 +16,12 @@ Kept as written, on purpose:
 
 What changed underneath.  The graph is ONE graph.DropoutStructure over D^-1/2 A D^-1/2 (row-major, columns ascending: the
 order of the reference's `_indices()`); a view is that structure with the sampled values (sparse.DroppedAdj) PLUS the step's
-random entries as a small CSR with its transpose (ops_extra.RandEntries, sorted on the device, no host synchronisation): a
+random entries as a small CSR with its transpose (ops.RandEntries, sorted on the device, no host synchronisation): a
 view's GCN layer is LeakyReLU(sparse.mm(view, x) + 0.05 R x) -- no E-sized coalesce per step.  MixHop's three upper and three
 bottom linears are one GEMM each (concatenated weights).  MixHopNetwork.forward returns no log_softmax (nothing reads it).
-fused_edges: the sampler is ops_extra.graphaug_edge_sample over P = z W1[:, :64]^T and Q = z W1[:, 64:]^T (two N-sized GEMMs
+fused_edges: the sampler is ops.graphaug_edge_sample over P = z W1[:, :64]^T and Q = z W1[:, 64:]^T (two N-sized GEMMs
 in place of the E-sized one); False: the reference's lines in plain torch over gathered [E, 128] rows.  fused_contrast: the
-denominator log sum_m exp(<p1_b, e2_m> / T) is ops_extra.graphaug_lse (no [B, M] matrix); False: the reference's lines.
+denominator log sum_m exp(<p1_b, e2_m> / T) is ops.graphaug_lse (no [B, M] matrix); False: the reference's lines.
 `feed_draws` queues GIVEN draws (parity tests), consumed in call order; without them the fused sampler draws in its launch,
 keyed by a device-resident step counter, and everything else draws from torch on the device.
 """
@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 
 N_RANDOM = 100000
 RANDOM_VALUE = 0.05
@@ -65,7 +65,7 @@ class GCNLayer(nn.Module):
     def forward(self, adj, embeds):
         """Model/GraphAug.py:55-71: act(adj x); a view's random entries are a second, small product."""
         if isinstance(adj, GraphAugView):
-            return ops_extra.graphaug_rand_layer(sparse.mm(adj.dropped, embeds), embeds, adj.rand, RANDOM_VALUE, self.leaky)
+            return ops.graphaug_rand_layer(sparse.mm(adj.dropped, embeds), embeds, adj.rand, RANDOM_VALUE, self.leaky)
         return self.act(sparse.mm(adj, embeds))
 
 
@@ -227,7 +227,7 @@ class ViewLearner(torch.nn.Module):
         if fused:
             d = z.shape[1]
             P, Q = z @ lin1.weight[:, :d].t(), z @ lin1.weight[:, d:].t()
-            val, val_t, logits, draws = ops_extra.graphaug_edge_sample(structure, P, Q, lin1.bias, lin2.weight, lin2.bias, u1, u2, state, seed,
+            val, val_t, logits, draws = ops.graphaug_edge_sample(structure, P, Q, lin1.bias, lin2.weight, lin2.bias, u1, u2, state, seed,
                                                                        salt, True, return_parts, return_parts)
         else:
             with torch.no_grad():
@@ -310,8 +310,8 @@ class GraphAug(nn.Module):
         return out
 
     def _fusable(self, flag, what):
-        if flag and int(self.dim_E) != ops_extra.GRAPHAUG_DIM:
-            raise ValueError(f"GraphAug: {what} tiles dim_E = {ops_extra.GRAPHAUG_DIM}, not {self.dim_E} (the reference's own "
+        if flag and int(self.dim_E) != ops.GRAPHAUG_DIM:
+            raise ValueError(f"GraphAug: {what} tiles dim_E = {ops.GRAPHAUG_DIM}, not {self.dim_E} (the reference's own "
                              f"shapes line up at 64 only)")
         return bool(flag)
 
@@ -381,7 +381,7 @@ class GraphAug(nn.Module):
         pckEmbeds2 = embeds2[nodes]
         if self._fusable(self.fused_contrast, "the log-sum-exp node"):
             pos = torch.sum(pckEmbeds1 * pckEmbeds2, dim=-1) / temp
-            return (ops_extra.graphaug_lse(pckEmbeds1, embeds2, 1.0 / temp) - pos).mean()
+            return (ops.graphaug_lse(pckEmbeds1, embeds2, 1.0 / temp) - pos).mean()
         nume = torch.exp(torch.sum(pckEmbeds1 * pckEmbeds2, dim=-1) / temp)
         deno = torch.exp(pckEmbeds1 @ embeds2.T / temp).sum(-1)
         return -torch.log(nume / deno).mean()
@@ -402,7 +402,7 @@ class GraphAug(nn.Module):
         else:
             rdmUsrs = torch.randint(self.num_user, [N_RANDOM], device=self.device)
             rdmItms1 = torch.randint_like(rdmUsrs, self.num_item)
-        rand = ops_extra.RandEntries(rdmUsrs, rdmItms1, st.n_rows)          # built once, shared by both views
+        rand = ops.RandEntries(rdmUsrs, rdmItms1, st.n_rows)          # built once, shared by both views
 
         node_embs = []
         ticked = False
@@ -411,7 +411,7 @@ class GraphAug(nn.Module):
             draws = dict(u1=u1[0], u2=u2[0]) if (u1 is not None and u2 is not None) else {}
             if fused and not draws:
                 if not ticked:
-                    ops_extra.step_tick(self._state)
+                    ops.step_tick(self._state)
                     ticked = True
                 draws = dict(state=self._state, seed=self.seed, salt=j)
             ant_node, ant_adj = self.view_learner(ofea, st, st, fused, masks, **draws)

@@ -15,15 +15,15 @@ Kept as written, on purpose:
 Departure: a denoiser's training step (not the rebuild's p_sample) is evaluated in float64 on the fp32 weights by default
 (`diffusion_double`): its weight gradients cancel about 1000 : 1 over the batch and Adam normalises the remainder.
 
-What changed underneath.  A rebuilt hypergraph is an ops_extra.HyperGraph (an ELL table of the top-k nodes and the node CSR,
+What changed underneath.  A rebuilt hypergraph is an ops.HyperGraph (an ELL table of the top-k nodes and the node CSR,
 built on the device), never a torch sparse tensor; a hypergraph layer with the residual and the dropout after it is ONE
-autograd node (ops_extra.mhrec_hyper_layer); fused_hyper = False runs the reference's lines in plain torch on the same
+autograd node (ops.mhrec_hyper_layer); fused_hyper = False runs the reference's lines in plain torch on the same
 HyperGraph.  The input hyperedges ([u] + similar users + [i] + similar items per interaction) are an int32 [E, width] table
 in HBM, read from hyperedges_*_u{}_i{}.npy under `MHRec.data_dir` or built on the device from the user co-occurrence graph
 and the item kNN; the dense [E, N] matrix of the reference's HyperDiffusionData is never formed: `diffusion_rows(batch)`
 scatter-adds a batch's rows (a hyperedge may name a node twice -- padded neighbours, the [0] * k placeholder -- and the
 reference's coo.toarray() sums those: the rows hold counts).  gcnLayers go through sparse.mm; the four contrastLoss
-denominators through ops_extra.graphaug_lse, the + 1e-8 added afterwards.  `feed_draws` queues GIVEN dropout masks (parity
+denominators through ops.graphaug_lse, the + 1e-8 added afterwards.  `feed_draws` queues GIVEN dropout masks (parity
 tests, the diffusion half's draws too), consumed in call order; without them the fused layer draws in its launch, keyed by a device-resident step counter.
 """
 import os
@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops, ops_extra, ranking, sparse
+from .. import graph, ops, ranking, sparse
 from .DiffMM import Denoise, GaussianDiffusion, _ModalMix
 
 
@@ -61,11 +61,11 @@ class HypergraphAttentionLayer(nn.Module):
         nn.init.xavier_uniform_(self.a)
 
     def forward(self, H, X, fused=True, keep=None, state=None, seed=0, salt=0):
-        """Model/MHRec.py:53-89 over an ops_extra.HyperGraph, WITH the two lines the model puts after it (:725-726):
+        """Model/MHRec.py:53-89 over an ops.HyperGraph, WITH the two lines the model puts after it (:725-726):
         -> dropout_0.5(layer(H, X) + X)."""
         if fused:
-            return ops_extra.mhrec_hyper_layer(H, X, self.a, keep, state, seed, salt, True)
-        return ops_extra.mhrec_hyper_layer_torch(H, X, self.a, keep, True)
+            return ops.mhrec_hyper_layer(H, X, self.a, keep, state, seed, salt, True)
+        return ops.mhrec_hyper_layer_torch(H, X, self.a, keep, True)
 
 
 class MHRec(nn.Module):
@@ -170,14 +170,14 @@ class MHRec(nn.Module):
 
     def topk_sample(self, k):
         """Model/MHRec.py:645-669 -> int32 [U, k] on the device: a user's first k co-occurring users, a shorter list padded with
-        repeats of its own members, [0] * k for a user without any (ops_extra.usergraph_sample, one launch)."""
+        repeats of its own members, [0] * k for a user without any (ops.usergraph_sample, one launch)."""
         path = self._file('user_graph_dict.npy')
         if path and os.path.exists(path):
-            s = ops_extra.UserGraphStructure.from_dict(np.load(path, allow_pickle=True).item(), self.num_user, device=self.device)
+            s = ops.UserGraphStructure.from_dict(np.load(path, allow_pickle=True).item(), self.num_user, device=self.device)
         else:
             rowptr, col = self.hist
-            s = ops_extra.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
-        return ops_extra.usergraph_sample(s, k, self.seed, 0)[0]
+            s = ops.usergraph_build(rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), self.num_item)
+        return ops.usergraph_sample(s, k, self.seed, 0)[0]
 
     def pre_processing(self):
         """The two int32 [E, 2 + uu_topk + ii_topk] tables, one row per training interaction: read from the reference's files
@@ -261,12 +261,12 @@ class MHRec(nn.Module):
         return torch.mean(torch.stack(lst), dim=0)
 
     def forward(self):
-        """Model/MHRec.py:708-779 over self.G_visual / self.G_textual (ops_extra.HyperGraph)."""
+        """Model/MHRec.py:708-779 over self.G_visual / self.G_textual (ops.HyperGraph)."""
         fused = bool(self.fused_hyper)
         if fused:
-            ops_extra.mhrec_check_shape(self.dim_E)
+            ops.mhrec_check_shape(self.dim_E)
             if not self._draws["keep"]:
-                ops_extra.step_tick(self._state)
+                ops.step_tick(self._state)
         v_embedding = self.getImageFeats()
         t_embedding = self.getTextFeats()
         weight = self.softmax(self.modal_weight)
@@ -291,9 +291,9 @@ class MHRec(nn.Module):
         embeds2 = F.normalize(embeds2, p=2)
         pckEmbeds1 = embeds1[nodes]
         pckEmbeds2 = embeds2[nodes]
-        if self.fused_contrast and int(self.dim_E) == ops_extra.GRAPHAUG_DIM and pckEmbeds1.is_cuda:
+        if self.fused_contrast and int(self.dim_E) == ops.GRAPHAUG_DIM and pckEmbeds1.is_cuda:
             pos = torch.sum(pckEmbeds1 * pckEmbeds2, dim=-1) / self.ssl_temp
-            deno = torch.exp(ops_extra.graphaug_lse(pckEmbeds1, embeds2, 1.0 / self.ssl_temp)) + 1e-8
+            deno = torch.exp(ops.graphaug_lse(pckEmbeds1, embeds2, 1.0 / self.ssl_temp)) + 1e-8
             return (torch.log(deno) - pos).mean()
         nume = torch.exp(torch.sum(pckEmbeds1 * pckEmbeds2, dim=-1) / self.ssl_temp)
         deno = torch.exp(pckEmbeds1 @ embeds2.T / self.ssl_temp).sum(-1) + 1e-8
@@ -404,11 +404,11 @@ class MHRec(nn.Module):
 
     def rebuild_hypergraphs(self, loader_visual, loader_textual=None, noise=None):
         """train_and_evaluate.py:394-497: per modality, every batch's denoised top-k in loader order (hyperedge j = the j-th row
-        the loader handed out) -> (G_visual, G_textual) as ops_extra.HyperGraph.  noise: a pair of lists of given q_sample
+        the loader handed out) -> (G_visual, G_textual) as ops.HyperGraph.  noise: a pair of lists of given q_sample
         noise, one per batch."""
         out = []
         with torch.no_grad():
             for m, loader in enumerate((loader_visual, loader_textual if loader_textual is not None else loader_visual)):
                 nodes = [self.denoised_topk(batch, m, None if noise is None else noise[m][b])[0] for b, batch in enumerate(loader)]
-                out.append(ops_extra.HyperGraph(torch.cat(nodes), self.num_user + self.num_item, validate=False))
+                out.append(ops.HyperGraph(torch.cat(nodes), self.num_user + self.num_item, validate=False))
         return out[0], out[1]

@@ -15,8 +15,8 @@ Kept as written, on purpose:
     entries at the value 1e-6.
 
 What changed underneath.  A convolution is x W on the MFMA GEMM, one CSR SpMM over D^-1/2 (A + I) D^-1/2 built once, and
-ONE launch for leaky_relu(dropout(normalize(. + bias))) (ops_extra.mvgae_conv_tail).  The tail -- two products of experts,
-four reparametrisations, four KL and four BPR terms -- is one autograd node (ops_extra.mvgae_tail): the noise is drawn only
+ONE launch for leaky_relu(dropout(normalize(. + bias))) (ops.mvgae_conv_tail).  The tail -- two products of experts,
+four reparametrisations, four KL and four BPR terms -- is one autograd node (ops.mvgae_tail): the noise is drawn only
 for the 3B rows the batch names, keyed by the table row, and the stacked [2, N, D] tables never exist.  Dropout masks and
 noise come from a counter RNG keyed by a device-resident step counter, so a captured step draws fresh values at every
 replay.  `loss(..., keep=, eps=)` takes GIVEN draws (parity tests).  fused_conv / fused_tail = False run the reference's
@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import graph, ops, ops_extra, ranking
+from .. import graph, ops, ranking
 
 EPS = 1e-15
 MAX_LOGVAR = 10
@@ -62,7 +62,7 @@ class BaseModel(nn.Module):
         """-> leaky_relu(update(A (x W))); owner: the MVGAE that holds the flags, the seed and the step counter."""
         s = ops.spmm(csr, ops.linear(x, self.weight.t()))
         if owner.fused_conv and owner._fusable:
-            return ops_extra.mvgae_conv_tail(s, self.bias, owner._state, owner.seed, salt, self.training, keep)
+            return ops.mvgae_conv_tail(s, self.bias, owner._state, owner.seed, salt, self.training, keep)
         y = F.normalize(s + self.bias, p=2, dim=-1)
         if self.training and keep is not None:
             y = y * (keep.to(y.dtype) * (1.0 / 0.9))
@@ -148,7 +148,7 @@ class MVGAE(nn.Module):
         self.n_layers = n_layers
         self.aggr_mode = 'add'
         self.concate = False
-        self._fusable = int(dim_E) == ops_extra.MVGAE_DIM
+        self._fusable = int(dim_E) == ops.MVGAE_DIM
 
         self.register_buffer("collaborative", nn.init.xavier_normal_(torch.rand((self.num_item, self.dim_E))), persistent=False)
         self.graph = graph.basicgcn_csr(edge_index, num_user + num_item).to(device)
@@ -262,12 +262,12 @@ class MVGAE(nn.Module):
         stands THEN: call backward() before the next loss() (an evaluation-mode one included), as every training loop
         here does -- otherwise the backward differentiates other masks and noise than its forward drew."""
         users, pos, neg = (t.to(self.device).to(torch.int64) for t in (users, pos_items, neg_items))
-        ops_extra.mvgae_tick(self._state)
+        ops.mvgae_tick(self._state)
         tables = self._tables(keep)
         if self.fused_tail and self._fusable:
             if eps is not None:
                 eps = torch.as_tensor(eps).to(self.device).float().contiguous()
-            total, parts, pd_mu = ops_extra.mvgae_tail(*tables, users, pos, neg, self.kl_weight, self._state, self.seed,
+            total, parts, pd_mu = ops.mvgae_tail(*tables, users, pos, neg, self.kl_weight, self._state, self.seed,
                                                        self.training, eps, row_ids=self._row_ids)
         else:
             total, parts, pd_mu = self._plain_tail(tables, users, pos, neg, eps)

@@ -186,7 +186,7 @@ class MacridVAE(nn.Module):
                 zh, _, _ = self.forward(users)
                 sc = ops.macrid_scores(zh.contiguous(), self.last["items"], self.last["cates"], self.tau, u0, self.hist, 1e-6,
                                        out=staging[:u1 - u0])
-                out[u0:u1], _ = ops.macrid_topk(sc, topk, id_offset=U)
+                out[u0:u1], _ = ops.rows_topk(sc, topk, id_offset=U)
         return ranking._to_host(out) if to_cpu else out
 
     full_sort_predict = gene_ranklist

@@ -29,7 +29,7 @@ _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_
 # exports whose `int` result the caller reads; every other `int` result is a status that load() checks
 INT_VALUE_EXPORTS = {"chaorec_abi_version", "chaorec_spmm_rows_per_wave", "chaorec_spmm_long_threshold",
                      "chaorec_adam_lowrank_strips", "chaorec_adam_multi_max",
-                     "chaorec_dgcf_check_shape"}   # a status, turned into a ValueError by ops_extra.dgcf_check_shape
+                     "chaorec_dgcf_check_shape"}   # a status, turned into a ValueError by ops_dgcf.dgcf_check_shape
 
 
 def _ctype(decl, name, is_return=False):

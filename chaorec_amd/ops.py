@@ -48,6 +48,45 @@ def _f32rows(t):
     return t.contiguous()
 
 
+def _typed(model, t, what, dtype, shape=None):
+    """`t` if it is a contiguous tensor of `dtype` (and of `shape`, when given); else ValueError naming the model's operand."""
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{model}: {what} must be a contiguous {str(dtype)[len('torch.'):]} tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{model}: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _f32(model, t, what, shape=None):
+    return _typed(model, t, what, torch.float32, shape)
+
+
+def _i32(model, t, what, shape=None):
+    return _typed(model, t, what, torch.int32, shape)
+
+
+def _empty_f32(device):
+    """f(*shape): an uninitialised fp32 tensor of that shape on `device` (a wrapper's outputs and scratch)."""
+    def f(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    return f
+
+
+def _check_dim(model, D, tiled):
+    """The models whose kernels are instantiated for one row width."""
+    if int(D) != tiled:
+        raise ValueError(f"{model}: dim_E={D}; the kernels tile D={tiled}")
+
+
+def step_tick(state, export="chaorec_adagcl_tick"):
+    """state int64 [2] on the device: [0] += 1, [1] = [0] -- the step the device draws of the launches after it are keyed
+    by.  One kernel (csrc/draws.h) behind three exports, one per library file that launches it: chaorec_dualvae_tick
+    (DualVAE, through ops_vae.dualvae_tick), chaorec_mvgae_tick (MVGAE, ops_mvgae.mvgae_tick) and chaorec_adagcl_tick
+    (AdaGCL, ops_edges.adagcl_tick).  Models without an export of their own call this with the default: GraphAug and MHRec."""
+    _need_cuda(state)
+    getattr(_lib.load(), export)(_ptr(state), _stream())
+
+
 # --------------------------------------------------------------------------------------------
 # SpMM
 # --------------------------------------------------------------------------------------------
@@ -966,7 +1005,7 @@ def rank_metrics(rank_idx, row_user, pos_rowptr, pos_items, k_list):
 
 
 # (ops.linear's pipe: "bf16x3" = split-bf16 MFMA, "f32" = the f32 MFMA chain.  Lives on this facade because callers and tests
-#  switch it here; ops_dense / ops_extra read it through the facade at call time.)
+#  switch it here; ops_dense, ops_adam and ops_diffmm read it through the facade at call time.)
 LINEAR_FORWARD = os.environ.get("CHAOREC_LINEAR_FORWARD", "bf16x3")
 
 
@@ -1012,43 +1051,28 @@ def mean_all(x):
     return _MeanAll.apply(x)
 
 
-# ---- the dense products (GEMM, linear, MMGCN's layer) and the optimizer / model-family wrappers live in their own modules since
-# ---- round 5 (ops.py had grown to 1 700 lines); everything is still reachable as chaorec_amd.ops.<name>, resolved
-# ---- on first use (PEP 562) because those modules import the helpers of this one.
-_MOVED = {
-    "ops_dense": (
-        "gemm_raw", "gemm_nt_bf16x3", "gemm_tn_bf16x3", "gemm_nn_bf16x3", "_dual_ok", "gemm_nt_bf16x3_dual",
-        "gemm_nn_bf16x3_dual", "gemm_tn_bf16x3_dual", "_linear_fwd_raw", "_leaky_bwd_raw", "_linear_gx_raw",
-        "_linear_gw_raw", "_Linear", "linear", "leaky_cat_add", "leaky_split_bwd", "MMGCN_LAYER", "MMGCN_DUAL",
-        "_MMGCNLayer", "mmgcn_layer", "_NormalizeRows", "normalize_rows",
-    ),
-    "ops_extra": (
-        "adam_step", "adam_bias_table", "unique_rows", "adam_lowrank_strips", "adam_lowrank", "_LinearRows",
-        "linear_rows", "adam_multi", "adam_multi_max", "_SpMMAdd", "spmm_add", "edge_dropout_norm", "_SpMMValues",
-        "spmm_values", "edge_dot_raw", "_EdgeDot", "edge_dot", "_NGCFLayer", "ngcf_layer", "weighted_sample_keep", "weighted_sample_keys",
-        "_RowCosineScale", "row_cosine_scale", "dgcf_check_shape", "dgcf_softmax", "dgcf_propagate_raw", "dgcf_p_schedule",
-        "dgcf_forward_raw", "_DGCFForward", "dgcf_forward", "_DGCFCor", "dgcf_cor_loss",
-        "MULTVAE_LATENT", "MultVAEStructure", "multvae_tick", "_MultVAEEncode", "multvae_encode", "_MultVAEDecode",
-        "multvae_decode",
-        "MACRID_D", "MACRID_K", "MACRID_H", "MACRID_STAGING_BYTES", "macrid_check_shape", "macrid_tick", "macrid_normal",
-        "_MacridConcept", "macrid_concept", "_MacridEncode", "macrid_encode", "macrid_split", "_MacridMix", "macrid_mix",
-        "macrid_range_users", "macrid_scores", "macrid_topk",
-        "DUALVAE_K", "DUALVAE_A", "DUALVAE_H", "DUALVAE_STAGING_BYTES", "dualvae_check_shape", "dualvae_tick", "_DualVAEEncode",
-        "dualvae_encode", "_DualVAEDense", "dualvae_dense", "dualvae_writeback", "dualvae_range_users", "dualvae_scores",
-        "_DualVAELinear", "dualvae_linear", "_DualVAELoss", "dualvae_loss",
-    ),
-}
+# ---- the dense products (ops_dense) and the wrappers of every later kernel family (one module per csrc file, laid out as csrc/
+# ---- is) live beside this file; each imports the helpers of this one, so this one cannot import them at import time.  Every
+# ---- public name of theirs is still reachable as chaorec_amd.ops.<name>: resolved on first use (PEP 562) against the modules'
+# ---- own __all__ lists, then kept in this module's globals.
+_FAMILY_MODULES = ("ops_dense", "ops_adam", "ops_sparse_family", "ops_dgcf", "ops_vae", "ops_usergraph", "ops_mvgae",
+                   "ops_diffmm", "ops_edges", "ops_mhrec")
+
+
+def _family(module):
+    import importlib
+    return importlib.import_module("." + module, __package__)
 
 
 def __getattr__(name):
-    for module, names in _MOVED.items():
-        if name in names:
-            import importlib
-            value = getattr(importlib.import_module("." + module, __package__), name)
-            globals()[name] = value
-            return value
+    if not name.startswith("__"):
+        for module in _FAMILY_MODULES:
+            m = _family(module)
+            if name in m.__all__:
+                value = globals()[name] = getattr(m, name)
+                return value
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def __dir__():
-    return sorted(set(globals()) | {n for names in _MOVED.values() for n in names})
+    return sorted(set(globals()).union(*(_family(module).__all__ for module in _FAMILY_MODULES)))

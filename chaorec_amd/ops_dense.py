@@ -1,7 +1,7 @@
 """Dense products behind the model classes: the f32 / split-bf16 MFMA GEMM wrappers, `nn.Linear` as an autograd node
 (ops.linear), MMGCN's fused layer and its row passes, F.normalize over a virtual concatenation.  Moved out of ops.py in round
-5 with no behaviour change; `chaorec_amd.ops` re-exports every name here (and keeps LINEAR_FORWARD, which
-tests switch on the facade: it is read through `_ops` at call time)."""
+5 with no behaviour change; every name in `__all__` resolves as `chaorec_amd.ops.<name>` too (ops keeps
+LINEAR_FORWARD, which tests switch on the facade: it is read through `_ops` at call time)."""
 import ctypes
 import os as _os
 
@@ -10,6 +10,13 @@ import torch
 from . import _lib
 from . import ops as _ops
 from .ops import _f32c, _f32rows, _need_cuda, _ptr, _stream, col_sum, spmm_raw  # noqa: F401
+
+__all__ = [
+    "gemm_raw", "gemm_nt_bf16x3", "gemm_tn_bf16x3", "gemm_nn_bf16x3", "_dual_ok", "gemm_nt_bf16x3_dual", "gemm_nn_bf16x3_dual",
+    "gemm_tn_bf16x3_dual", "_linear_fwd_raw", "_leaky_bwd_raw", "_linear_gx_raw", "_linear_gw_raw", "_Linear", "linear",
+    "leaky_cat_add", "leaky_split_bwd", "MMGCN_LAYER", "MMGCN_DUAL", "_MMGCNLayer", "mmgcn_layer", "_NormalizeRows",
+    "normalize_rows",
+]
 
 
 # --------------------------------------------------------------------------------------------

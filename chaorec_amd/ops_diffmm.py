@@ -1,0 +1,140 @@
+"""DiffMM over csrc/diffmm.hip: the noised history rows in one launch, the denoiser's output layer with both losses and the
+gradient by its output in one pass."""
+import ctypes
+
+import torch
+
+from . import _lib
+from . import ops as _ops
+from .ops import _f32, _f32c, _need_cuda, _ptr, _stream, col_sum
+from .ops_dense import gemm_nn_bf16x3, gemm_raw, gemm_tn_bf16x3
+
+__all__ = [
+    "DIFFMM_D", "diffmm_check_shape", "diffmm_tiles", "diffmm_rows_per_block", "diffmm_ld", "diffmm_rows", "_diffmm_big",
+    "diffmm_out_loss_raw", "_DiffMMDenoiseLoss", "diffmm_denoise_loss",
+]
+
+
+DIFFMM_D = 64                # the embedding width of r and F
+
+
+def diffmm_check_shape(B, I, H, D=DIFFMM_D):
+    _lib.load().chaorec_diffmm_check_shape(int(B), int(I), int(H), int(D))
+
+
+def diffmm_tiles():
+    """(bm, bn, bk) of the one-pass output layer."""
+    v = [ctypes.c_int32(0) for _ in range(3)]
+    _lib.load().chaorec_diffmm_tiles(*(ctypes.byref(x) for x in v))
+    return tuple(int(x.value) for x in v)
+
+
+def diffmm_rows_per_block():
+    return int(_lib.load().chaorec_diffmm_rows_per_block())
+
+
+def diffmm_ld(num_item):
+    """The row stride of x_in and d_out: I rounded up to a multiple of 4 (float4 stores, vector loads in the GEMMs)."""
+    return (int(num_item) + 3) // 4 * 4
+
+
+def diffmm_rows(users, rowptr, col, num_item, a_row=None, s_row=None, noise=None, keep=None, seed=0, step=0, salt=0, plain=False):
+    """users int64 [B] -> (x_in fp32 [B, I], a view of a [B, ld] buffer whose pad columns are 0; bits uint32-as-int32
+    [B, ceil(I / 32)]).  plain: the multi-hot rows themselves.  Otherwise x_in = dropout_0.5(a x0 + s n) with n and the keep
+    flags given ([B, I]) or drawn from the counter RNG keyed (seed, step, salt, user, item)."""
+    _need_cuda(users, rowptr, col, a_row, s_row, noise, keep)
+    users = users.to(torch.int64).contiguous()
+    B, I, U = users.numel(), int(num_item), rowptr.numel() - 1
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32:
+        raise TypeError("diffmm_rows: rowptr must be int64 and col int32")
+    if not plain:
+        a_row, s_row = _f32("diffmm", a_row, "a_row", (B,)), _f32("diffmm", s_row, "s_row", (B,))
+        if noise is not None:
+            noise = _f32("diffmm", noise, "noise", (B, I))
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+            if tuple(keep.shape) != (B, I):
+                raise ValueError("diffmm: keep must be [B, I]")
+    ld = diffmm_ld(I)
+    x = torch.empty((B, ld), dtype=torch.float32, device=users.device)
+    bits = torch.empty((B, (I + 31) // 32), dtype=torch.int32, device=users.device)
+    _lib.load().chaorec_diffmm_rows_f32(_ptr(users), B, U, _ptr(rowptr), _ptr(col), I, ld, _ptr(a_row), _ptr(s_row),
+                                        _ptr(None if plain else noise), _ptr(None if plain else keep), int(seed), int(step),
+                                        int(salt), int(bool(plain)), _ptr(x), _ptr(bits), _stream())
+    return x[:, :I], bits
+
+
+def _diffmm_big(rows):
+    """The split-bf16 GEMMs read strided operands in place and pay from a few hundred rows on (ops_dense._linear_fwd_raw)."""
+    return _ops.LINEAR_FORWARD == "bf16x3" and rows >= 256
+
+
+def diffmm_out_loss_raw(h, W_out, b_out, bits, x0E, F, w, e_loss):
+    """The forward of diffmm_denoise_loss without a tape -> (loss [1], diff_rows [B] float64, gc_rows [B], d_out [B, ld] with
+    d loss / d out in its first I columns and 0 in the rest, r [B, 64])."""
+    _need_cuda(h, W_out, b_out, bits, x0E, F, w)
+    B, H = h.shape
+    I = W_out.shape[0]
+    h, W_out = _ops._f32rows(h), _ops._f32rows(W_out)
+    b_out, F = _f32("diffmm", b_out, "b_out", (I,)), _f32("diffmm", F, "F", (I, DIFFMM_D))
+    x0E = _f32("diffmm", x0E, "x0E", (B, DIFFMM_D))
+    if W_out.shape[1] != H or tuple(bits.shape) != (B, (I + 31) // 32) or bits.dtype != torch.int32 or not bits.is_contiguous():
+        raise ValueError("diffmm: W_out must be [I, H] and bits int32 [B, ceil(I / 32)]")
+    if w.dtype != torch.float64 or tuple(w.shape) != (B,):
+        raise ValueError("diffmm: the weight is float64 [B] (GaussianDiffusion.SNR works on float64 tables)")
+    diffmm_check_shape(B, I, H)
+    lib, dev = _lib.load(), h.device
+    M = gemm_raw(W_out, F, transA=True)                                     # [H, 64]
+    r = gemm_raw(h, M)                                                      # [B, 64]
+    r = (r + gemm_raw(b_out.reshape(1, I), F) - x0E).contiguous()
+    w = w.contiguous()
+    c_row = (w * (2.0 / (float(B) * float(I)))).to(torch.float32)           # formed in double
+    kf = 2.0 * float(e_loss) / (float(B) * DIFFMM_D)
+    bn = diffmm_tiles()[1]
+    ld, NT = diffmm_ld(I), (I + bn - 1) // bn
+    d_out = torch.empty((B, ld), dtype=torch.float32, device=dev)
+    part = torch.empty((B, NT), dtype=torch.float32, device=dev)
+    diff_rows = torch.empty(B, dtype=torch.float64, device=dev)
+    gc_rows, loss = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+    lib.chaorec_diffmm_out_loss_f32(_ptr(h), h.stride(0), _ptr(W_out), W_out.stride(0), _ptr(b_out), _ptr(bits), _ptr(r), _ptr(F),
+                                    _ptr(w), _ptr(c_row), kf, float(e_loss), B, I, H, _ptr(d_out), ld, _ptr(part),
+                                    _ptr(diff_rows), _ptr(gc_rows), _ptr(loss), _stream())
+    return loss, diff_rows, gc_rows, d_out, r
+
+
+class _DiffMMDenoiseLoss(torch.autograd.Function):
+    """(h [B, H], W_out [I, H], b_out [I]) -> loss [1], diff_rows [B] float64, gc_rows [B] (Model/DiffMM.py:468-471,
+    :640-658).  Forward: M = W_out^T F, r = h M + b_out F - x0 E (three small GEMMs), then the one-pass launch, which leaves
+    d loss / d out.  Backward: dW_out = d_out^T (g h), dh = g (d_out W_out), db_out = g colsum(d_out); g is folded into the
+    [B, H] operands, d_out is not passed over again."""
+
+    @staticmethod
+    def forward(ctx, h, W_out, b_out, bits, x0E, F, w, e_loss):
+        loss, diff_rows, gc_rows, d_out, _ = diffmm_out_loss_raw(h, W_out, b_out, bits, x0E, F, w, e_loss)
+        ctx.save_for_backward(h, W_out, d_out)
+        ctx.mark_non_differentiable(diff_rows, gc_rows)
+        return loss, diff_rows, gc_rows
+
+    @staticmethod
+    def backward(ctx, g, _gd, _gg):
+        h, W_out, d_full = ctx.saved_tensors
+        B, I = h.shape[0], W_out.shape[0]
+        g = _f32c(g).reshape(1)
+        d_out = d_full[:, :I]
+        dW = dh = db = None
+        if ctx.needs_input_grad[1]:
+            gh = h * g
+            dW = gemm_tn_bf16x3(d_out, gh) if _diffmm_big(B) else gemm_raw(d_out.contiguous(), gh.contiguous(), transA=True)
+        if ctx.needs_input_grad[0]:
+            dh = gemm_nn_bf16x3(d_out, W_out) if _diffmm_big(B) else gemm_raw(d_out.contiguous(), W_out.contiguous())
+            dh = dh * g
+        if ctx.needs_input_grad[2]:
+            db = col_sum(d_full)[:I] * g
+        return dh, dW, db, None, None, None, None, None
+
+
+def diffmm_denoise_loss(h, W_out, b_out, bits, x0E, F, w, e_loss):
+    """-> (loss [1] = mean_b w_b mse_b + e_loss mean_b gc_b, diff_rows [B] float64, gc_rows [B]).  bits: the x0 bit table of
+    diffmm_rows; x0E [B, 64] = the batch's history-row sums of the item embeddings; F [I, 64] the modality's projected
+    features; w float64 [B] the SNR weight.  x0E and F carry no gradient (the reference detaches them)."""
+    return _DiffMMDenoiseLoss.apply(h, W_out, b_out, bits, x0E.detach(), F.detach(), w, float(e_loss))
