@@ -10,59 +10,12 @@
 // launch/latency-bound (0.79 MB gathered at B=1024), so the forward is two launches with a
 // fixed reduction order (bit-reproducible loss) and the backward is one launch of 256-B
 // atomic row adds (the full-rate atomic shape on gfx950).
+#include "bpr_rows.h"
 #include "draws.h"
 #include <cstdlib>
 
 namespace chaorec {
 
-
-// the wave of triple b: five wave butterflies over the three rows' elements -- rows(k, u, p, n) yields element k of the user /
-// positive / negative row --, lane 0 writes the term / coefficient / L2 parts
-template <class Rows>
-__device__ __forceinline__ float bpr_terms_wave_of(Rows &&rows, int b, int B, int D, int variant, float *__restrict__ coef,
-                                                   float *__restrict__ ws) {
-  const int lane = threadIdx.x & 63;
-  float sp = 0.f, sn = 0.f, ru = 0.f, rp = 0.f, rn = 0.f;
-  for (int k = lane; k < D; k += 64) {
-    float u, p, n;
-    rows(k, u, p, n);
-    sp += u * p;
-    sn += u * n;
-    ru += u * u;
-    rp += p * p;
-    rn += n * n;
-  }
-  sp = wave_sum(sp);
-  sn = wave_sum(sn);
-  ru = wave_sum(ru);
-  rp = wave_sum(rp);
-  rn = wave_sum(rn);
-  float c = 0.f;
-  if (lane == 0) {
-    const float d = sp - sn;
-    const float invB = 1.0f / (float)B;
-    float term;
-    if (variant == CHAOREC_BPR_LOG_SIGMOID_EPS) {
-      const float s = sigmoidf_acc(d);
-      term = logf(s + 1e-5f);
-      c = -invB * (s * (1.0f - s)) / (s + 1e-5f);
-    } else if (variant == CHAOREC_BPR_LOGSIGMOID) {
-      // logsigmoid(d) = min(d,0) - log1p(exp(-|d|))
-      term = fminf(d, 0.f) - log1pf(expf(-fabsf(d)));
-      c = -invB * sigmoidf_acc(-d);
-    } else {
-      const float s = sigmoidf_acc(d);
-      term = logf(s);
-      c = -invB * (1.0f - s);
-    }
-    coef[b] = c;
-    ws[b] = term;
-    ws[B + b] = ru;
-    ws[2 * B + b] = rp;
-    ws[3 * B + b] = rn;
-  }
-  return __shfl(c, 0, 64);
-}
 
 // ... with three row gathers from a table
 __device__ __forceinline__ float bpr_terms_wave(const float *__restrict__ tab_u, const float *__restrict__ tab_i,
@@ -84,12 +37,6 @@ __global__ __launch_bounds__(256) void bpr_fwd_terms_kernel(
   if (b >= B) return;
   bpr_terms_wave(tab_u, tab_i, users[b], pos[b], neg[b], b, B, D, variant, coef, ws);
 }
-
-// draw_triple is defined below (sampler section)
-__device__ __forceinline__ void draw_triple(const int64_t *__restrict__, int64_t, const int64_t *__restrict__,
-                                            const int32_t *__restrict__, int64_t, uint32_t, uint64_t, uint64_t,
-                                            uint32_t, int64_t &, int64_t &, int64_t &, const int64_t *__restrict__,
-                                            int64_t);
 
 // The same forward with the batch drawn IN the launch: lane 0 of triple b's wave picks the training edge and rejects
 // negatives against the user's history, the wave shares the three ids by shuffle, gathers and reduces.  The ids are
@@ -128,30 +75,7 @@ __global__ __launch_bounds__(256) void bpr_fwd_terms_drawn_kernel(
 // memory put a store -> load round trip into a launch that is nothing but latency: 7.3 -> 10.9 us) and parks them in `rows`
 // ([3 B, D]: triple b's user, positive, negative at 3 b, 3 b + 1, 3 b + 2) for the ordered launch, which would otherwise
 // form them again.
-constexpr int kMeanMaxTabs = 4;
-constexpr int kMeanMaxQ = 4;
-struct MeanSrc {
-  const float *t[kMeanMaxTabs];             // x_0 .. x_L, [N, D] each, users first
-  int n;
-  float w;
-  int64_t item_offset;                      // row of item 0
-  float *rows;
-};
-// (NT, the table count, is a template parameter of the launch: with a run-time count every table's load sat in a branch of
-//  its own and waited for the one before -- twelve round trips in a row instead of one, 7.4 -> 10.7 us)
-template <int NT>
-__device__ __forceinline__ void mean_elems(const MeanSrc &M, size_t ou, size_t op, size_t on, float &mu, float &mp, float &mn) {
-  float tu[NT], tp[NT], tn[NT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i) tu[i] = M.t[i][ou], tp[i] = M.t[i][op], tn[i] = M.t[i][on];
-  mu = mul_rn(M.w, tu[0]), mp = mul_rn(M.w, tp[0]), mn = mul_rn(M.w, tn[0]);
-#pragma unroll
-  for (int i = 1; i < NT; ++i) {
-    mu = add_rn(mu, mul_rn(M.w, tu[i]));
-    mp = add_rn(mp, mul_rn(M.w, tp[i]));
-    mn = add_rn(mn, mul_rn(M.w, tn[i]));
-  }
-}
+// (kMeanMaxTabs, kMeanMaxQ, MeanSrc, mean_elems: bpr_rows.h)
 
 // Forward terms AND the backward's row updates in one launch, for a loss that is differentiated with d(loss) = 1
 // (a plain loss.backward()): the coefficient of sample b depends on its own score difference only, never on the
@@ -174,11 +98,7 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_drawn_kernel(
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   // the optimizer's step count and this step's bias corrections (two double pow()s on one otherwise idle thread,
   // under the other lanes' draw + gathers): nothing else in this launch reads them, the Adam epilogue comes later
-  if (adam_step && blockIdx.x == 0 && threadIdx.x == blockDim.x - 1) {
-    const int st = adam_step[0] + 1;
-    adam_step[0] = st;
-    adam_bias_corrections(st, beta1, beta2, adam_bc[0], adam_bc[1]);
-  }
+  if (adam_step && blockIdx.x == 0 && threadIdx.x == blockDim.x - 1) adam_step_on(adam_step, beta1, beta2, adam_bc);
   if (b >= B) return;
   int64_t u = 0, p = 0, n = 0;
   if (edges) {
@@ -225,17 +145,10 @@ __global__ __launch_bounds__(256) void bpr_fwd_bwd_drawn_kernel(
       float uu, pp, nn;
       if constexpr (MEAN) uu = pick(mu, k), pp = pick(mp, k), nn = pick(mn, k);
       else uu = tab_u[ou + k], pp = tab_i[op + k], nn = tab_i[on + k];
-      atomicAdd(g_u + ou + k, c * (pp - nn) + r2 * uu);
-      atomicAdd(g_i + op + k, c * uu + r2 * pp);
-      atomicAdd(g_i + on + k, -c * uu + r2 * nn);
+      bpr_grad_adds(g_u, g_i, ou + k, op + k, on + k, c, r2, uu, pp, nn);
     }
   }
-  // the rows of the gradient buffer this sample touched, for the row-sparse backward propagates
-  // (chaorec_spmm_csr_rowsparse_f32): bit r of a bitmap over the joined table's rows, items from bits_item_offset on
-  if (row_bits && lane < 3) {
-    const int64_t r = lane == 0 ? u : bits_item_offset + (lane == 1 ? p : n);
-    atomicOr(row_bits + (r >> 5), 1u << (r & 31));
-  }
+  flag_triple_rows(row_bits, bits_item_offset, lane, u, p, n);
 }
 
 // One block, fixed order: thread t sums elements t, t+256, ... then a fixed LDS tree.
@@ -644,14 +557,7 @@ static bool launch_bpr_ordered(OrdArgs &P, int groups, hipStream_t st) {
 // ---- sampler -------------------------------------------------------------------------------
 // Counter-based generator: splitmix64 finaliser over (seed, step, b, attempt).  Stateless, so a
 // draw does not depend on launch geometry or on how many draws other samples needed.
-// (mix64: common.h; the keying: draws.h)
-__device__ __forceinline__ uint32_t sampler_draw(uint64_t seed, uint64_t step, uint32_t b,
-                                                 uint32_t attempt, uint32_t num_item) {
-  uint64_t h = draw_hash(seed, step, ((uint64_t)b << 32) | attempt);
-  // Lemire multiply-shift onto [0, num_item): bias <= num_item / 2^32, far below test resolution
-  return (uint32_t)(((h >> 32) * (uint64_t)num_item) >> 32);
-}
-
+// (mix64: common.h; the keying, sampler_draw and draw_triple: draws.h)
 __global__ __launch_bounds__(256) void sample_negatives_kernel(
     const int64_t *__restrict__ hist_rowptr, const int32_t *__restrict__ hist_col,
     const int64_t *__restrict__ users, int B, uint32_t num_item, uint64_t seed, uint64_t step,
@@ -675,42 +581,6 @@ __global__ __launch_bounds__(256) void sample_negatives_kernel(
     if (attempt >= 4096u) break;  // a user who interacted with ~every item: give up, bounded
   }
   out_neg[b] = (int64_t)cand + id_offset;
-}
-
-// sample b of batch `step`: a training edge picked uniformly (user, positive as LOCAL item id) and one negative the
-// user has not interacted with (rejection against the ascending history row, bounded)
-__device__ __forceinline__ void draw_triple(const int64_t *__restrict__ edges, int64_t n_edges,
-                                            const int64_t *__restrict__ hist_rowptr,
-                                            const int32_t *__restrict__ hist_col, int64_t num_user, uint32_t num_item,
-                                            uint64_t seed, uint64_t step, uint32_t b, int64_t &u, int64_t &p,
-                                            int64_t &n, const int64_t *__restrict__ perm,
-                                            int64_t perm_pos) {
-  uint64_t idx;
-  if (perm) {
-    // epoch permutation (DataLoader(shuffle=True)): every edge once.  A read position past the end (a caller that
-    // draws more batches than the epoch holds) is clamped, never dereferenced.
-    const int64_t q = perm_pos + (int64_t)b;
-    idx = (uint64_t)perm[q < n_edges ? (q < 0 ? 0 : q) : n_edges - 1];
-  } else {
-    const uint64_t hsel = draw_hash(seed, step, 0xED6E5ull ^ ((uint64_t)b << 32));
-    // 64x64 -> high 64 multiply-shift onto [0, n_edges)
-    idx = (uint64_t)(((unsigned __int128)hsel * (unsigned __int128)(uint64_t)n_edges) >> 64);
-  }
-  u = edges[2 * idx];
-  p = edges[2 * idx + 1] - num_user;
-  const int64_t h0 = hist_rowptr[u], h1 = hist_rowptr[u + 1];
-  uint32_t cand = 0;
-  for (uint32_t attempt = 0;; ++attempt) {
-    cand = sampler_draw(seed, step, b, attempt, num_item);
-    int64_t lo = h0, hi = h1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((uint32_t)hist_col[mid] < cand) lo = mid + 1; else hi = mid;
-    }
-    const bool seen = (lo < h1) && ((uint32_t)hist_col[lo] == cand);
-    if (!seen || attempt >= 4096u) break;
-  }
-  n = (int64_t)cand;
 }
 
 // One launch per batch: pick B training edges uniformly (counter-based, with replacement across batches),
@@ -877,10 +747,6 @@ extern "C" int chaorec_bpr_fwd_bwd_f32(const float *tab_u, const float *tab_i, c
                                     nullptr, 0, stream);
 }
 
-static int bpr_bwd_ordered(const float *tab_u, const float *tab_i, const float *rows, const int64_t *users, const int64_t *pos,
-                           const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight, const float *grad_out,
-                           float *g_u, float *g_i, void *stream);
-
 // (mean: NULL = the rows of tab_u / tab_i; else the layer-table row source, tab_u / tab_i unused)
 static int bpr_fwd_bwd(const float *tab_u, const float *tab_i, const MeanSrc *mean, const int64_t *edges, int64_t n_edges,
                        const int64_t *hist_rowptr, const int32_t *hist_col, int64_t num_user, int32_t num_item, uint64_t seed,
@@ -889,24 +755,12 @@ static int bpr_fwd_bwd(const float *tab_u, const float *tab_i, const MeanSrc *me
                        int64_t *out_pos, int64_t *out_neg, float *coef, float *workspace, const int64_t *perm,
                        const int64_t *perm_pos, int64_t pos_offset, float *g_u, float *g_i, int32_t *adam_step, float beta1,
                        float beta2, float *adam_bc, uint32_t *row_bits, int64_t bits_item_offset, void *stream) {
-  if ((!mean && (!tab_u || !tab_i)) || !coef || !workspace || !g_u || !g_i)
-    return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: NULL argument");
-  if (pos_offset < 0) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: pos_offset %lld", (long long)pos_offset);
-  if (adam_step && !adam_bc) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: adam_step without adam_bc");
-  if (edges) {
-    if (!hist_rowptr || !out_users || !out_pos || !out_neg) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: NULL draw argument");
-    if (n_edges <= 0 || num_item <= 0) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: bad sizes");
-    if (perm && !perm_pos) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: perm without perm_pos");
-  } else if (!in_users || !in_pos || !in_neg) {
-    return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: neither an edge list to draw from nor a batch");
-  }
-  if (B <= 0 || D <= 0) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: B=%d D=%d", B, D);
-  if (variant < 0 || variant > 2) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: variant %d", variant);
-  // CHAOREC_BPR_ORDERED=2: the fused steps' gradient rows too are added by the ordered, atomic-free launch (one more launch per
-  // step -- ~7 us of a 121 us sports step, nothing of a configs[4] step --: a LightGCN run is then the same bits every time,
-  // and the fused step equals the autograd step bit for bit also on batches with repeated rows).  Read per call.
-  const char *env = std::getenv("CHAOREC_BPR_ORDERED");
-  bool ordered = env && env[0] == '2' && 3 * (int64_t)B <= kOrdMaxSlots && D <= 256;
+  if (!mean && (!tab_u || !tab_i)) return fail(CHAOREC_E_INVALID, "bpr_fwd_bwd: NULL argument");
+  if (int rc = bpr_fwd_bwd_check("bpr_fwd_bwd", coef, workspace, g_u, g_i, edges, n_edges, hist_rowptr, num_item, in_users,
+                                 in_pos, in_neg, out_users, out_pos, out_neg, perm, perm_pos, pos_offset, adam_step, adam_bc, B,
+                                 D, variant))
+    return rc;
+  const bool ordered = bpr_ordered_after_fused(B, D);
   const int64_t *ids_u = edges ? out_users : in_users, *ids_p = edges ? out_pos : in_pos, *ids_n = edges ? out_neg : in_neg;
 #define CHAOREC_BPR_FWD_BWD_ARGS                                                                                            \
   tab_u, tab_i, edges, n_edges, hist_rowptr, hist_col, num_user, (uint32_t)num_item, seed, step, step_dev, in_users, in_pos,    \
@@ -1010,10 +864,14 @@ extern "C" int chaorec_bpr_bwd_ordered_f32(const float *tab_u, const float *tab_
   return bpr_bwd_ordered(tab_u, tab_i, nullptr, users, pos, neg, B, D, coef, reg_weight, grad_out, g_u, g_i, stream);
 }
 
-// (rows: NULL = the table rows users[b] / pos[b] / neg[b] of tab_u / tab_i; else MeanSrc::rows, the tables unused)
-static int bpr_bwd_ordered(const float *tab_u, const float *tab_i, const float *rows, const int64_t *users, const int64_t *pos,
-                           const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight, const float *grad_out,
-                           float *g_u, float *g_i, void *stream) {
+bool chaorec::bpr_ordered_after_fused(int32_t B, int32_t D) {
+  const char *env = std::getenv("CHAOREC_BPR_ORDERED");
+  return env && env[0] == '2' && 3 * (int64_t)B <= kOrdMaxSlots && D <= 256;
+}
+
+int chaorec::bpr_bwd_ordered(const float *tab_u, const float *tab_i, const float *rows, const int64_t *users, const int64_t *pos,
+                             const int64_t *neg, int32_t B, int32_t D, const float *coef, float reg_weight, const float *grad_out,
+                             float *g_u, float *g_i, void *stream) {
   if ((!rows && (!tab_u || !tab_i)) || !users || !pos || !neg || !coef || !g_u || !g_i)
     return fail(CHAOREC_E_INVALID, "bpr_bwd_ordered: NULL argument");
   if (B <= 0 || D <= 0) return fail(CHAOREC_E_INVALID, "bpr_bwd_ordered: B=%d D=%d", B, D);

@@ -27,6 +27,52 @@ __device__ __forceinline__ float draw_normal(uint64_t key, uint64_t a, uint64_t 
 // each caller packs its own x (salts and shifts stay with it) and cuts its own bits from the result
 __device__ __forceinline__ uint64_t draw_hash(uint64_t seed, uint64_t step, uint64_t x) { return mix64(seed ^ mix64(step ^ mix64(x))); }
 
+// ---- the BPR sampler's draws (csrc/bpr.hip, csrc/bpr_frontier.hip) ----------------------------------------------------
+// Counter-based: the draw_hash keying over (seed, step, b, attempt).  Stateless, so a draw does not depend on launch
+// geometry or on how many draws other samples needed.
+__device__ __forceinline__ uint32_t sampler_draw(uint64_t seed, uint64_t step, uint32_t b,
+                                                 uint32_t attempt, uint32_t num_item) {
+  uint64_t h = draw_hash(seed, step, ((uint64_t)b << 32) | attempt);
+  // Lemire multiply-shift onto [0, num_item): bias <= num_item / 2^32, far below test resolution
+  return (uint32_t)(((h >> 32) * (uint64_t)num_item) >> 32);
+}
+
+// sample b of batch `step`: a training edge picked uniformly (user, positive as LOCAL item id) and one negative the
+// user has not interacted with (rejection against the ascending history row, bounded)
+__device__ __forceinline__ void draw_triple(const int64_t *__restrict__ edges, int64_t n_edges,
+                                            const int64_t *__restrict__ hist_rowptr,
+                                            const int32_t *__restrict__ hist_col, int64_t num_user, uint32_t num_item,
+                                            uint64_t seed, uint64_t step, uint32_t b, int64_t &u, int64_t &p,
+                                            int64_t &n, const int64_t *__restrict__ perm,
+                                            int64_t perm_pos) {
+  uint64_t idx;
+  if (perm) {
+    // epoch permutation (DataLoader(shuffle=True)): every edge once.  A read position past the end (a caller that
+    // draws more batches than the epoch holds) is clamped, never dereferenced.
+    const int64_t q = perm_pos + (int64_t)b;
+    idx = (uint64_t)perm[q < n_edges ? (q < 0 ? 0 : q) : n_edges - 1];
+  } else {
+    const uint64_t hsel = draw_hash(seed, step, 0xED6E5ull ^ ((uint64_t)b << 32));
+    // 64x64 -> high 64 multiply-shift onto [0, n_edges)
+    idx = (uint64_t)(((unsigned __int128)hsel * (unsigned __int128)(uint64_t)n_edges) >> 64);
+  }
+  u = edges[2 * idx];
+  p = edges[2 * idx + 1] - num_user;
+  const int64_t h0 = hist_rowptr[u], h1 = hist_rowptr[u + 1];
+  uint32_t cand = 0;
+  for (uint32_t attempt = 0;; ++attempt) {
+    cand = sampler_draw(seed, step, b, attempt, num_item);
+    int64_t lo = h0, hi = h1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((uint32_t)hist_col[mid] < cand) lo = mid + 1; else hi = mid;
+    }
+    const bool seen = (lo < h1) && ((uint32_t)hist_col[lo] == cand);
+    if (!seen || attempt >= 4096u) break;
+  }
+  n = (int64_t)cand;
+}
+
 // out[e] = std * N(0, 1) keyed (seed, state[1], SALT, e) (the autoencoders' epsilon: it keeps their prefix, and its name)
 template <int BITS, uint64_t SALT>
 static __global__ __launch_bounds__(256) void vae_normal_kernel(float *__restrict__ out, int64_t n, uint64_t seed,

@@ -785,6 +785,43 @@ def bpr_fwd_bwd(tab, item_offset, grad, B, variant, reg_weight, coef, ws, ids, e
                                                int(item_offset), _ptr(rows), *args)
 
 
+def bpr_frontier_round_entries():
+    """Entries of a triple's three rows that ops.bpr_fwd_bwd_frontier gathers per round (csrc/bpr_frontier.hip's kCH)."""
+    return int(_lib.load().chaorec_bpr_frontier_round_entries())
+
+
+def bpr_fwd_bwd_frontier(csr, layer_tabs, layer_w, rows, item_offset, grad, B, variant, reg_weight, coef, ws, ids, edges=None,
+                         hist=None, num_user=0, num_item=0, seed=0, step=0, step_dev=None, perm=None, perm_pos=None,
+                         adam_step=None, betas=(0.9, 0.999), adam_bc=None, pos_offset=0, row_bits=None, bits_item_offset=None):
+    """The last forward propagate and bpr_fwd_bwd(layer_tabs=...) in one launch (chaorec_bpr_fwd_bwd_frontier_f32):
+    layer_tabs = x_0 .. x_{L-1}, and the batch's 3 B rows of x_L = A x_{L-1} are computed by the launch itself from `csr` --
+    spmm_raw's rows bit for bit -- before it forms layer_w x_0 + ... + layer_w x_L for them.  Everything else is
+    bpr_fwd_bwd's: `rows` (float32 [3 B, D]) receives the mean rows, ids / coef / ws / grad / row_bits / Adam's counters as
+    there.  D = 64, a graph with static values, 1 .. 3 tables."""
+    _need_cuda(csr.rowptr, grad, coef, ws, edges, step_dev, perm, perm_pos, adam_step, adam_bc, row_bits, rows, *ids, *layer_tabs)
+    D = grad.shape[1]
+    for t in layer_tabs:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != grad.shape:
+            raise TypeError("bpr_fwd_bwd_frontier: layer_tabs must be contiguous float32 tables of grad's shape")
+    if grad.shape[0] != csr.n_rows or csr.n_rows != csr.n_cols:
+        raise ValueError(f"bpr_fwd_bwd_frontier: a square graph over the table's {grad.shape[0]} rows")
+    if rows is None or rows.dtype != torch.float32 or not rows.is_contiguous() or rows.numel() < 3 * int(B) * D:
+        raise TypeError("bpr_fwd_bwd_frontier: rows must be a contiguous float32 buffer of 3 B rows")
+    draw = edges is not None
+    hist_rowptr, hist_col = hist if hist is not None else (None, None)
+    ptrs = (ctypes.c_void_p * len(layer_tabs))(*[t.data_ptr() for t in layer_tabs])
+    mode = 1 if getattr(csr, "dynamic_values", False) else 0     # (refused by the launch)
+    _lib.load().chaorec_bpr_fwd_bwd_frontier_f32(
+        ctypes.cast(ptrs, ctypes.c_void_p), len(layer_tabs), float(layer_w), int(item_offset), _ptr(rows), _ptr(csr.rowptr),
+        _ptr(csr.col), _ptr(csr.val), csr.n_rows, mode, _ptr(edges), edges.shape[0] if draw else 0, _ptr(hist_rowptr),
+        _ptr(hist_col), int(num_user), int(num_item), int(seed) & (2**64 - 1), int(step), _ptr(step_dev),
+        _ptr(None if draw else ids[0]), _ptr(None if draw else ids[1]), _ptr(None if draw else ids[2]), int(B), D, int(variant),
+        float(reg_weight), _ptr(ids[0] if draw else None), _ptr(ids[1] if draw else None), _ptr(ids[2] if draw else None),
+        _ptr(coef), _ptr(ws), _ptr(perm), _ptr(perm_pos), int(pos_offset), _ptr(grad),
+        ctypes.c_void_p(grad.data_ptr() + item_offset * D * 4), _ptr(adam_step), betas[0], betas[1], _ptr(adam_bc), _ptr(row_bits),
+        int(item_offset if bits_item_offset is None else bits_item_offset), _stream())
+
+
 def bpr_finalize(ws, B, D, reg_weight, out_loss, out_total=None, loss_accum=None, advance=None, perm_pos=None,
                  adam_step=None, betas=(0.9, 0.999), adam_bc=None):
     """Reduce a BPR forward's workspace to out_loss = [total, bpr, reg] and do the step's scalar bookkeeping

@@ -500,6 +500,20 @@ def _inner_mean_rows_mode(k, light, n_layers, D):
     return bool(built and os.environ.get("CHAOREC_INNER_MEAN_ROWS", "auto") != "0")
 
 
+def _inner_frontier_mode(inner_mean_rows, D, dynamic_values, batch_size, n_rows, longest_row, round_entries):
+    """-> whether the INNER steps of a replay compute the batch's rows of x_L inside the BPR launch (ops.bpr_fwd_bwd_frontier:
+    L - 1 plain propagates, then one launch for the last propagate and the BPR forward + backward).  The launch exists where
+    the inner steps form the mean in the batch's rows (inner_mean_rows), D = 64 and the graph's values are static.  By rule it
+    is on where, besides, the batch is a small part of the table (12 B <= n_rows, _few_source_mode's rule: otherwise the dense
+    propagate's one pass is the cheaper way to the same rows) and the graph's longest row is at most 32 rounds of the launch
+    (longest_row <= 32 round_entries: a workgroup walks its triple's rows alone, and one popular item of a large graph would
+    be its tail).  CHAOREC_INNER_FRONTIER = auto / 0 / 1: by that rule / off / on wherever the launch exists."""
+    mode = os.environ.get("CHAOREC_INNER_FRONTIER", "auto")
+    built = bool(inner_mean_rows) and D == 64 and not dynamic_values
+    by_rule = 12 * batch_size <= n_rows and longest_row <= 32 * round_entries
+    return bool(built and mode != "0" and (mode == "1" or by_rule))
+
+
 class _FusedStep:
     """What FusedLightGCNStep and dist_lightgcn.FusedShardedLightGCNStep share around their launch sequences: the
     constructor checks, the moment views, state save / restore, the capture protocol and replay.  A subclass supplies
@@ -625,7 +639,8 @@ class _FusedStep:
 
 class FusedLightGCNStep(_FusedStep):
     """One LightGCN training iteration -- train_and_evaluate.py:43-48: zero_grad, model.loss() (Model/LightGCN.py:
-    123-135: L propagates + layer mean, BPR + L2), loss.backward(), Adam step -- as 2L + 2 kernel launches (2L + 1 + 1/k in a k-step replay) with no
+    123-135: L propagates + layer mean, BPR + L2), loss.backward(), Adam step -- as 2L + 2 kernel launches (in a k-step replay
+    2L + 1 + 1/k, and 2L + 1/k where the inner steps run the last propagate inside the BPR launch: `inner_frontier`) with no
     autograd tape and no optimizer launch, captured in one hipGraph:
 
         L x  SpMM (layer mean in the epilogue; the last one writes only the mean = model.result)
@@ -736,6 +751,14 @@ class FusedLightGCNStep(_FusedStep):
         # (inner steps of a replay: see _inner_mean_rows_mode; _mean_rows holds the batch's 3 B rows of the mean)
         self.inner_mean_rows = _inner_mean_rows_mode(self.steps_per_replay, self.light, L, D)
         self._mean_rows = torch.empty((3 * self.B, D), dtype=torch.float32, device=dev) if self.inner_mean_rows else None
+        # (.. and compute x_L in those rows only, inside the BPR launch: see _inner_frontier_mode.  The longest row is read here,
+        #  once, before anything is captured.)
+        self.inner_frontier = False
+        if self.inner_mean_rows and D == 64:
+            rp = model.graph.rowptr
+            longest = int((rp[1:] - rp[:-1]).max()) if rp.numel() > 1 else 0
+            self.inner_frontier = _inner_frontier_mode(True, D, getattr(model.graph, "dynamic_values", False), self.B, N, longest,
+                                                       ops.bpr_frontier_round_entries())
         if capture:
             model.graph.schedule(D)             # (lazily built by the first SpMM call: must exist before capture)
             self._capture(dev)
@@ -782,7 +805,19 @@ class FusedLightGCNStep(_FusedStep):
                             betas=group["betas"], adam_bc=self.bc)
         else:
             src = dict(tab=self.final)
-            if self.inner_mean_rows and j < k - 1:
+            batch = dict(edges=self.edges, hist=model.hist if draw else None, num_user=model.num_user, num_item=model.num_item,
+                         seed=self.seed, step=j, step_dev=self.step_dev, perm=self.perm, perm_pos=self.perm_pos,
+                         adam_step=opt._step_dev, betas=group["betas"], adam_bc=self.bc, pos_offset=j * B, row_bits=r0_bits)
+            if self.inner_frontier and j < k - 1:
+                # an inner step: L - 1 plain propagates; the launch below computes the batch's rows of x_L itself, forms the
+                # mean's rows and does the BPR launch's work.  Nothing is written into `final`.
+                xs = [x0]
+                for l in range(L - 1):
+                    xs.append(ops.spmm_raw(csr, xs[-1], y=self.fbuf[l]))
+                ops.bpr_fwd_bwd_frontier(csr, xs, w, self._mean_rows, model.num_user, self.G, B, ops.VARIANT_LOG_SIGMOID_EPS,
+                                         model.reg_weight, self.coef, ws, self.ids, **batch)
+                src = None
+            elif self.inner_mean_rows and j < k - 1:
                 # an inner step: x_L goes where the mean would (nothing reads `final` as a mean in such a step), the BPR
                 # launch forms the mean's rows it reads
                 xs = [x0]
@@ -791,11 +826,9 @@ class FusedLightGCNStep(_FusedStep):
                 src = dict(tab=None, layer_tabs=xs, layer_w=w, rows=self._mean_rows)
             else:
                 ops.forward_layers(csr, x0, L, self.final, self.fbuf)
-            ops.bpr_fwd_bwd(src.pop("tab"), model.num_user, self.G, B, ops.VARIANT_LOG_SIGMOID_EPS, model.reg_weight,
-                            self.coef, ws, self.ids, edges=self.edges, hist=model.hist if draw else None,
-                            num_user=model.num_user, num_item=model.num_item, seed=self.seed, step=j, step_dev=self.step_dev,
-                            perm=self.perm, perm_pos=self.perm_pos, adam_step=opt._step_dev, betas=group["betas"],
-                            adam_bc=self.bc, pos_offset=j * B, row_bits=r0_bits, **src)
+            if src is not None:
+                ops.bpr_fwd_bwd(src.pop("tab"), model.num_user, self.G, B, ops.VARIANT_LOG_SIGMOID_EPS, model.reg_weight,
+                                self.coef, ws, self.ids, **batch, **src)
         book = dict(out_total=self.static_loss, loss_accum=self.loss_accum, advance=self.step_dev if draw else None,
                     perm_pos=self.perm_pos if (draw and self.perm is not None) else None)
         if k == 1:

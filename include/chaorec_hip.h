@@ -430,6 +430,28 @@ int chaorec_bpr_finalize_steps_f32(const float *workspace, int64_t ws_stride, in
                                    int32_t D, float reg_weight, float *out_loss, float *out_total,
                                    float *loss_accum, int64_t *advance, int64_t *perm_pos, float *scratch, void *stream);
 
+/* chaorec_bpr_fwd_bwd_layers_f32 with the LAST layer table never formed either (csrc/bpr_frontier.hip; an inner step of a
+ * k-step replay): tabs holds x_0 .. x_{n_tabs - 1} (1 .. 3 tables) and the launch computes the batch's 3 B rows of
+ *     x_{n_tabs} = A x_{n_tabs - 1}
+ * itself from the CSR arrays (rowptr int64 [n_rows + 1], col, val; tabs[n_tabs - 1] 16-byte aligned) -- every row the
+ * sequential CSR-order sum from +0 with separately rounded product and sum, the row chaorec_spmm_csr_f32 writes with
+ * alpha = 1 and no z, bit for bit -- and the mean over the n_tabs + 1 tables from them.  So it stands for the last forward
+ * propagate AND the BPR launch: same ids, coef, workspace, `rows`, gradient rows, row_bits and Adam counters.
+ * One workgroup per triple; a round of chaorec_bpr_frontier_round_entries() entries of the triple's three rows is gathered
+ * at once.  D = 64 only; mode: the propagate's (CHAOREC_SPMM_DYNAMIC_VALUES is refused).  Checked before any launch. */
+int chaorec_bpr_fwd_bwd_frontier_f32(const float *const *tabs, int32_t n_tabs, float w, int64_t item_offset, float *rows,
+                                     const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                                     int32_t mode, const int64_t *edges, int64_t n_edges, const int64_t *hist_rowptr,
+                                     const int32_t *hist_col, int64_t num_user, int32_t num_item, uint64_t seed,
+                                     uint64_t step, const int64_t *step_dev, const int64_t *in_users,
+                                     const int64_t *in_pos, const int64_t *in_neg, int32_t B, int32_t D, int32_t variant,
+                                     float reg_weight, int64_t *out_users, int64_t *out_pos, int64_t *out_neg,
+                                     float *coef, float *workspace, const int64_t *perm, const int64_t *perm_pos,
+                                     int64_t pos_offset, float *g_u, float *g_i, int32_t *adam_step, float beta1,
+                                     float beta2, float *adam_bc, uint32_t *row_bits, int64_t bits_item_offset,
+                                     void *stream);
+int64_t chaorec_bpr_frontier_round_entries(void);
+
 /* ---------------------------------------------------------------------------------------
  * R: all-items scoring + history mask + top-K, never materialising the [U, I] matrix.
  *
