@@ -37,6 +37,11 @@ def build_parser():
     parser.add_argument('--num_hypernodes', type=int, default=10, help='MHRec: nodes per rebuilt hyperedge.')
     parser.add_argument('--beta1', type=float, default=0.5, help='MHRec beta1')
     parser.add_argument('--beta2', type=float, default=0.5, help='MHRec beta2')
+    parser.add_argument('--K_s', type=int, default=1, help='BSPM sharpening steps, T_s / tau')
+    parser.add_argument('--T_s', type=float, default=1, help='BSPM sharpening time T_s')
+    parser.add_argument('--K_b', type=int, default=1, help='BSPM blurring steps, T_b / tau (stored, never read)')
+    parser.add_argument('--T_b', type=float, default=1, help='BSPM blurring time T_b (stored, never read)')
+    parser.add_argument('--idl_beta', type=float, default=1, help='BSPM weight of the ideal low-pass term')
     parser.add_argument('--n_mca', type=int, default=2, help='MCLN counterfactual layer.')
     parser.add_argument('--prompt_num', type=float, default=0.1, help='prompt modal numbers.')
     parser.add_argument('--neg_weight', type=float, default=0.1, help='weak modal weight.')

@@ -363,6 +363,17 @@ def train_and_evaluate(model, train_loader, val_data, test_data, optimizer, epoc
     on_device = getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda" and max(topk) <= 50
     if on_device:
         val_data, test_data = EvalLists(val_data, model.device), EvalLists(test_data, model.device)
+    if model_name == "BSPM":
+        # train_and_evaluate.py:531-552: nothing to train, no epochs -- rank once, evaluate both splits, return the test metrics
+        model.eval()
+        rank_list = model.gene_ranklist(to_cpu=False) if on_device else model.gene_ranklist()
+        val_metrics = evaluate(model, val_data, rank_list, topk)
+        test_metrics = evaluate(model, test_data, rank_list, topk)
+        _log_metrics('Validation Metrics:', val_metrics)
+        _log_metrics('Test Metrics:', test_metrics)
+        if history is not None:
+            history.append({"epoch": 1, "loss": 0.0, "val": val_metrics, "test": test_metrics})
+        return test_metrics
     for epoch in range(epochs):
         if model_name in PRE_EPOCH:
             model.pre_epoch_processing()

@@ -1468,6 +1468,34 @@ int chaorec_mhrec_layer_bwd_f32(const int32_t *nodes, int64_t E, int32_t k, cons
                                 uint64_t seed, const int64_t *state, int32_t salt, int32_t training, float *gm, float *tn,
                                 float *dE, float *dX, float *pa1, float *pa2, double *pacc, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * BSPM (Model/BSPM.py:133-181) -- csrc/bspm.hip.  Additive to ABI 16: new names only.  The training-free blur / sharpen
+ * filter for a tile of B users (B a multiple of 4 in [4, 1024]: the SpMM's rule for its feature width), in item space:
+ * P = Rn^T Rn as a CSR (p_ptr int64 [I + 1], p_col int32, p_val fp32, nnz entries) and the ODE state transposed,
+ * Yt fp32 [I, B].  Xt, the tile's rows of Rn transposed, is a tile-local CSR over items: xt_ptr int64 [I + 1], xt_slot
+ * int32 (the slot within the tile, ascending inside an item), xt_val fp32, nxt entries.  No float atomics: every output
+ * has one owner and every sum a fixed order, so two runs on the same inputs give the same bits.
+ * chaorec_bspm_check_shape: CHAOREC_E_INVALID unless B is as above and m a multiple of 4 in [4, 128].
+ * chaorec_bspm_long_row(): a row of P with more entries is shared by the four waves of a last_step workgroup.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_bspm_check_shape(int64_t I, int64_t B, int64_t m);
+int64_t chaorec_bspm_long_row(void);
+/* Z[b, :] = sum_e x_val[e] F[x_item[e], :] over slot b's entries x_ptr[b] .. x_ptr[b + 1] in order (x_ptr int64 [B + 1],
+ * nx entries); F fp32 [I, m], Z fp32 [B, m] written whole. */
+int chaorec_bspm_project_f32(const int64_t *x_ptr, const int32_t *x_item, const float *x_val, int64_t nx, const float *F,
+                             int64_t I, int64_t B, int64_t m, float *Z, void *stream);
+/* Y0t[j, :] = beta idlT[j, :] + sum_{i in P_j} P_ji Xt[i, :], the entries of P_j in CSR order; only the stored entries of
+ * Xt are walked.  idlT fp32 [I, B] may be NULL when beta is 0.  Y0t fp32 [I, B] written whole. */
+int chaorec_bspm_seed_f32(const int64_t *p_ptr, const int32_t *p_col, const float *p_val, int64_t nnz, int64_t I,
+                          const int64_t *xt_ptr, const int32_t *xt_slot, const float *xt_val, int64_t nxt, int64_t B,
+                          float beta, const float *idlT, float *Y0t, void *stream);
+/* scores[b, j] = Yt[j, b] - h (P Yt)[j, b] with the SpMM epilogue's roundings for alpha = -h, beta = 1, then mask_value at
+ * the (j, slot) pairs of xt_ptr / xt_slot (xt_ptr NULL: no mask); scores fp32 [B, I] row-major, written whole, not Yt's
+ * memory.  h = 0: the masked transpose of Yt, bit for bit. */
+int chaorec_bspm_last_step_f32(const int64_t *p_ptr, const int32_t *p_col, const float *p_val, int64_t nnz, int64_t I,
+                               const float *Yt, int64_t B, float h, const int64_t *xt_ptr, const int32_t *xt_slot, int64_t nxt,
+                               float mask_value, float *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
