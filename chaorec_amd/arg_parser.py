@@ -42,6 +42,10 @@ def build_parser():
     parser.add_argument('--K_b', type=int, default=1, help='BSPM blurring steps, T_b / tau (stored, never read)')
     parser.add_argument('--T_b', type=float, default=1, help='BSPM blurring time T_b (stored, never read)')
     parser.add_argument('--idl_beta', type=float, default=1, help='BSPM weight of the ideal low-pass term')
+    parser.add_argument('--steps', type=int, default=5, help='CF_Diff diffusion steps')
+    parser.add_argument('--noise_scale', type=float, default=0.1, help='CF_Diff noise scale for noise generating')
+    parser.add_argument('--noise_min', type=float, default=0.0001, help='CF_Diff noise lower bound for noise generating')
+    parser.add_argument('--noise_max', type=float, default=0.02, help='CF_Diff noise upper bound for noise generating')
     parser.add_argument('--n_mca', type=int, default=2, help='MCLN counterfactual layer.')
     parser.add_argument('--prompt_num', type=float, default=0.1, help='prompt modal numbers.')
     parser.add_argument('--neg_weight', type=float, default=0.1, help='weak modal weight.')

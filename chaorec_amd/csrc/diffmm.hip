@@ -21,7 +21,8 @@ constexpr int DM_BITS = 24;       // random bits of a uniform
 // the bit table, and every lane then writes 8 float4 of x_in.  plain: x_in = x0.  Otherwise
 //   x_t = fl(fl(a x0) + fl(s n)),  x_in = kept ? fl(2 x_t) : 0
 // n = noise[b, i] or normal(seed, step, 2 salt, u, i); kept = keep[b, i] != 0 or uniform(seed, step, 2 salt + 1, u, i) < 1/2:
-// the place in the batch is not part of a draw's key.  Columns I .. ld of a row are written 0.
+// the place in the batch is not part of a draw's key.  Columns I .. ld of a row are written 0.  plain == 2: x_in = x_t, no
+// dropout and no keep draw (chaorec_diffmm_rows_noised_f32: CF_Diff drops out after its encoder, not before).
 template <class = void>
 static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
     const int64_t *__restrict__ users, int64_t B, int64_t U, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -34,7 +35,7 @@ static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
   const bool live = b < B;
   const int64_t u = live ? users[b] : -1;
   const VaeHistRow hr = vae_hist_row(rowptr, u, U);
-  const float a = (live && !plain) ? a_row[b] : 1.f, s = (live && !plain) ? s_row[b] : 0.f;
+  const float a = (live && plain != 1) ? a_row[b] : 1.f, s = (live && plain != 1) ? s_row[b] : 0.f;
   const uint64_t key_n = draw_key(seed, step, 2 * salt), key_k = draw_key(seed, step, 2 * salt + 1);
   for (int64_t c0 = 0; c0 < ld; c0 += DM_CH) {      // the same trip count for every wave of the workgroup
     words[wave][lane] = 0u;
@@ -60,12 +61,12 @@ static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
           float x = 0.f;
           if (i < I) {
             const float x0 = ((word >> ((4 * v + q) & 31)) & 1u) ? 1.f : 0.f;
-            if (plain) x = x0;
+            if (plain == 1) x = x0;
             else {
               const float n = noise ? noise[b * I + i] : draw_normal<DM_BITS>(key_n, (uint64_t)u, (uint64_t)i);
-              const bool kept = keep ? keep[b * I + i] != 0 : draw_uniform<DM_BITS>(key_k, (uint64_t)u, (uint64_t)i) < 0.5f;
+              const bool kept = plain == 2 || (keep ? keep[b * I + i] != 0 : draw_uniform<DM_BITS>(key_k, (uint64_t)u, (uint64_t)i) < 0.5f);
               const float xt = add_rn(mul_rn(a, x0), mul_rn(s, n));
-              x = kept ? mul_rn(2.f, xt) : 0.f;
+              x = plain == 2 ? xt : (kept ? mul_rn(2.f, xt) : 0.f);
             }
           }
           o[q] = x;
@@ -303,7 +304,19 @@ extern "C" int chaorec_diffmm_rows_f32(const int64_t *users, int64_t B, int64_t 
   if (ld != (I + 3) / 4 * 4 || !dm_aligned16(x_in)) return fail(CHAOREC_E_INVALID, "diffmm_rows: ld=%lld must be I rounded up to 4, x_in 16-byte aligned", (long long)ld);
   if (B == 0) return CHAOREC_OK;
   hipLaunchKernelGGL(dm_rows_kernel<>, dim3((unsigned)((B + DM_ROWS - 1) / DM_ROWS)), dim3(64 * DM_ROWS), 0, (hipStream_t)stream, users,
-                     B, U, rowptr, col, I, ld, a_row, s_row, noise, keep, seed, step, (uint64_t)salt, plain, x_in, bits, (I + 31) / 32);
+                     B, U, rowptr, col, I, ld, a_row, s_row, noise, keep, seed, step, (uint64_t)salt, plain ? 1 : 0, x_in, bits, (I + 31) / 32);
+  return check_launch("dm_rows_kernel");
+}
+
+extern "C" int chaorec_diffmm_rows_noised_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                              int64_t I, int64_t ld, const float *a_row, const float *s_row, const float *noise,
+                                              uint64_t seed, uint64_t step, uint32_t salt, float *x_t, uint32_t *bits, void *stream) {
+  if (!users || !rowptr || !col || !x_t || !bits || !a_row || !s_row) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: NULL argument");
+  if (B < 0 || U < 0 || I <= 0 || I > ((int64_t)1 << 31) - 256) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: B=%lld I=%lld", (long long)B, (long long)I);
+  if (ld != (I + 3) / 4 * 4 || !dm_aligned16(x_t)) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: ld=%lld must be I rounded up to 4, x_t 16-byte aligned", (long long)ld);
+  if (B == 0) return CHAOREC_OK;
+  hipLaunchKernelGGL(dm_rows_kernel<>, dim3((unsigned)((B + DM_ROWS - 1) / DM_ROWS)), dim3(64 * DM_ROWS), 0, (hipStream_t)stream, users,
+                     B, U, rowptr, col, I, ld, a_row, s_row, noise, (const uint8_t *)nullptr, seed, step, (uint64_t)salt, 2, x_t, bits, (I + 31) / 32);
   return check_launch("dm_rows_kernel");
 }
 

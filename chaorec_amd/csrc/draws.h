@@ -17,6 +17,8 @@ __device__ __forceinline__ float draw_uniform(uint64_t key, uint64_t a, uint64_t
   const uint64_t r = mix64(key ^ mix64((a << 32) ^ b));
   return ((float)(r >> (64 - BITS)) + 0.5f) * (1.0f / (float)(1 << BITS));
 }
+// the 64 bits draw_uniform cuts its value from: 64 fair coins of (key, a, b) (cfdiff.hip's rate-1/2 keep flags)
+__device__ __forceinline__ uint64_t draw_bits64(uint64_t key, uint64_t a, uint64_t b) { return mix64(key ^ mix64((a << 32) ^ b)); }
 template <int BITS>
 __device__ __forceinline__ float draw_normal(uint64_t key, uint64_t a, uint64_t c) {   // Box-Muller
   const float u1 = draw_uniform<BITS>(key, a, 2 * c), u2 = draw_uniform<BITS>(key, a, 2 * c + 1);

@@ -12,7 +12,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import dataload
-from .Model import (AdaGCL, BM3, BPRMF, BSPM, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, Grade, GraphAug, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MHRec, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
+from .Model import (AdaGCL, BM3, BPRMF, BSPM, CF_Diff, COHESION, DCCF, DGCF, DDRec, DHCF, DRAGON, DualGNN, DualVAE, FKAN_GCF, FREEDOM, GRCN, GUME, Grade, GraphAug, HCCF, LATTICE, LGMRec, LightGCL, LayerGCN, LightGCN, LightGT, MCLN, MENTOR, MGAT, MGCL, MGCN, MHRec, MICRO, MMGCN, MMSSL, MVGAE, MacridVAE, DiffMM, MultVAE, NCL, NGCF, MMGCL, POWERec, SelfCF, SGL, SimGCL, SLMRec,
                     SMORE, VBPR, VGCL, XSimGCL)
 from .arg_parser import load_yaml_config, parse_args
 from .train_and_evaluate import train_and_evaluate
@@ -175,6 +175,9 @@ def build_model(args, num_user, num_item, train_data, user_item_dict, v_feat, t_
         # sharpened and ranked, csrc/bspm.hip.  The reference passes args.K_s where T_b belongs; neither is read, T_b it is here
         'BSPM': lambda: BSPM(num_user, num_item, train_data, user_item_dict, args.K_s, args.T_s, args.K_b, args.T_b,
                              args.idl_beta, device),
+        # (main.py:372-373) the cross-attention denoiser: its rows come from the history CSR, its attention is csrc/cfdiff.hip
+        'CF_Diff': lambda: CF_Diff(num_user, num_item, user_item_dict, args.noise_scale, args.noise_min, args.noise_max,
+                                   args.steps, args.learning_rate, device, seed=args.seed),
     }
     if args.Model == 'MHRec':      # Model/MHRec.py:578, :604-612 read user_graph_dict.npy and the hyperedge files there
         MHRec.data_dir = os.path.join(args.data_root, args.data_path)
@@ -222,8 +225,9 @@ def main(argv=None):
         model = build_model(args, num_user, num_item, train_data, user_item_dict, v_feat, t_feat, device)
         model.to(device)
         # reference: torch.optim.Adam (main.py:397); same update, one fused launch per tensor
-        # (BSPM has no parameter: no optimizer, as its branch of train_and_evaluate never steps one)
-        optimizer = None if args.Model == 'BSPM' else FusedAdam([{'params': model.parameters(), 'lr': args.learning_rate}])
+        # (BSPM has no parameter: no optimizer, as its branch of train_and_evaluate never steps one; CF_Diff's epoch creates its
+        # own AdamW over CAM_AE, train_and_evaluate.py:317)
+        optimizer = None if args.Model in ('BSPM', 'CF_Diff') else FusedAdam([{'params': model.parameters(), 'lr': args.learning_rate}])
         current = train_and_evaluate(model, train_loader, val_data, test_data, optimizer, args.num_epoch,
                                      model_name=args.Model, topk=args.topk, patience=args.patience,
                                      graph=not args.no_graph)

@@ -10,7 +10,7 @@ from .ops import _f32, _f32c, _need_cuda, _ptr, _stream, col_sum
 from .ops_dense import gemm_nn_bf16x3, gemm_raw, gemm_tn_bf16x3
 
 __all__ = [
-    "DIFFMM_D", "diffmm_check_shape", "diffmm_tiles", "diffmm_rows_per_block", "diffmm_ld", "diffmm_rows", "_diffmm_big",
+    "DIFFMM_D", "diffmm_check_shape", "diffmm_tiles", "diffmm_rows_per_block", "diffmm_ld", "diffmm_rows", "diffmm_rows_noised", "_diffmm_big",
     "diffmm_out_loss_raw", "_DiffMMDenoiseLoss", "diffmm_denoise_loss",
 ]
 
@@ -62,6 +62,25 @@ def diffmm_rows(users, rowptr, col, num_item, a_row=None, s_row=None, noise=None
                                         _ptr(None if plain else noise), _ptr(None if plain else keep), int(seed), int(step),
                                         int(salt), int(bool(plain)), _ptr(x), _ptr(bits), _stream())
     return x[:, :I], bits
+
+
+def diffmm_rows_noised(users, rowptr, col, num_item, a_row, s_row, noise=None, seed=0, step=0, salt=0):
+    """users int64 [B] -> x_t fp32 [B, I] = a x0 + s n from the history CSR, no input dropout (csrc/diffmm.hip's rows launch
+    through chaorec_diffmm_rows_noised_f32).  n: noise [B, I] or, None, the counter RNG keyed (seed, step, 2 salt, user, item)."""
+    _need_cuda(users, rowptr, col, a_row, s_row, noise)
+    users = users.to(torch.int64).contiguous()
+    B, I, U = users.numel(), int(num_item), rowptr.numel() - 1
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32:
+        raise TypeError("diffmm_rows_noised: rowptr must be int64 and col int32")
+    a_row, s_row = _f32("diffmm", a_row, "a_row", (B,)), _f32("diffmm", s_row, "s_row", (B,))
+    if noise is not None:
+        noise = _f32("diffmm", noise, "noise", (B, I))
+    ld = diffmm_ld(I)
+    x = torch.empty((B, ld), dtype=torch.float32, device=users.device)
+    bits = torch.empty((B, (I + 31) // 32), dtype=torch.int32, device=users.device)
+    _lib.load().chaorec_diffmm_rows_noised_f32(_ptr(users), B, U, _ptr(rowptr), _ptr(col), I, ld, _ptr(a_row), _ptr(s_row), _ptr(noise),
+                                               int(seed), int(step), int(salt), _ptr(x), _ptr(bits), _stream())
+    return x[:, :I]
 
 
 def _diffmm_big(rows):

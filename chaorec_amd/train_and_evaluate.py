@@ -24,7 +24,8 @@ BUILD_FIRST = ("LATTICE", "MICRO")                # reference train_and_evaluate
 NO_CAPTURE = ("NCL", "VGCL", "LATTICE", "MICRO", "SGL", "SelfCF", "MMGCL", "LightGT", "MMSSL", "DiffMM", "AdaGCL",    # (MMSSL, AdaGCL: several optimizers per batch, their own loops)
               "GraphAug",             # (its views' structure -- the random entries -- changes every step; the plain loss() loop below)
               "Grade",                # (four optimizers per batch, its own loop)
-              "MHRec")                # (three phases per epoch, the hypergraphs its loss() reads are rebuilt in the second)
+              "MHRec",                # (three phases per epoch, the hypergraphs its loss() reads are rebuilt in the second)
+              "CF_Diff")              # (user-id batches, an AdamW of its own over CAM_AE, host-sampled timesteps)
 
 
 def _train_epoch_in_launch(model, loader, optimizer, graphed):
@@ -188,6 +189,29 @@ def _train_epoch_diffmm(model, train_loader, optimizer, diffusion_loader=None):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_cfdiff(model, train_loader, diffusion_loader=None):
+    """reference train_and_evaluate.py:316-330: one pass over shuffled user batches, AdamW(weight_decay = 0) over CAM_AE created
+    anew every epoch (its moments restart, as there).  A batch is its user ids: both hops' rows come from the history CSR
+    (model.diffusion_step).  diffusion_loader: by default a dataload.DeviceUserBatches at the train loader's batch size, kept
+    on the model between epochs."""
+    if diffusion_loader is None:
+        diffusion_loader = model.__dict__.get("_diffusion_loader")
+        if diffusion_loader is None:
+            from .dataload import DeviceUserBatches
+            diffusion_loader = model.__dict__["_diffusion_loader"] = DeviceUserBatches(
+                model.num_user, train_loader.batch_size, model.device, getattr(train_loader, "seed", 42))
+    optimizer = torch.optim.AdamW(model.CAM_AE.parameters(), lr=model.learning_rate, weight_decay=0)
+    sum_loss = None
+    for users in diffusion_loader:
+        optimizer.zero_grad()
+        loss = model.diffusion_step(users)
+        loss.backward()
+        optimizer.step()
+        d = loss.detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    return float(sum_loss.item()) if sum_loss is not None else 0.0
+
+
 def _train_epoch_mhrec(model, train_loader, optimizer, diffusion_loaders=None, times=None):
     """reference train_and_evaluate.py:331-512 in its three phases: (1) one pass of the visual diffusion loader, then one of the
     textual, each denoiser under an Adam optimizer created anew every epoch (:333-336: their moments restart); (2) the two
@@ -252,6 +276,8 @@ def train(model, train_loader, optimizer, model_name="LightGCN", graphed=None):
         return _train_epoch_mmssl(model, train_loader, optimizer)
     if model_name == "DiffMM":
         return _train_epoch_diffmm(model, train_loader, optimizer)
+    if model_name == "CF_Diff":
+        return _train_epoch_cfdiff(model, train_loader)
     if model_name == "AdaGCL":
         return _train_epoch_adagcl(model, train_loader, optimizer)
     if model_name == "Grade":

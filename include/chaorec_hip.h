@@ -1303,6 +1303,11 @@ int chaorec_diffmm_rows_f32(const int64_t *users, int64_t B, int64_t U, const in
                             int64_t ld, const float *a_row, const float *s_row, const float *noise, const uint8_t *keep,
                             uint64_t seed, uint64_t step, uint32_t salt, int32_t plain, float *x_in, uint32_t *bits,
                             void *stream);
+/* The same launch with x_in = x_t: the noised rows themselves, no input dropout and no keep draw (CF_Diff, Model/CF_Diff.py:
+ * 84-96, encodes x_t and drops out after the encoder).  Arguments, keying of the noise and outputs as above. */
+int chaorec_diffmm_rows_noised_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
+                                   int64_t I, int64_t ld, const float *a_row, const float *s_row, const float *noise,
+                                   uint64_t seed, uint64_t step, uint32_t salt, float *x_t, uint32_t *bits, void *stream);
 /* The output layer of Denoise.forward (:468-471) with GaussianDiffusion.training_losses' mse, weight, diff_loss and gc_loss
  * (:640-658) and the mean over the batch of both, in one pass; model_output, the squared error and usr_model_embeds do
  * not exist.  out = h W_out^T + b_out (h [B, H] row stride ldh, W_out [I, H] row stride ldw), err = out - x0 (x0 from bits
@@ -1495,6 +1500,43 @@ int chaorec_bspm_seed_f32(const int64_t *p_ptr, const int32_t *p_col, const floa
 int chaorec_bspm_last_step_f32(const int64_t *p_ptr, const int32_t *p_col, const float *p_val, int64_t nnz, int64_t I,
                                const float *Yt, int64_t B, float h, const int64_t *xt_ptr, const int32_t *xt_slot, int64_t nxt,
                                float mask_value, float *scores, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * CF_Diff (Model/CF_Diff.py:108-111) -- csrc/cfdiff.hip.  Additive to ABI 16: new names only.  The core of
+ * nn.MultiheadAttention(16, 4, dropout = 0.5): 4 heads of width 4 over L tokens, never forming an [L, L] array.  q, k, v, out
+ * and their gradients fp32 [B, L, 16] contiguous, 16-byte aligned, head h in columns 4h .. 4h + 3, one L for queries and
+ * keys; scores <q, k> / 2.  fp32, no float atomics, no scratch; every output row has one owner and every sum runs in
+ * ascending index order (in segments of 32 terms): the same bits every run.
+ * A workgroup owns one (b, head) and stages 32 bytes (forward, query pass) or 48 bytes (key pass) per token in LDS, at most
+ * 64 KiB: chaorec_cfdiff_max_len() = 1365, and two workgroups are resident on a CU at any accepted L.
+ * chaorec_cfdiff_check_shape: CHAOREC_E_INVALID unless 1 <= L <= max_len and 1 <= B <= 2^28.
+ *
+ * The keep flags of the rate-1/2 dropout on the probabilities: training == 0: none.  Otherwise keep uint8 [B, 4, L, L]
+ * (given; non-zero = kept) or, keep NULL, device draws: flag (b, head, query i, key j) is bit (j & 63) of the 64-bit draw
+ *   mix64(key ^ mix64((((b0 + b) * 4 + head) << 32) ^ ((i << 20) | (j >> 6)))),  key = mix64(mix64(seed ^ salt) + state[1])
+ * (csrc/draws.h: draw_bits64 over draw_key; state int64 [2] as the step tick keeps it) -- one draw serves the 64 keys of an
+ * aligned key word, a set bit is a kept entry.  b0 is the slot of the launch's first row (0 <= b0, b0 + B <= 2^30): a row's
+ * flags depend on its slot, not on the launch geometry or on the launch it is part of.
+ * --------------------------------------------------------------------------------------------------------------- */
+int64_t chaorec_cfdiff_max_len(void);
+int chaorec_cfdiff_check_shape(int64_t B, int64_t L);
+/* out = (keep ? 2 P : 0) V (training == 0: P V), P = softmax over ALL keys of the scores (F.dropout after the softmax); a
+ * query whose keys are all dropped gives exact zeros.  lse fp32 [B, 4, L] = log sum_j exp(score). */
+int chaorec_cfdiff_attn_fwd_f32(const float *q, const float *k, const float *v, int64_t B, int64_t L, int32_t training,
+                                const uint8_t *keep, uint64_t seed, const int64_t *state, uint32_t salt, int64_t b0, float *out,
+                                float *lse, void *stream);
+/* dq, dk, dv from the forward's operands, out, lse and dout, with the same draw arguments: the flags are redrawn, no mask is
+ * stored.  D_i = <dout_i, out_i>, dS_ij = P_ij (2 keep_ij <dout_i, v_j> - D_i), dq_i = 1/2 sum_j dS_ij k_j,
+ * dk_j = 1/2 sum_i dS_ij q_i, dv_j = sum_i 2 keep_ij P_ij dout_i.  Two launches: the query pass writes dq and rnorm fp32
+ * [B, 4, L] (1 / sum_j exp(score - lse): the rounding of the stored lse, taken out of P again), the key pass reads it. */
+int chaorec_cfdiff_attn_bwd_f32(const float *q, const float *k, const float *v, const float *out, const float *lse,
+                                const float *dout, int64_t B, int64_t L, int32_t training, const uint8_t *keep, uint64_t seed,
+                                const int64_t *state, uint32_t salt, int64_t b0, float *dq, float *dk, float *dv, float *rnorm,
+                                void *stream);
+/* The device-drawn flags of (seed, state[1], salt, b0) as bytes, keep uint8 [B, 4, L, L]: for the plain composition and
+ * the tests, which reproduce a device-drawn step with them. */
+int chaorec_cfdiff_attn_keep_u8(int64_t B, int64_t L, uint64_t seed, const int64_t *state, uint32_t salt, int64_t b0,
+                                uint8_t *keep, void *stream);
 
 #ifdef __cplusplus
 }
