@@ -7,7 +7,6 @@ Bounds: every reference quantity is stored with its own fp32-vs-fp64 deviation; 
 import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -181,8 +180,8 @@ def test_model_surface():
 
 
 def test_cli_yaml_and_training_branch():
-    from chaorec_amd import main as cli
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs, main as cli
+    from chaorec_amd.registry import MODELS
     from chaorec_amd.arg_parser import load_yaml_config, parse_args
     cfg = load_yaml_config("AdaGCL")
     assert cfg["hyper_parameters"] == ["n_layers", "learning_rate", "reg_weight", "ssl_alpha", "ssl_temp"]
@@ -193,12 +192,12 @@ def test_cli_yaml_and_training_branch():
         setattr(args, p, cfg[p][0])
     m = cli.build_model(args, c["U"], c["I"], c["edges"], ah.user_item_dict(c["edges"]), None, None, torch.device("cpu"))
     assert type(m).__name__ == "AdaGCL" and (m.ssl_temp, m.ssl_alpha, m.reg_weight, m.n_layers) == (0.5, 0.1, 0.001, 2)
-    needs = re.search(r"needs_feat = args\.Model in \(([^)]*)\)", inspect.getsource(cli.main)).group(1)
-    assert '"AdaGCL"' not in needs
-    assert "AdaGCL" in te.NO_CAPTURE and "AdaGCL" not in te.MMGCN_STYLE + te.PRE_EPOCH + te.E_STEP + te.BUILD_FIRST
-    src = inspect.getsource(te._train_epoch_adagcl)
+    spec = MODELS["AdaGCL"]
+    assert not spec.features
+    assert not spec.capture and spec.batch == "triple" and not spec.pre_epoch and spec.before_step is None and not spec.build_first
+    src = inspect.getsource(epochs._train_epoch_adagcl)
     assert "eps=0.001" in src and src.count("opt.step()") == 3 and "opt_gen_1.step()" in src and "opt_gen_2.step()" in src
-    assert 'model_name == "AdaGCL"' in inspect.getsource(te.train)
+    assert spec.epoch is epochs._train_epoch_adagcl
 
 
 def test_ops_raise_on_cpu_tensors():

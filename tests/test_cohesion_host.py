@@ -4,6 +4,7 @@ the fused node's float32 restatement (the contract's order, chunked and unchunke
 float64 autograd; and the part of the model's surface that needs no device (the constructor's arguments, the methods, the
 plumbing)."""
 import inspect
+import json
 import os
 import sys
 
@@ -155,7 +156,7 @@ def test_nan_in_the_id_columns_of_g_stays_out():
 
 
 def test_model_surface():
-    from chaorec_amd import main, train_and_evaluate
+    from chaorec_amd.registry import MODELS
     from chaorec_amd.arg_parser import load_yaml_config, parse_args
     from chaorec_amd.Model import COHESION
     args = [p for p in inspect.signature(COHESION.__init__).parameters][1:]
@@ -165,14 +166,16 @@ def test_model_surface():
                  "build_representation", "process_user_item_representation", "get_knn_adj_mat", "get_norm_adj_mat"):
         assert callable(getattr(COHESION, name)), name
     assert COHESION.fused_aggregation is True and COHESION.user_graph_path is None and COHESION.bwd_chunk == 64
-    assert "COHESION" in train_and_evaluate.PRE_EPOCH
+    assert MODELS["COHESION"].pre_epoch
     assert parse_args(["--Model", "COHESION"]).Model == "COHESION"
     cfg = load_yaml_config("COHESION")
     assert cfg["mm_image_weight"] == [0.1] and cfg["reg_weight"] == [0.001] and cfg["dropout"] == [0] and cfg["n_layers"] == [1]
     assert set(cfg["hyper_parameters"]) == {"reg_weight", "learning_rate", "dropout", "n_layers", "mm_image_weight", "ii_topk", "mm_layers"}
-    src = inspect.getsource(main.build_model)
-    assert "'COHESION'" in src and "COHESION.user_graph_path" in src and "args.mm_image_weight" in src
-    assert '"COHESION"' in inspect.getsource(main.main)                   # needs_feat
+    # what build_model hands the constructor and sets on the class (tests/test_model_registry.py replays this record against the table)
+    built = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_constructor_args.json")))["COHESION"]
+    assert built[0] == "COHESION" and built[3] == {"COHESION.user_graph_path": "DATA_ROOT/sports/user_graph_dict.npy"}
+    assert built[1][-2] == cfg["mm_image_weight"][0] and built[1][-1] == "device"
+    assert MODELS["COHESION"].features
 
 
 def test_header_declares_the_entries():

@@ -123,9 +123,10 @@ def test_cli_flags_and_yaml_grid():
 
 
 def test_main_table_has_dgcf():
-    import inspect
-    from chaorec_amd import main
-    assert "'DGCF': lambda: DGCF(" in inspect.getsource(main.build_model)
+    from chaorec_amd import registry
+    from chaorec_amd.Model import DGCF
+    spec = registry.MODELS["DGCF"]
+    assert registry.M.DGCF is DGCF and callable(spec.build) and spec.capture and spec.epoch is None and not spec.features
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])

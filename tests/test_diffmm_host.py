@@ -177,7 +177,8 @@ def test_batch_rows_come_from_the_history_csr(fx):
 
 
 def test_wiring():
-    from chaorec_amd import main as cmain, train_and_evaluate as te
+    from chaorec_amd import epochs, main as cmain
+    from chaorec_amd.registry import MODELS
     from chaorec_amd.arg_parser import load_yaml_config, parse_args
     args = parse_args(["--Model", "DiffMM", "--e_loss", "0.5", "--rebuild_k", "3"])
     assert (args.e_loss, args.ris_lambda, args.rebuild_k) == (0.5, 0.5, 3)
@@ -185,7 +186,7 @@ def test_wiring():
     cfg = load_yaml_config("DiffMM")
     assert cfg["hyper_parameters"] == ["e_loss", "learning_rate", "reg_weight", "ssl_alpha", "ris_lambda", "ssl_temp", "rebuild_k"]
     assert cfg["e_loss"] == [0.01] and cfg["rebuild_k"] == [1] and cfg["n_layers"] == [1]
-    assert "DiffMM" in te.NO_CAPTURE and callable(te._train_epoch_diffmm)
+    assert not MODELS["DiffMM"].capture and MODELS["DiffMM"].epoch is epochs._train_epoch_diffmm
     c = mh.small_case()
     for p in cfg["hyper_parameters"]:
         setattr(args, p, cfg[p][0])

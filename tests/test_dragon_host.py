@@ -3,6 +3,7 @@ the co-occurrence top-N against what the reference's own script wrote for baby, 
 the synthetic graph, the epoch sample's law against the epoch graph the reference's topk_sample drew; and the part of the
 model's surface that needs no device (the constructor's arguments, the methods)."""
 import inspect
+import json
 import os
 import sys
 
@@ -133,7 +134,7 @@ def test_generator_is_uniform_enough():
 
 
 def test_model_surface():
-    from chaorec_amd import main, train_and_evaluate
+    from chaorec_amd.registry import MODELS
     from chaorec_amd.arg_parser import load_yaml_config, parse_args
     from chaorec_amd.Model import DRAGON
     args = [p for p in inspect.signature(DRAGON.__init__).parameters][1:]
@@ -141,9 +142,11 @@ def test_model_surface():
                     "reg_weight", "n_layers", "ii_topk", "uu_topk", "mm_image_weight", "aggr_mode", "device"]     # main.py:284
     for name in ("forward", "loss", "pre_epoch_processing", "gene_ranklist", "topk_sample", "init_weight", "get_knn_adj_mat"):
         assert callable(getattr(DRAGON, name)), name
-    assert "DRAGON" in train_and_evaluate.PRE_EPOCH
+    assert MODELS["DRAGON"].pre_epoch and MODELS["DRAGON"].features
     a = parse_args(["--Model", "DRAGON"])
     assert (a.uu_topk, a.ii_topk) == (10, 10)
     cfg = load_yaml_config("DRAGON")
     assert cfg["uu_topk"] == [40] and cfg["ii_topk"] == [10] and cfg["lambda_coeff"] == [0.6] and cfg["reg_weight"] == [0.01]
-    assert "'DRAGON'" in inspect.getsource(main.build_model)
+    # what build_model hands the constructor and sets on the class (tests/test_model_registry.py replays this record against the table)
+    built = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_constructor_args.json")))["DRAGON"]
+    assert built[0] == "DRAGON" and built[3] == {"DRAGON.user_graph_path": "DATA_ROOT/sports/user_graph_dict.npy"}

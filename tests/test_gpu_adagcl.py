@@ -359,7 +359,7 @@ def test_generated_views_meet_the_reference():
 
 def test_three_steps_of_the_training_loop():
     """train_and_evaluate's AdaGCL branch -- three Adam optimizers, the generators stepped twice -- over one batch three times."""
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs as te
     c, w, g, _ = case()
     drs = ah.draws(c, ah.N_STEPS, seed_offset=2)
     m = make_model(w)

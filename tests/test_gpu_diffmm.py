@@ -383,7 +383,7 @@ def test_epoch_finite_and_no_dense_interaction_matrix(dev):
     memory would be at least that.  What the epoch legitimately holds is far below it, from the shapes: the denoisers with
     gradients and Adam moments 4 x 2 x (1000 (I + 10) + 1000 I + ...) x 4 B = 0.26 GB, some dozens of [U + I, 64] tables of the
     graph half at 35 MB each, and a dozen [1024, I] row tensors at 17 MB each."""
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs as te
     from chaorec_amd.Model import DiffMM
     from chaorec_amd.dataload import DeviceUserBatches
     from chaorec_amd.optim import FusedAdam

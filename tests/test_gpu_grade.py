@@ -292,7 +292,7 @@ def test_three_steps_of_the_training_loop():
 
     Measured on the MI355X: largest deviation / bound 0.97, at the update of generator_3.decoder.decoder.1.weight (2.075e-4
     against 2.141e-4; 1.73 before the decoder's gradients were accumulated in float64); the next largest is 0.57."""
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs as te
     c, w, g, _ = case()
     drs = gh.draws(c, gh.N_STEPS, seed_offset=2)
     m = make_model(w)

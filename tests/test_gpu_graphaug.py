@@ -269,11 +269,11 @@ def test_model_view_values(fused):
 
 
 def test_model_trajectory_through_the_training_loop():
-    from chaorec_amd import train_and_evaluate
+    from chaorec_amd import registry, train_and_evaluate
     c, w, g, _ = case()
     m = make_model()
     feed(m, gh.draws(c, gh.N_STEPS, seed_offset=2))
-    assert "GraphAug" in train_and_evaluate.NO_CAPTURE
+    assert not registry.MODELS["GraphAug"].capture
     opt = torch.optim.Adam(m.parameters(), lr=gh.LR)
     total = train_and_evaluate.train(m, [batch()] * gh.N_STEPS, opt, "GraphAug")
     within(total, float(g["traj_losses"].sum()), g["dev_traj_losses"], "sum of the trajectory's losses")

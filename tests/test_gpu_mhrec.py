@@ -266,7 +266,7 @@ def test_one_epoch_of_the_training_loop():
     1.278e-4 (4 x the reference's own 3.195e-5), at an entry (hidden unit 247, input column 4) whose gradient is a sum of 128
     terms cancelling about 1000 : 1; the same fp32 lines on the host give 3.7e-5 with 8 threads and 6.3e-5 with one, the f32 MFMA
     GEMMs 4.0e-4.  In float64 it is 8e-6."""
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs as te
     c, w, g, dr = case()
     m = make_model(w)
     for mod in range(2):

@@ -6,7 +6,6 @@ Bounds: every reference quantity is stored with its own fp32-vs-fp64 deviation; 
 import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -177,8 +176,8 @@ def test_model_surface():
 
 
 def test_cli_yaml_and_training_branch():
-    from chaorec_amd import main as cli
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs, main as cli
+    from chaorec_amd.registry import MODELS
     from chaorec_amd.arg_parser import load_yaml_config, parse_args
     cfg = load_yaml_config("Grade")
     assert cfg["hyper_parameters"] == ["n_layers", "learning_rate", "reg_weight", "ssl_alpha", "ssl_temp", "ssl_temp2", "noise_alpha"]
@@ -194,20 +193,20 @@ def test_cli_yaml_and_training_branch():
                         torch.from_numpy(c["t_feat"]), torch.device("cpu"))
     assert type(m).__name__ == "Grade"
     assert (m.ssl_temp, m.ssl_alpha, m.ssl_temp2, m.noise_alpha, m.reg_weight, m.n_layers) == (0.3, 0.2, 0.3, 0.2, 0.1, 5)
-    needs = re.search(r"needs_feat = args\.Model in \(([^)]*)\)", inspect.getsource(cli.main)).group(1)
-    assert '"Grade"' in needs
-    assert "Grade" in te.NO_CAPTURE and "Grade" not in te.MMGCN_STYLE + te.PRE_EPOCH + te.E_STEP + te.BUILD_FIRST
-    src = inspect.getsource(te._train_epoch_grade)
+    spec = MODELS["Grade"]
+    assert spec.features
+    assert not spec.capture and spec.batch == "triple" and not spec.pre_epoch and spec.before_step is None and not spec.build_first
+    src = inspect.getsource(epochs._train_epoch_grade)
     assert src.count("torch.optim.Adam(") == 4 and src.count("opt.step()") == 2 and "eps=" not in src
     order = [src.index(s) for s in ("model.loss_1(", "model.bpr_reg_loss(", "model.gen_loss(", "opt_gen_1.step()", "opt_gen_2.step()",
                                     "opt_gen_3.step()")]
     assert order == sorted(order) and src.index("opt.step()") < src.index("model.bpr_reg_loss(") < src.rindex("opt.step()") < src.index("model.gen_loss(")
-    assert 'model_name == "Grade"' in inspect.getsource(te.train)
+    assert spec.epoch is epochs._train_epoch_grade
 
 
 def test_training_branch_steps_in_the_reference_s_order():
     """The loop's branch over a stand-in model: which loss is stepped by which optimizer, in which order."""
-    from chaorec_amd import train_and_evaluate as te
+    from chaorec_amd import epochs as te
     import types
 
     class Tiny(torch.nn.Module):

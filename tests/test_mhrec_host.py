@@ -183,14 +183,15 @@ def test_diffusion_rows_hold_counts():
 
 
 def test_cli_yaml_and_loop_entries():
-    from chaorec_amd import arg_parser, train_and_evaluate as te
+    from chaorec_amd import arg_parser, epochs
+    from chaorec_amd.registry import MODELS
     a = arg_parser.parse_args(["--Model", "MHRec"])
     assert (a.h_layers, a.num_hypernodes, a.beta1, a.beta2) == (2, 10, 0.5, 0.5)
     cfg = arg_parser.load_yaml_config("MHRec")
     assert set(cfg["hyper_parameters"]) == {"n_layers", "h_layers", "learning_rate", "reg_weight", "uu_topk", "ii_topk", "num_hypernodes",
                                             "ssl_alpha", "ssl_temp", "beta1", "beta2"}
     assert all(isinstance(cfg[k], list) and len(cfg[k]) == 1 for k in cfg["hyper_parameters"])
-    assert "MHRec" in te.NO_CAPTURE and callable(te._train_epoch_mhrec)
+    assert not MODELS["MHRec"].capture and MODELS["MHRec"].epoch is epochs._train_epoch_mhrec
 
 
 def test_diffusion_step_in_double_is_the_restatement():

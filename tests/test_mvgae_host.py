@@ -6,7 +6,6 @@ Bounds: every reference quantity is stored with its own fp32-vs-fp64 deviation; 
 import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -185,10 +184,10 @@ def test_cli_and_yaml():
     m = cli.build_model(args, c["U"], c["I"], c["edges"], mh.user_item_dict(c["edges"]), torch.from_numpy(c["v_feat"]),
                         torch.from_numpy(c["t_feat"]), torch.device("cpu"))
     assert type(m).__name__ == "MVGAE" and (m.kl_weight, m.n_layers) == (0.1, 2) and not hasattr(m, "pre_epoch_processing")
-    needs = re.search(r"needs_feat = args\.Model in \(([^)]*)\)", inspect.getsource(cli.main)).group(1)
-    assert '"MVGAE"' in needs
-    from chaorec_amd import train_and_evaluate as te
-    assert "MVGAE" not in te.MMGCN_STYLE + te.PRE_EPOCH + te.E_STEP + te.BUILD_FIRST
+    from chaorec_amd.registry import MODELS
+    spec = MODELS["MVGAE"]
+    assert spec.features
+    assert spec.batch == "triple" and not spec.pre_epoch and spec.before_step is None and not spec.build_first
 
 
 def test_ops_raise_on_cpu_tensors():

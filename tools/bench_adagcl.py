@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """AdaGCL at sports on the MI355X (measurement only): one eager training step (four losses, three Adam optimizers, as
-train_and_evaluate's branch runs it) with the fused edge work (ops_extra.adagcl_edge_gate / adagcl_edge_keep) against the
+epochs._train_epoch_adagcl runs it) with the fused edge work (ops_extra.adagcl_edge_gate / adagcl_edge_keep) against the
 SAME model with `fused_edges = False`, i.e. the reference's per-edge lines in plain torch over gathered [E, 64] rows; the
 gate node alone (training form, forward + backward) both ways; the keep decision alone both ways; peak memory of each.
 
@@ -87,7 +87,7 @@ def main():
     opt_gen_1 = torch.optim.Adam(m.generator_1.parameters(), lr=0.001, weight_decay=0)
     opt_gen_2 = torch.optim.Adam(filter(lambda p: p.requires_grad, m.generator_2.parameters()), lr=0.001, weight_decay=0, eps=0.001)
 
-    def step():                            # train_and_evaluate._train_epoch_adagcl's body
+    def step():                            # epochs._train_epoch_adagcl's body
         opt.zero_grad()
         opt_gen_1.zero_grad()
         opt_gen_2.zero_grad()

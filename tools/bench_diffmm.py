@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from chaorec_amd import dataload, ops_extra, train_and_evaluate as te  # noqa: E402
+from chaorec_amd import dataload, epochs, ops_extra  # noqa: E402
 from chaorec_amd.Model import DiffMM  # noqa: E402
 from chaorec_amd.optim import FusedAdam  # noqa: E402
 from tools.bench_mvgae import compare  # noqa: E402
@@ -127,7 +127,7 @@ def main():
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats()
                 t0 = time.perf_counter()
-                te._train_epoch_diffmm(m, sampler, opt)
+                epochs._train_epoch_diffmm(m, sampler, opt)
                 torch.cuda.synchronize()
                 if k:
                     ts_.append(time.perf_counter() - t0)

@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 from chaorec_amd import dataload, main as cmain, train_and_evaluate as te  # noqa: E402
 from chaorec_amd.arg_parser import load_yaml_config, parse_args  # noqa: E402
 from chaorec_amd.optim import FusedAdam  # noqa: E402
+from chaorec_amd.registry import MODELS  # noqa: E402
 
 ALL = ["LightGCN", "NGCF", "LayerGCN", "BPR", "VBPR", "MGCN", "FREEDOM", "MMGCN", "SimGCL", "XSimGCL", "NCL", "SelfCF", "SLMRec", "MCLN",
        "DHCF", "LGMRec", "POWERec", "SMORE", "GUME", "MMGCL", "FKAN_GCF", "VGCL", "DDRec", "DCCF", "MICRO", "LATTICE", "MENTOR", "HCCF",
@@ -34,20 +35,19 @@ for name in models:
         for p in cfg["hyper_parameters"]:
             setattr(args, p, cfg[p][0])
         cmain.setup_seed(args.seed)
-        needs = name in ("MMGCN", "FREEDOM", "MGCN", "VBPR", "SLMRec", "MCLN", "POWERec", "LGMRec", "SMORE", "MMGCL", "LightGT", "GUME",
-                         "DDRec", "MICRO", "MENTOR", "BM3", "MGCL", "LATTICE", "MMSSL", "GRCN", "MGAT", "MVGAE", "DiffMM")
+        needs = MODELS[name].features
         train, val, test, uid, U, I, v, t = dataload.data_load("sports", has_v=needs, has_t=needs, data_root=args.data_root, synthetic=False)
         loader = dataload.DeviceBatchSampler(U, I, uid, train, args.batch_size, dev, name, args.seed)
         args.num_user, args.num_item = U, I
         model = cmain.build_model(args, U, I, train, uid, v, t, dev).to(dev)
         opt = FusedAdam([{"params": model.parameters(), "lr": args.learning_rate}])
-        if name in te.PRE_EPOCH:
+        if MODELS[name].pre_epoch:
             model.pre_epoch_processing()
         graphed = te._capture_step(model, loader, opt, name)
         ep, ev = [], []
         val_l = te.EvalLists(val, dev)
         for k in range(5):
-            if name in te.PRE_EPOCH:
+            if MODELS[name].pre_epoch:
                 model.pre_epoch_processing()
             torch.cuda.synchronize()
             t0 = time.perf_counter()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Grade at sports on the MI355X (measurement only): one eager training step (three losses, four Adam optimizers, as
-train_and_evaluate's branch runs it) with the fused three-view node (ops_extra.grade_views) against the SAME model with
+epochs._train_epoch_grade runs it) with the fused three-view node (ops_extra.grade_views) against the SAME model with
 `fused_edges = False`, i.e. the reference's per-edge lines in plain torch over gathered [E, 64] rows; the three-view node alone
 both ways; the node at G = 3 against three G = 1 calls; the step's SpMM share (the same step with its propagates alone); peak
 memory of each.
@@ -79,7 +79,7 @@ def main():
     opt = torch.optim.Adam(m.parameters(), lr=0.001, weight_decay=0)
     opt_gens = [torch.optim.Adam(g.parameters(), lr=0.001, weight_decay=0) for g in gens]
 
-    def step():                            # train_and_evaluate._train_epoch_grade's body
+    def step():                            # epochs._train_epoch_grade's body
         opt.zero_grad()
         m.loss_1(users, pos, neg).backward()
         opt.step()

@@ -2,7 +2,7 @@
 """MHRec on the MI355X (measurement only): the hypergraph attention layer, forward + backward, as the fused node
 (ops_extra.mhrec_hyper_layer, csrc/mhrec.hip) against the plain-torch restatement on the same HyperGraph
 (ops_extra.mhrec_hyper_layer_torch: gathers, a [nnz, 128] concatenation, two index_adds); and one epoch of
-train_and_evaluate's MHRec branch split into its three phases -- the two diffusion passes, the rebuild, the BPR steps -- with
+epochs._train_epoch_mhrec split into its three phases -- the two diffusion passes, the rebuild, the BPR steps -- with
 `fused_hyper` on and off.  The hypergraph is the one the untrained denoisers rebuild (hub-heavy, as the model's own are).
 
     python tools/bench_mhrec.py [--blocks 7] [--batch 1024] [--dataset baby] [--num_hypernodes 10] [--epochs 2] [--out FILE]
@@ -22,7 +22,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from chaorec_amd import dataload, ops_extra, train_and_evaluate as te  # noqa: E402
+from chaorec_amd import dataload, epochs, ops_extra  # noqa: E402
 from chaorec_amd.Model import MHRec  # noqa: E402
 from chaorec_amd.optim import FusedAdam  # noqa: E402
 from tools.bench_mvgae import compare  # noqa: E402
@@ -84,7 +84,7 @@ def main():
                 for p, w in zip(m.parameters(), snapshot):
                     p.copy_(w)
             times = {}
-            te._train_epoch_mhrec(m, loader, opt, diff_loaders, times)
+            epochs._train_epoch_mhrec(m, loader, opt, diff_loaders, times)
             if ep:
                 phases[fused].append(times)
     m.fused_hyper = True
