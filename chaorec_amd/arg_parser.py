@@ -77,7 +77,8 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=42, help='Number of seed')
     parser.add_argument('--num_workers', type=int, default=1, help='Workers number.')
     # reference: type=float (arg_parser.py:92), which breaks ranked_list[:k] for CLI-supplied values; ints here
-    parser.add_argument('--topk', type=int, nargs='+', default=[5, 10, 20], help='topK')
+    parser.add_argument('--topk', type=int, nargs='+', default=[5, 10, 20],
+                        help='topK: the cut-offs of the evaluation, each at most 1024 (above 50 the rank list is built that wide)')
     parser.add_argument('--patience', type=int, default=20, help='early-stopping patience (reference: 20)')
     parser.add_argument('--host_sampler', action='store_true',
                         help='use the reference-style DataLoader + python sampler instead of the device sampler')

@@ -930,7 +930,7 @@ def _stats_dict(v):
 
 
 def score_topk(user_emb, item_emb, hist, mask_value, K, id_offset=0, precision=0, stats=None, hint=None,
-               hint_valid=False, hint_rank=80, light=False, counters=None, idx_out=None):
+               hint_valid=False, hint_rank=80, light=False, counters=None, idx_out=None, staging_bytes=None):
     """Top-K of user_emb @ item_emb.T with history masking, without the [U,I] matrix.
     Returns (idx int64 [U,K] = item + id_offset, val fp32 [U,K]).  `stats`: a dict to fill with the prefilter
     route's counters (chaorec_score_topk_stats; costs a device sync).
@@ -946,7 +946,15 @@ def score_topk(user_emb, item_emb, hist, mask_value, K, id_offset=0, precision=0
     CHAOREC_SCORE_WS_LIMIT (24 GiB) is cut into user ranges of equal length -- the users are independent --, one range after
     the other on the caller's stream.  (Round 5 also ran them PIPELINED -- range k's back phase on a second stream beside range
     k + 1's front phase, two workspaces in flight --: 634 ms against 630 ms serial and 628 ms in one piece at the config-5 shard,
-    every kernel of the call fills the chip on its own; that code is profiles/r05_exp_score_pipeline.patch)"""
+    every kernel of the call fills the chip on its own; that code is profiles/r05_exp_score_pipeline.patch)
+
+    64 < K <= 1024 (ops_wide.score_topk_wide): the exact scores of a user range are staged in HBM (staging_bytes, default
+    CHAOREC_WIDE_STAGING_BYTES = 512 MiB, sets the range length) and every staged row's top-K selected from them -- the same
+    scores, the same order, ties to the lowest index.  hint, hint_valid, light and counters are ignored and left untouched,
+    precision changes nothing, `stats` receives {"wide_users": U}.  K > 1024: ValueError."""
+    if int(K) > 64:
+        return _family("ops_wide").score_topk_wide(user_emb, item_emb, hist, mask_value, K, id_offset=id_offset, stats=stats,
+                                                   idx_out=idx_out, staging_bytes=staging_bytes)
     _need_cuda(user_emb, item_emb)
     user_emb, item_emb = _f32c(user_emb), _f32c(item_emb)
     U, D = user_emb.shape
@@ -1032,7 +1040,10 @@ def rank_metrics(rank_idx, row_user, pos_rowptr, pos_items, k_list):
     disc = 1.0 / np.log(np.arange(int(k.max())) + 2.0)          # the reference's own discount table (metrics.py:31,34)
     n_rows = int(row_user.shape[0])
     lib = _lib.load()
-    nbytes = lib.chaorec_rank_metrics_workspace_bytes(n_rows, len(k))
+    if int(k.max()) > 64:        # a wave per row, the discount table beside the partial sums
+        nbytes = lib.chaorec_rank_metrics_wide_workspace_bytes(n_rows, len(k), int(k.max()))
+    else:
+        nbytes = lib.chaorec_rank_metrics_workspace_bytes(n_rows, len(k))
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=rank_idx.device)
     out = torch.empty((len(k), 5), dtype=torch.float64, device=rank_idx.device)
     lib.chaorec_rank_metrics_f64(_ptr(rank_idx), rank_idx.shape[0], rank_idx.shape[1], _ptr(row_user), _ptr(pos_rowptr),
@@ -1093,7 +1104,7 @@ def mean_all(x):
 # ---- public name of theirs is still reachable as chaorec_amd.ops.<name>: resolved on first use (PEP 562) against the modules'
 # ---- own __all__ lists, then kept in this module's globals.
 _FAMILY_MODULES = ("ops_dense", "ops_adam", "ops_sparse_family", "ops_dgcf", "ops_vae", "ops_usergraph", "ops_mvgae",
-                   "ops_diffmm", "ops_edges", "ops_mhrec", "ops_bspm", "ops_cfdiff")
+                   "ops_diffmm", "ops_edges", "ops_mhrec", "ops_bspm", "ops_cfdiff", "ops_wide")
 
 
 def _family(module):

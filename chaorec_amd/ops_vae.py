@@ -370,8 +370,11 @@ def macrid_scores(zh, items, cates, tau, user_begin, hist, mask_value, out=None)
 def rows_topk(scores, topk, id_offset=0):
     """Exact top-k per row of scores [n, I], ties to the lowest index -> (int64 [n, topk] ids + id_offset, fp32 [n, topk]).
     The export and the messages keep the name of the first user (MacridVAE's ranking); DualVAE's ranking and DiffMM's graph
-    rebuild call it too."""
+    rebuild call it too.  64 < topk <= min(1024, I): chaorec_rows_topk_wide_f32 (ops_wide.rows_topk_wide), same order."""
     _need_cuda(scores)
+    if int(topk) > 64:
+        from .ops_wide import rows_topk_wide
+        return rows_topk_wide(scores, topk, id_offset)
     scores = _f32("macrid", scores, "scores")
     n, I = scores.shape
     if not 1 <= int(topk) <= min(64, I):

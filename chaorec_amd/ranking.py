@@ -112,7 +112,10 @@ def gene_ranklist(result, num_user, num_item, hist, mask_value=1e-6, topk=50, to
     """result [N, D] (users first) on the GPU -> LongTensor [num_user, topk] of GLOBAL item ids on the CPU (the
     reference's contract); to_cpu=False keeps it in HBM for utils.gene_metrics_device.
     id_offset (default num_user): what is added to an item's row number -- a user shard ranks its own users against the
-    replicated items and reports item + num_user_GLOBAL.  items: the item table where it is not part of `result`."""
+    replicated items and reports item + num_user_GLOBAL.  items: the item table where it is not part of `result`.
+    topk up to 1024 (ValueError beyond): past 64 the list comes from the staged scores of ops_wide."""
+    topk = int(topk)
+    ops.check_wide_k("gene_ranklist", topk)
     if items is not None and result.shape[1] not in (8, 16, 32, 64, 128) and not (result.shape[1] > 128 and result.shape[1] % 64 == 0):
         result, items = torch.cat((result[:num_user].detach(), items.detach()), 0), None     # (odd width: padded below)
     id_offset = num_user if id_offset is None else int(id_offset)
@@ -129,7 +132,11 @@ def gene_ranklist(result, num_user, num_item, hist, mask_value=1e-6, topk=50, to
             result = torch.cat((result, result.new_zeros(result.shape[0], wide - D)), 1)
         ue = result[:num_user]
         ie = items.detach() if items is not None else result[num_user:num_user + num_item]
-        if state is not None:
+        if topk > 64:
+            # the wide route (ops_wide.score_topk_wide) carries no thresholds: `state` is neither consulted nor changed, a later
+            # narrow call finds it as it was
+            idx, _ = ops.score_topk(ue, ie, hist, mask_value, topk, id_offset=id_offset, idx_out=host)
+        elif state is not None:
             hint = state.buffer(num_user, result.device)
             hinted = state.use_hints(num_user)          # (once per call: it consumes the previous call's counters)
             light = hinted and state.light()

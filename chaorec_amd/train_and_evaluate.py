@@ -54,6 +54,17 @@ def evaluate(model, data, ranklist, topk):
         return gene_metrics(data, ranklist, topk)
 
 
+MAX_TOPK = 1024          # ops_wide.WIDE_K: the widest rank list the selection and the metric kernels take
+DEFAULT_COLUMNS = 50     # gene_ranklist()'s default width (Model/LightGCN.py:137)
+
+
+def _rank_list(model, kmax, on_device):
+    """The evaluation's rank list, wide enough for the largest cut-off: the model's default 50 columns, or kmax of them."""
+    if kmax <= DEFAULT_COLUMNS:
+        return model.gene_ranklist(to_cpu=False) if on_device else model.gene_ranklist()
+    return model.gene_ranklist(topk=kmax, to_cpu=False) if on_device else model.gene_ranklist(topk=kmax)
+
+
 def _log_metrics(title, metrics):
     logging.info(title)
     for k, m in metrics.items():
@@ -122,16 +133,20 @@ def train_and_evaluate(model, train_loader, val_data, test_data, optimizer, epoc
     graphed, capture_pending = None, bool(graph)
     early_stopping = EarlyStopping(patience=patience, verbose=True)
     topk = [int(k) for k in topk]
-    # evaluation stays on the device when the model can hand the rank list over in HBM
-    # (gene_ranklist returns 50 columns, as the reference's does: larger cut-offs take the host path, which truncates)
-    on_device = getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda" and max(topk) <= 50
+    # evaluation stays on the device when the model can hand the rank list over in HBM.  gene_ranklist returns 50 columns by
+    # default, as the reference's does; a larger cut-off asks it for that many (the wide selection, up to MAX_TOPK), and one
+    # beyond that fails here, before any epoch, instead of reporting "Recall@k" of a shorter list
+    kmax = max(topk)
+    if kmax > MAX_TOPK:
+        raise ValueError(f"topk={topk}: the largest cut-off the rank lists serve is {MAX_TOPK}")
+    on_device = getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda"
     if on_device:
         val_data, test_data = EvalLists(val_data, model.device), EvalLists(test_data, model.device)
     spec = spec_of(model_name)
     if not spec.trains:
         # train_and_evaluate.py:531-552 (BSPM): nothing to train, no epochs -- rank once, evaluate both splits, return the test metrics
         model.eval()
-        rank_list = model.gene_ranklist(to_cpu=False) if on_device else model.gene_ranklist()
+        rank_list = _rank_list(model, kmax, on_device)
         val_metrics = evaluate(model, val_data, rank_list, topk)
         test_metrics = evaluate(model, test_data, rank_list, topk)
         _log_metrics('Validation Metrics:', val_metrics)
@@ -155,7 +170,7 @@ def train_and_evaluate(model, train_loader, val_data, test_data, optimizer, epoc
             # whoever reads a claimed table between epochs -- model.state_dict(), a checkpoint, a per-epoch kNN rebuild -- sees
             # current rows (one launch per claimed table; the rows' values are the eager ones bit for bit either way)
             optimizer.flush()
-        rank_list = model.gene_ranklist(to_cpu=False) if on_device else model.gene_ranklist()
+        rank_list = _rank_list(model, kmax, on_device)
         val_metrics = evaluate(model, val_data, rank_list, topk)
         test_metrics = evaluate(model, test_data, rank_list, topk)
         _log_metrics('Validation Metrics:', val_metrics)

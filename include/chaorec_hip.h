@@ -556,6 +556,30 @@ int chaorec_score_topk_stats(const void *workspace, int64_t n_users, int64_t n_i
                              uint64_t *out10, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Rank lists past 64 columns (csrc/topk_wide.hip).  Additive to ABI 16: new names only.
+ *
+ * Replaces: the same gene_ranklist lines as chaorec_score_topk_f32 (Model/LightGCN.py:147-155, Model/FREEDOM.py:230-238,
+ *           Model/MMGCN.py:220-230) for 64 < topk <= 1024, in two launches per user range: the exact scores of the range
+ *           into a staging block, then the exact top-k of every staged row.
+ *
+ * chaorec_score_rows_f32: scores[u - user_begin, i] for the users user_begin .. user_begin + n of user_emb [n_users, D]
+ * against all n_items rows of item_emb -- the same fp32 value as chaorec_score_topk_f32 ranks (the two interleaved fmaf
+ * chains stated there, 64-wide chunks above D = 128), history entries (hist_rowptr int64 [n_users + 1], hist_col int32
+ * LOCAL item ids ascending inside a row; hist_rowptr may be NULL) = mask_value.  scores is [n, ld] fp32 with ld >= n_items
+ * (columns n_items .. ld are left alone); n * ld * 4 must not exceed scores_bytes: the [U, I] matrix never exists whole, the
+ * caller walks the users in ranges.  D as chaorec_score_topk_f32.  One launch, no workspace. */
+int chaorec_score_rows_f32(const float *user_emb, const float *item_emb, int64_t n_users, int64_t n_items, int32_t D,
+                           int64_t user_begin, int64_t n, const int64_t *hist_rowptr, const int32_t *hist_col,
+                           float mask_value, float *scores, int64_t ld, size_t scores_bytes, void *stream);
+/* Exact top-k of every row of scores [n_rows, ld] (row r = scores + r * ld, its first I columns; any 4-byte alignment) for
+ * 64 < topk <= min(1024, I): descending by chaorec_macrid_topk_f32's bit-pattern order (-0 < +0, a NaN by sign and
+ * payload), ties to the lowest index (torch.topk's values, Model/LightGCN.py:155): idx [n_rows, topk] = column + id_offset,
+ * val [n_rows, topk].  One workgroup per row: radix search for the k-th key, ordered compaction, bitonic sort of the k
+ * winners in LDS.  No atomics: the same bits on every run. */
+int chaorec_rows_topk_wide_f32(const float *scores, int64_t n_rows, int64_t I, int64_t ld, int32_t topk, int64_t id_offset,
+                               int64_t *idx, float *val, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * M: ranking metrics of every evaluation row in one launch.
  *
  * Replaces: utils.gene_metrics' python loop over users x K x {precision, recall, ndcg, hit_rate, map}
@@ -566,13 +590,18 @@ int chaorec_score_topk_stats(const void *workspace, int64_t n_users, int64_t n_i
  *   rank_idx   [n_users, rank_stride] int64 global item ids, best first (chaorec_score_topk_f32's out_idx)
  *   row_user   [n_rows] user of each evaluation row; pos_rowptr/pos_items: the rows' positives as a CSR
  *              (val.npy / test.npy rows [user, pos...]), global item ids, duplicates allowed
- *   k_list     HOST array of n_k <= 8 cut-offs, each <= min(64, rank_stride)
+ *   k_list     HOST array of n_k <= 8 cut-offs, each <= min(1024, rank_stride).  With every cut-off <= 64 a thread owns
+ *              an evaluation row (one 64-bit hit mask); a call with a larger one gives every row to a wave (16 mask words)
+ *              and needs chaorec_rank_metrics_wide_workspace_bytes(n_rows, n_k, max k) of workspace, which also holds
+ *              the discount table (it travels in kernel arguments, 480 doubles per launch: still kernels only)
  *   discount   HOST array, discount[p] = 1 / log(p + 2) for p < max(k) as the caller's libm gives it (the
  *              per-user terms are then bit-identical to a host evaluation with the same table)
  *   out        DEVICE [n_k][5] fp64: precision, recall, ndcg, hit_rate, map, each averaged over n_rows
  * fp64 throughout; the sums over rows are reduced in a fixed order (run-to-run identical).
  * ------------------------------------------------------------------------------------- */
 size_t chaorec_rank_metrics_workspace_bytes(int64_t n_rows, int32_t n_k);
+/* (kmax <= 64: the value above) */
+size_t chaorec_rank_metrics_wide_workspace_bytes(int64_t n_rows, int32_t n_k, int32_t kmax);
 int chaorec_rank_metrics_f64(const int64_t *rank_idx, int64_t n_users, int64_t rank_stride,
                              const int64_t *row_user, const int64_t *pos_rowptr, const int64_t *pos_items,
                              int64_t n_rows, const int32_t *k_list, int32_t n_k, const double *discount,
