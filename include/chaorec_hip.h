@@ -911,7 +911,13 @@ int chaorec_bpr_multi_bwd_f32(const float *tab_u, const int64_t *users, int32_t 
                               float *const *g_i, const int64_t *const *scatter_rows, float *const *scatter_out,
                               void *stream);
 /* ... and its ordered, atomic-free form (see chaorec_bpr_bwd_ordered_f32): g_u, every g_i[k] and every scatter_out[k] must be
- * DISTINCT buffers (each is one group of rows with one owner wave per row). */
+ * DISTINCT buffers (each is one group of rows with one owner wave per row).  The DEFINED order, restated by
+ * oracle_bpr_multi_bwd_ordered_f32 and compared bit for bit (tests/test_gpu_bpr_multi.py): with
+ * c = coef[k][b] * (grad_out * wvec[k]), a row of g_u takes the addends c * (p - n) of all terms, term by term and in batch
+ * order inside a term; a row of g_i[k] first the batch's positive slots in batch order (c * u), then its negative slots
+ * ((-c) * u); a row of scatter_out[k] the same two passes, keyed by scatter_rows[k][pos] / scatter_rows[k][neg].  Every
+ * addend is rounded to float and added to the row's ONE running float sum, which starts from what the buffer holds.  Falls
+ * back to the atomic launch (no defined order) beyond 16384 slots in a group (T B for the users, 2 B per table) or D > 256. */
 int chaorec_bpr_multi_bwd_ordered_f32(const float *tab_u, const int64_t *users, int32_t T, const float *const *tabs,
                                       const int64_t *const *pos, const int64_t *const *neg, int32_t B, int32_t D,
                                       const float *coef, const float *wvec, const float *grad_out, float *g_u,

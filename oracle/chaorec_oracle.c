@@ -170,6 +170,55 @@ void oracle_bpr_bwd_ordered_f32(const float *tab_u, const float *tab_i, const in
   }
 }
 
+/* Several BPR terms over one user table (Model/FREEDOM.py:203-215), the float index_add of every gradient buffer in a stated
+ * order -- what the product's ordered multi-term launch (chaorec_bpr_multi_bwd_ordered_f32) reproduces bit for bit.  With
+ * c(k, b) = coef[k][b] * (grad_out * wvec[k])  (two float products, in this association), every addend rounded to float
+ * before it is added, no fused multiply-add, and ONE running float sum per destination row that starts from what the row
+ * already holds (the function ADDS INTO the arrays it is given):
+ *   * the user table g_u: the addends  c * (p - n)  of ALL terms, term by term (k ascending), the batch in order inside a term;
+ *   * the item table g_i[k] of term k: first the positive rows of the whole batch in batch order (+c * u), then the negative
+ *     rows in batch order ((-c) * u); a row that is positive for one sample and negative for another has one running sum;
+ *   * scatter_out[k], where scatter_rows[k] is given (term k's table is a block of rows gathered from a longer table): the
+ *     same two passes and the same addends, added to row scatter_rows[k][pos] / scatter_rows[k][neg]; gathered rows that map
+ *     to one table row share its running sum.
+ * The buffers are independent of each other (g_u, every g_i[k], every scatter_out[k] distinct), so the order BETWEEN buffers
+ * is immaterial.  coef [T, B] float; tabs / pos / neg / g_i / scatter_rows / scatter_out: arrays of T pointers, the last two
+ * NULL or with NULL entries for terms without a scatter. */
+void oracle_bpr_multi_bwd_ordered_f32(const float *tab_u, const int64_t *users, int32_t T, const float *const *tabs,
+                                      const int64_t *const *pos, const int64_t *const *neg, int32_t B, int32_t D,
+                                      const float *coef, const float *wvec, float grad_out, float *g_u, float *const *g_i,
+                                      const int64_t *const *scatter_rows, float *const *scatter_out) {
+  for (int32_t k = 0; k < T; ++k) {
+    const float gw = grad_out * wvec[k];
+    for (int32_t b = 0; b < B; ++b) {
+      const float c = coef[(size_t)k * B + b] * gw;
+      const size_t ou = (size_t)users[b] * D, op = (size_t)pos[k][b] * D, on = (size_t)neg[k][b] * D;
+      for (int32_t q = 0; q < D; ++q) {
+        const float d = tabs[k][op + q] - tabs[k][on + q];
+        const float v = c * d;
+        g_u[ou + q] += v;
+      }
+    }
+  }
+  for (int32_t k = 0; k < T; ++k) {
+    const float gw = grad_out * wvec[k];
+    const int64_t *srows = scatter_rows ? scatter_rows[k] : NULL;
+    for (int role = 0; role < 2; ++role) {
+      for (int32_t b = 0; b < B; ++b) {
+        const float c = coef[(size_t)k * B + b] * gw;
+        const float cs = role == 0 ? c : -c;
+        const int64_t r = role == 0 ? pos[k][b] : neg[k][b];
+        const size_t ou = (size_t)users[b] * D;
+        for (int32_t q = 0; q < D; ++q) {
+          const float v = cs * tab_u[ou + q];
+          g_i[k][(size_t)r * D + q] += v;
+          if (srows) scatter_out[k][(size_t)srows[r] * D + q] += v;
+        }
+      }
+    }
+  }
+}
+
 /* ---- S sampler -------------------------------------------------------------------------
  * dataload.py:74-79: draw uniformly from all items until the draw is not in the user's
  * history.  The generator is this build's counter-based one (the reference's is Python's

@@ -200,7 +200,98 @@ def bpr_bwd_ordered(tab_u, tab_i, users, pos, neg, coef, reg_weight, grad_out=1.
     return g_u, g_i
 
 
-SECOND_DRAW_SALT = 0x9E3779B97F4A7C15      # the stream of the sample's second draw (dataload.py:81-84), chaorec_hip.h
+def _ptr_array(arrays, ty):
+    """A C array of len(arrays) pointers (None -> NULL); the arrays must outlive the call."""
+    return (ty * len(arrays))(*[_p(a, ty) for a in arrays])
+
+
+def bpr_multi_fwd(tab_u, users, tabs, pos, neg, variant, wvec):
+    """Model/FREEDOM.py:203-215 in fp64: losses[k] and coef[k] are oracle_bpr_fwd_f32's with reg_weight 0 on term k
+    (tabs[k], pos[k], neg[k]; the user table and the users are shared), total = sum_k wvec[k] * losses[k] in double.
+    -> (total, losses [T], coef [T, B])."""
+    T = len(tabs)
+    losses = np.zeros(T, np.float64)
+    coef = np.zeros((T, len(users)), np.float64)
+    for k in range(T):
+        out, coef[k] = bpr_fwd(tab_u, tabs[k], users, pos[k], neg[k], variant, 0.0)
+        losses[k] = out[1]
+    return float(np.dot(np.asarray(wvec, np.float64), losses)), losses, coef
+
+
+def bpr_multi_bwd(tab_u, users, tabs, pos, neg, coef, wvec, grad_out=1.0, scatter_rows=None, scatter_sizes=None):
+    """Gradient of bpr_multi_fwd's total times grad_out, in fp64 (index_add of c (p - n), c u, -c u with
+    c = coef[k][b] * grad_out * wvec[k]), and for every element the SUM OF |addend| and the NUMBER of addends that met in
+    it -- what an error bound for a float sum of those addends is made of.  scatter_rows[k] (or None): term k's table is
+    a block of rows gathered from a table of scatter_sizes[k] rows; its gradient is also added into that table's rows.
+    -> three tuples (g_u, [g_i[k]], [scattered[k] or None]): the gradients, the |addend| sums, the counts."""
+    tab_u = np.asarray(tab_u, np.float64)
+    users = np.asarray(users, np.int64)
+    T, D = len(tabs), tab_u.shape[1]
+    coef = np.asarray(coef, np.float64).reshape(T, -1)
+    wvec = np.asarray(wvec, np.float64)
+    new = lambda rows: tuple(np.zeros((rows, D), np.float64) for _ in range(3))     # sum, sum of |.|, count
+    g_u, g_i, g_s = new(tab_u.shape[0]), [], []
+    one = np.ones((len(users), D))
+
+    def add(dst, rows, v):
+        np.add.at(dst[0], rows, v)
+        np.add.at(dst[1], rows, np.abs(v))
+        np.add.at(dst[2], rows, one)
+
+    for k in range(T):
+        tab = np.asarray(tabs[k], np.float64)
+        p, n = np.asarray(pos[k], np.int64), np.asarray(neg[k], np.int64)
+        c = (coef[k] * float(grad_out) * wvec[k])[:, None]
+        u = tab_u[users]
+        add(g_u, users, c * (tab[p] - tab[n]))
+        g_i.append(new(tab.shape[0]))
+        add(g_i[k], p, c * u)
+        add(g_i[k], n, -c * u)
+        rows = None if scatter_rows is None else scatter_rows[k]
+        if rows is None:
+            g_s.append(None)
+        else:
+            rows = np.asarray(rows, np.int64)
+            g_s.append(new(int(scatter_sizes[k])))
+            add(g_s[k], rows[p], c * u)
+            add(g_s[k], rows[n], -c * u)
+    pick = lambda j: (g_u[j], [g[j] for g in g_i], [None if g is None else g[j] for g in g_s])
+    return pick(0), pick(1), pick(2)
+
+
+def bpr_multi_bwd_ordered(tab_u, users, tabs, pos, neg, coef, wvec, grad_out=1.0, g_u=None, g_i=None, scatter_rows=None,
+                          scatter_out=None):
+    """The float index_add of the multi-term BPR gradient in the order oracle_bpr_multi_bwd_ordered_f32 states: bit-exact
+    twin of the product's chaorec_bpr_multi_bwd_ordered_f32.  ADDS INTO g_u [U, D], g_i[k] and scatter_out[k] (float32,
+    C-contiguous; g_u / g_i None: zero-filled here) and returns (g_u, g_i, scatter_out)."""
+    tab_u = _c(tab_u, np.float32)
+    users = _c(users, np.int64)
+    T, B, D = len(tabs), len(users), tab_u.shape[1]
+    tabs = [_c(t, np.float32) for t in tabs]
+    pos, neg = [_c(p, np.int64) for p in pos], [_c(n, np.int64) for n in neg]
+    coef, wvec = _c(coef, np.float32), _c(wvec, np.float32)
+    assert coef.size == T * B and wvec.size == T
+    g_u = np.zeros(tab_u.shape, np.float32) if g_u is None else g_u
+    g_i = [np.zeros(t.shape, np.float32) for t in tabs] if g_i is None else list(g_i)
+    outs = [g_u] + g_i
+    srows = souts = None
+    if scatter_rows is not None:
+        srows = [None if r is None else _c(r, np.int64) for r in scatter_rows]
+        souts = list(scatter_out)
+        assert all((r is None) == (o is None) for r, o in zip(srows, souts))
+        outs += [o for o in souts if o is not None]
+    assert all(o.dtype == np.float32 and o.flags.c_contiguous and o.flags.writeable for o in outs)
+    _pp = ctypes.POINTER
+    lib().oracle_bpr_multi_bwd_ordered_f32(
+        _p(tab_u, _f32p), _p(users, _i64p), ctypes.c_int32(T), _ptr_array(tabs, _f32p), _ptr_array(pos, _i64p),
+        _ptr_array(neg, _i64p), ctypes.c_int32(B), ctypes.c_int32(D), _p(coef, _f32p), _p(wvec, _f32p),
+        ctypes.c_float(grad_out), _p(g_u, _f32p), _ptr_array(g_i, _f32p),
+        ctypes.cast(None, _pp(_i64p)) if srows is None else _ptr_array(srows, _i64p),
+        ctypes.cast(None, _pp(_f32p)) if souts is None else _ptr_array(souts, _f32p))
+    return g_u, g_i, souts
+
+
+SECOND_DRAW_SALT = 0x9E3779B97F4A7C15     # the stream of the sample's second draw (dataload.py:81-84), chaorec_hip.h
 
 
 def sample_negatives(hist, users, num_item, seed, step, id_offset, second=False):
