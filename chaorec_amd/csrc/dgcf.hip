@@ -534,6 +534,8 @@ extern "C" int chaorec_dgcf_dcor_fwd_f32(const float *table, const int64_t *idx,
                                          void *ws, size_t ws_bytes, void *stream) {
   if (int rc = check_shape("dgcf_dcor_fwd", D, K)) return rc;
   if (K < 2) return fail(CHAOREC_E_INVALID, "dgcf_dcor_fwd: K=%d (at least 2 slices)", K);
+  // refused here, before the gather below is launched: pass 2 gives every thread D / 16 columns of its row
+  if (D < DC_T) return fail(CHAOREC_E_INVALID, "dgcf_dcor_fwd: unsupported D=%d for K=%d", D, K);
   if (!table || !idx || !loss || !ws || n < 1) return fail(CHAOREC_E_INVALID, "dgcf_dcor_fwd: null pointer or n=%lld", (long long)n);
   if (ws_bytes < dcor_ws_layout(n, D, K, nullptr, nullptr)) return fail(CHAOREC_E_INVALID, "dgcf_dcor_fwd: workspace too small");
   DcorWs w;
