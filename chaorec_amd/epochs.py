@@ -194,6 +194,25 @@ def _train_epoch_cfdiff(model, train_loader, optimizer, diffusion_loader=None):
     return float(sum_loss.item()) if sum_loss is not None else 0.0
 
 
+def _train_epoch_diffrec(model, train_loader, optimizer, diffusion_loader=None):
+    """reference train_and_evaluate.py:304-315: one pass over shuffled user batches, AdamW(weight_decay = 0) over the denoiser
+    created anew every epoch (its moments restart, as there).  A batch is its user ids: the noised rows come from the history
+    CSR (model.diffusion_step).  diffusion_loader: by default a dataload.DeviceUserBatches at the train loader's batch size,
+    kept on the model between epochs.  The optimizer handed in is not read (main() builds none for this model)."""
+    if diffusion_loader is None:
+        diffusion_loader = _cached_user_batches(model, "_diffusion_loader", train_loader, lambda: model.num_user)
+    optimizer = torch.optim.AdamW(model.dnn.parameters(), lr=model.learning_rate, weight_decay=0)
+    sum_loss = None
+    for users in diffusion_loader:
+        optimizer.zero_grad()
+        loss = model.diffusion_step(users)
+        loss.backward()
+        optimizer.step()
+        d = loss.detach()
+        sum_loss = d.clone() if sum_loss is None else sum_loss.add_(d)
+    return float(sum_loss.item()) if sum_loss is not None else 0.0
+
+
 def _train_epoch_mhrec(model, train_loader, optimizer, diffusion_loaders=None, times=None):
     """reference train_and_evaluate.py:331-512 in its three phases: (1) one pass of the visual diffusion loader, then one of the
     textual, each denoiser under an Adam optimizer created anew every epoch (:333-336: their moments restart); (2) the two

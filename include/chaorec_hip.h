@@ -1359,6 +1359,37 @@ int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const float *W_out,
                                 float *part, double *diff_rows, float *gc_rows, float *loss, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * DiffRec (Model/DiffRec.py) -- csrc/diffrec.hip.  Additive to ABI 16: new names only.  fp32, no float atomics, no scratch,
+ * the same bits every run.  One 128 x 128 x 16 tile loop on the f32 MFMA pipe (v_mfma_f32_32x32x2_f32) with two epilogues:
+ * both operands [rows][k], k a multiple of 4 (chaorec_diffrec_check_shape: CHAOREC_E_INVALID otherwise, nothing launched),
+ * rows 16-byte aligned, the k chain of an element cut into segments of 64 added in ascending order as DiffMM's.
+ * chaorec_diffrec_tiles gives the tile.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_diffrec_check_shape(int64_t B, int64_t I, int64_t H);
+int chaorec_diffrec_tiles(int32_t *bm, int32_t *bn, int32_t *bk);
+/* The output layer of DNN.forward (:86-89) with training_losses' mse, reweight_loss, the division by pt and the batch mean
+ * (:445-461) in one pass; model_output does not exist.  out = h W_out^T + b_out (h [B, H] row stride ldh, W_out [I, H] row
+ * stride ldw), err = out - x0 with x0 from bits (uint32 [B, ceil(I / 32)], bit i % 32 of word i / 32, as
+ * chaorec_diffmm_rows_f32 writes it):
+ *   d_out[b, i] = c_row[b] err[b, i]                   (fp32 [B, ldd], I <= ldd <= the end of the last item tile, columns I .. ldd written 0)
+ *   reloss_rows[b] = w[b] / I sum_i err^2              (double; w double [B]: what update_Lt_history receives)
+ *   loss[0] = mean_b reloss_rows[b] / pt[b]            (pt double [B])
+ * With c_row[b] = 2 w[b] / (pt[b] B I), d_out is d loss / d out.  part fp32 [B, ceil(I / 128)] holds every row's sum of err^2
+ * per item tile (columns in a fixed butterfly order); a second launch adds them in tile order, in double. */
+int chaorec_diffrec_out_loss_f32(const float *h, int64_t ldh, const float *W_out, int64_t ldw, const float *b_out,
+                                 const uint32_t *bits, const double *w, const double *pt, const float *c_row, int64_t B,
+                                 int64_t I, int64_t H, float *d_out, int64_t ldd, float *part, double *reloss_rows,
+                                 float *loss, void *stream);
+/* One step of p_sample (:263-303 at sampling_steps = 0, no sampling noise) in the denoiser's hidden space:
+ *   p_next[b, n] = c1 (sum_k z[b, k] G[n, k] + g0[n]) + c2 p[b, n],   z_next[b, n] = tanh(p_next[b, n] + e_next[n])
+ * z fp32 [B, K] row stride ldz, G fp32 [N, K] row stride ldg, p fp32 [B, N] row stride ldp, g0 and e_next fp32 [N], p_next and
+ * z_next fp32 [B, N] row stride ldo; c1, c2 the posterior-mean coefficients of the step (one t for the whole batch).  p_next
+ * may be p itself; no other aliasing.  In DiffRec N = K = H, G = W1x W_out and g0 = W1x b_out. */
+int chaorec_diffrec_chain_f32(const float *z, int64_t ldz, const float *G, int64_t ldg, const float *g0, const float *p,
+                              int64_t ldp, const float *e_next, float c1, float c2, int64_t B, int64_t N, int64_t K,
+                              float *p_next, float *z_next, int64_t ldo, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * AdaGCL (Model/AdaGCL.py) -- csrc/adagcl.hip.  Additive to ABI 16: new names only.
  * The E-sized work of the two view generators over ONE symmetric-pattern CSR of N = U + I nodes: rowptr int64 [N + 1],
  * col int32 [E], entry_row int32 [E], tentry int32 [E] (the stored entry of the reversed pair).  D = 64 is what the keep
