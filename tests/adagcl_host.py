@@ -10,6 +10,7 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+from accept import rel_dev, user_item_dict  # noqa: F401
 
 D = 64
 DIM_E, REG_WEIGHT, N_LAYERS, SSL_TEMP, SSL_ALPHA, LR = 64, 0.001, 2, 0.5, 0.1, 0.001
@@ -28,19 +29,6 @@ GEN_1 = tuple(n for n in NAMES if n.startswith("generator_1."))
 LOSSES = ("loss_1", "loss_2", "bpr_reg_loss", "gen_loss")
 # the parameters each loss alone reaches (the generators' views are generated without gradient)
 WITH_GRAD = {"loss_1": NAMES[:2], "loss_2": NAMES[:2], "bpr_reg_loss": NAMES[:2], "gen_loss": NAMES}
-
-
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def small_case():

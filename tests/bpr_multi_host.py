@@ -4,11 +4,11 @@ files see the same inputs, the derived error bound of a float row sum, and a sec
 of the ordered backward that can also produce the WRONG orders the tests must be able to tell from the right one.  Also the
 guarded device buffers (`Guarded`) that tests/test_gpu_bpr_multi.py and tests/test_gpu_rowops.py let the launches write into."""
 import numpy as np
+from accept import ULP24 as U24  # noqa: F401  (unit roundoff of float32)
 
 U_ROWS, I_ROWS, TABLE_ROWS = 37, 23, 40       # user table, plain item table, the longer table gathered blocks map onto
 WVEC = (1.0, 1e-3, 0.0, -0.37)                # a unit, a small, a zero and a negative weight
 GRAD_OUT = 0.7
-U24 = 2.0 ** -24                              # unit roundoff of float32
 
 # (T, B, D, variant): what each case reaches in csrc/bpr.hip is listed in tests/test_gpu_bpr_multi.py
 CASES = [

@@ -5,11 +5,11 @@ import os
 
 import numpy as np
 import torch
+from accept import EPS32 as ULP, rel_dev, user_item_dict  # noqa: F401
 
 U, FACTOR, TOPK, EMPTY_ITEMS = 70, 16, 50, 10
 CASES = ((1, 1.0, 1.0), (2, 1.5, 0.7), (3, 1.0, 0.0))          # (K_s, T_s, idl_beta)
 MASK = 1e-6
-ULP = float(np.finfo(np.float32).eps)
 FIXTURE = "bspm_small.npz"
 
 
@@ -30,13 +30,6 @@ def small_case(I, seed):
         rows += [(u, U + i) for i in sorted(own)]
     edges = np.asarray(rows, dtype=np.int64)
     return edges[rng.permutation(len(edges))]
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in edges.tolist():
-        d.setdefault(int(u), []).append(int(i))
-    return d
 
 
 def step_sizes(K_s, T_s):
@@ -111,12 +104,6 @@ def top_lists(scores, k=TOPK):
     """Exact top-k per row, ties to the lowest index -> (ids [U, k], values)."""
     idx = np.argsort(-scores, axis=1, kind="stable")[:, :k]
     return idx, np.take_along_axis(scores, idx, 1)
-
-
-def rel_dev(x, ref, scale=None):
-    ref = np.asarray(ref, np.float64)
-    scale = np.abs(ref).max() if scale is None else scale
-    return float(np.abs(np.asarray(x, np.float64) - ref).max() / scale)
 
 
 def load_fixture(golden_dir):

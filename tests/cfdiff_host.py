@@ -1,14 +1,18 @@
 """Host side of the CF_Diff tests: the small case, the float64 restatement of CAM_AE and of the attention's backward identities,
 and the keep-bit keying of csrc/cfdiff.hip restated in numpy.  Shared by tests/golden/gen_cfdiff.py, tests/test_cfdiff_host.py and
 tests/test_gpu_cfdiff.py."""
+import functools
 import math
 import os
 
+import accept
 import numpy as np
 import torch
+from accept import EPS32 as ULP, user_item_dict  # noqa: F401
 
+ZERO_REF = "absolute"            # an all-zero reference compares absolutely here and in DiffRec's tests, which share this module
+rel_dev = functools.partial(accept.rel_dev, zero_ref=ZERO_REF)
 FIXTURE = "cfdiff_small.npz"
-ULP = float(np.finfo(np.float32).eps)
 U, I = 12, 48                    # user 11 has no history; items 44 .. 47 have no users; item 0 is held by every user with a history
 EMPTY_ITEMS = 4
 STEPS, NOISE_SCALE, NOISE_MIN, NOISE_MAX = 10, 0.1, 0.0005, 0.005
@@ -27,13 +31,6 @@ def load_fixture(golden_dir):
     return np.load(os.path.join(golden_dir, FIXTURE), allow_pickle=False)
 
 
-def rel_dev(got, ref, scale=None):
-    """max |got - ref| relative to the largest magnitude of ref (or `scale`); an all-zero ref compares absolutely."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    scale = float(np.abs(ref).max()) if scale is None else float(scale)
-    return float(np.abs(got - ref).max()) / (scale if scale > 0 else 1.0)
-
-
 def small_case(seed=5):
     """edges int64 [E, 2] (user, global item id), unique, sorted."""
     rng = np.random.RandomState(seed)
@@ -45,13 +42,6 @@ def small_case(seed=5):
     e = np.array(sorted(pairs), dtype=np.int64)
     e[:, 1] += U
     return e
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(int(u), []).append(int(i))
-    return d
 
 
 def dense_rows(edges):

@@ -10,10 +10,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bpr_multi_host import GUARD, SENTINEL, Guarded, bits  # noqa: E402,F401
+from bpr_multi_host import GUARD, SENTINEL, U24, Guarded, bits  # noqa: E402,F401
 from test_dgcf_host import distance_correlation, edge_operator, intent_propagate, routing_scores  # noqa: E402,F401
 
-U24 = 2.0 ** -24                                  # unit roundoff of float32
 
 # ---- the planted graph ---------------------------------------------------------------------------------------------------
 U, I = 37, 29                                     # U is no multiple of any RPW (1, 2, 4, 8, 16)

@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 import torch
+from accept import ULP24 as ULP, rel_dev, user_item_dict  # noqa: F401
 
 D, H, EMB, STEPS = 64, 1000, 10, 5
 NAMES = ("uEmbeds", "iEmbeds", "modal_weight", "image_trans_l.weight", "image_trans_l.bias", "text_trans_l.weight",
@@ -13,20 +14,6 @@ NAMES = ("uEmbeds", "iEmbeds", "modal_weight", "image_trans_l.weight", "image_tr
     f"denoise_model_{m}.{n}" for m in ("image", "text")
     for n in ("emb_layer.weight", "emb_layer.bias", "in_layers.0.weight", "in_layers.0.bias", "out_layers.0.weight", "out_layers.0.bias"))
 HYPER = dict(reg_weight=1e-4, n_layers=1, ssl_alpha=0.01, ssl_temp=0.1, ris_lambda=0.5, e_loss=0.01, rebuild_k=1)
-ULP = 2.0 ** -24
-
-
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def small_case():

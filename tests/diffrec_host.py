@@ -8,9 +8,9 @@ import numpy as np
 import torch
 
 import cfdiff_host as ch
+from accept import ULP24 as ULP, user_item_dict  # noqa: F401
 
 FIXTURE = "diffrec_small.npz"
-ULP = 2.0 ** -24
 U, I = ch.U, ch.I                # 12 x 48: user 11 has no history; items 44 .. 47 have no users; item 0 is held by every other user
 STEPS, NOISE_SCALE, NOISE_MIN, NOISE_MAX = 5, 0.1, 0.0005, 0.005
 HID, EMB = 68, 10                # dims = "[68]": one past a segment of 64, a multiple of 4
@@ -21,7 +21,8 @@ TS = np.array([0, 4, 3, 1, 0, 4, 2, 3, 1, 2, 3, 1], dtype=np.int64)       # one 
 NAMES = ("dnn.emb_layer.weight", "dnn.emb_layer.bias", "dnn.in_layers.0.weight", "dnn.in_layers.0.bias",
          "dnn.out_layers.0.weight", "dnn.out_layers.0.bias")
 
-small_case, user_item_dict, dense_rows, rel_dev, masked = ch.small_case, ch.user_item_dict, ch.dense_rows, ch.rel_dev, ch.masked
+small_case, dense_rows, masked = ch.small_case, ch.dense_rows, ch.masked
+rel_dev, ZERO_REF = ch.rel_dev, ch.ZERO_REF
 
 
 def load_fixture(golden_dir):

@@ -8,10 +8,11 @@ import os
 import numpy as np
 import scipy.sparse as sp
 import torch
+from accept import ULP24, rel_dev, user_item_dict  # noqa: F401
 from vae_ops_host import mix64      # csrc/common.h mix64 on uint64 arrays
 
 TOPN = 200
-EPS32 = 2.0 ** -24          # unit roundoff of fp32
+EPS32 = ULP24               # unit roundoff of fp32, 2^-24 (this module's older name for it; accept.EPS32 is the spacing 2^-23)
 # the Parameters of Model/DRAGON.py in registration order, and the ones the loss reaches
 NAMES = ("weight_u", "weight_i", "MLP_v.weight", "MLP_t.weight", "MLP_user.weight", "MLP_user.bias",
          "v_gcn.preference", "v_gcn.MLP.weight", "v_gcn.MLP.bias", "v_gcn.MLP_1.weight", "v_gcn.MLP_1.bias",
@@ -25,12 +26,6 @@ WITH_GRAD = ("weight_u",
 # the reference's DRAGON on the synthetic graph of small_case(): main.py:284's arguments
 DIM, REG_WEIGHT, N_LAYERS, II_TOPK, UU_TOPK, MM_IMAGE_WEIGHT = 64, 0.01, 2, 10, 10, 0.6
 GRAD_ROWS = np.arange(0, 256, 4)      # the rows of the two [256, feat] MLP.weight gradients the fixture stores
-
-
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
 
 
 # ---- (a) the co-occurrence graph ---------------------------------------------------------------------------------------------
@@ -234,13 +229,6 @@ def step(weights, v_feat, t_feat, edges, U, I, epoch_idx, epoch_w, users, pos_lo
         gs = torch.autograd.grad(loss, [p[n] for n in WITH_GRAD])
         out["grads"] = {n: g.numpy() for n, g in zip(WITH_GRAD, gs)}
     return out
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def small_case():

@@ -10,6 +10,7 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+from accept import rel_dev, user_item_dict  # noqa: F401
 
 D = 64
 DIM_E, REG_WEIGHT, N_LAYERS, SSL_TEMP, SSL_ALPHA, SSL_TEMP2, NOISE_ALPHA, LR = 64, 0.1, 2, 0.3, 0.2, 0.3, 0.2, 0.001
@@ -37,25 +38,12 @@ LOSSES = ("loss_1", "bpr_reg_loss", "gen_loss")
 WITH_GRAD = {"loss_1": EMB + TRS, "bpr_reg_loss": EMB, "gen_loss": EMB + TRS + GEN[1] + GEN[2] + GEN[3]}
 
 
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
-
-
 def stored(name, x):
     """What the golden keeps of a gradient or a trained tensor: all of it, but of the fifteen 64 x 64 Linear weights and the two
     projections only the first STORED_ROWS rows (the file stays well under the size limit); every deviation next to it was
     measured over the whole tensor."""
     x = np.asarray(x)
     return x[:STORED_ROWS] if name.endswith(".weight") and x.ndim == 2 and x.shape[0] == DIM_E and name not in EMB else x
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def small_case(seed=FIRST_SEED):

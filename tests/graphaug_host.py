@@ -11,6 +11,7 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+from accept import ULP24, rel_dev, user_item_dict  # noqa: F401
 
 D = 64
 DIM_E, REG_WEIGHT, N_LAYERS, SSL_TEMP, SSL_ALPHA, LR = 64, 0.001, 3, 0.2, 0.01, 0.001
@@ -29,19 +30,6 @@ PARAMS = ("uEmbeds", "iEmbeds") + UPPER + FC + MLP                              
 NAMES = ("uEmbeds", "iEmbeds") + UPPER + FC + tuple(n.replace("backbone_gnn.", "view_learner.encoder.") for n in UPPER + FC) + MLP
 WITH_GRAD = ("uEmbeds", "iEmbeds") + UPPER + FC                                        # the edge MLP gets no gradient
 PARTS = ("bpr", "reg", "cl", "kl")
-
-
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def small_case():
@@ -95,9 +83,9 @@ def draws(c, n_steps=1, seed_offset=1):
         views = []
         for _ in range(2):
             masks = [rng.random((g["N"], H)) >= DROP for _ in range(6)]
-            u1, u2 = (np.minimum(rng.random(g["E"]).astype(np.float32), np.float32(1 - 2.0 ** -24)) for _ in range(2))
-            u1[:2] = [0.0, 1 - 2.0 ** -24]                     # both ends of torch.rand's range
-            u2[:3] = [0.0, 1 - 2.0 ** -24, 0.5]                # (clamp_probs moves the ends to 2^-23 and 1 - 2^-23)
+            u1, u2 = (np.minimum(rng.random(g["E"]).astype(np.float32), np.float32(1 - ULP24)) for _ in range(2))
+            u1[:2] = [0.0, 1 - ULP24]                     # both ends of torch.rand's range
+            u2[:3] = [0.0, 1 - ULP24, 0.5]                # (clamp_probs moves the ends to 2^-23 and 1 - 2^-23)
             views.append(dict(masks=masks, u1=u1, u2=u2))
         out.append(dict(rdm=rdm, views=views))
     return out

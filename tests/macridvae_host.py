@@ -8,6 +8,7 @@ import os
 import numpy as np
 import torch
 
+from accept import ULP24
 from multvae_host import dense_rows, flags_from_mask, hist_csr, mask_from_flags, rel_dev, user_item_dict  # noqa: F401
 
 K = 10
@@ -115,7 +116,7 @@ def eval_scores(weights, rowptr, col, users, dtype=torch.float64):
 # The rounding gap of one fp32 score log p_ui: p's relative error is at most the largest error of a logit l = zh . it / tau.
 # With |zh| = |it| = 1 the 64-term dot rounds by at most 64 * 2^-24; zh itself comes out of an fp32 encoder whose longest
 # sums have 600 (hidden layer) + 64 (normalisations) terms, one rounding each: (64 + 600 + 64) * 2^-24 / tau = 4.3e-4.
-SCORE_GAP = (64 + 600 + 64) * 2.0 ** -24 / TAU
+SCORE_GAP = (64 + 600 + 64) * ULP24 / TAU
 
 
 def ranklist_check(ranks, weights, rowptr, col, hist_rowptr, hist_col, users, topk=50, chunk=512):

@@ -7,13 +7,13 @@ import os
 
 import numpy as np
 import torch
+from accept import ULP24 as ULP, rel_dev, user_item_dict  # noqa: F401
 
 D, H, EMB, STEPS, SAMPLING_STEPS = 64, 1000, 10, 20, 5
 LONG_ROW = 256            # chaorec_mhrec_long_row(): the layer cases are built around it (test_gpu_mhrec asserts the library agrees)
 HYPER = dict(reg_weight=1e-4, ii_topk=3, uu_topk=3, num_hypernodes=10, n_layers=2, h_layers=2, ssl_temp=0.2, ssl_alpha=0.01,
              beta1=0.5, beta2=0.5)
 LR, TOPK, N_STEPS, DIFF_BATCH = 1e-3, 10, 3, 128
-ULP = 2.0 ** -24
 MAIN = ("modal_weight", "image_embedding.weight", "image_trs.weight", "image_trs.bias", "text_embedding.weight", "text_trs.weight",
         "text_trs.bias", "user_embedding.weight", "user_visual_embedding.weight", "user_textual_embedding.weight",
         "item_embedding.weight")
@@ -25,19 +25,6 @@ DENOISE = tuple(f"denoise_model_{m}.{n}" for m in ("image", "text")
 NAMES = MAIN + tuple(n for m in ("Visual", "Textual") for l in range(HYPER["h_layers"])
                      for n in (f"hypergraphLayers{m}.{l}.a", f"hypergraphLayers{m}.{l}.W.weight")) + DENOISE
 WITH_GRAD = MAIN + HYPER_A           # what loss() reaches (the layers' W and the denoisers get no gradient from it)
-
-
-def rel_dev(a, b, scale=None):
-    """max |a - b| relative to the largest |b| (or to a given scale)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()) if scale is None else float(scale), 1e-300))
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def user_graph_dict(edges, U):

@@ -5,6 +5,7 @@ tests/test_multvae_host.py (against the reference goldens of tests/golden/gen_mu
 import numpy as np
 import torch
 import torch.nn.functional as F
+from accept import ULP24, rel_dev, user_item_dict  # noqa: F401
 
 LATENT = 64
 KEEP_PROB = 0.5
@@ -122,7 +123,7 @@ def ranklist_check(ranks, weights, z, hist_rowptr, hist_col, topk=50, chunk=2048
     for o in range(0, len(users), chunk):
         us = users[o:o + chunk]
         sc, mag = scores(weights, z, us)
-        tol = 8.0 * 2.0 ** -24 * (mag + bp[None, :])
+        tol = 8.0 * ULP24 * (mag + bp[None, :])
         for r, u in enumerate(us):
             c = torch.as_tensor(hist_col[hist_rowptr[u]:hist_rowptr[u + 1]]).long()
             sc[r, c] = 1e-6
@@ -136,12 +137,6 @@ def ranklist_check(ranks, weights, z, hist_rowptr, hist_col, topk=50, chunk=2048
         allowed = torch.maximum(torch.gather(tol, 1, got), torch.gather(tol, 1, want))
         bad += int((diff & (gap > allowed)).sum())
     return differ / float(ranks.numel()), bad
-
-
-def rel_dev(x, ref):
-    """max |x - ref| relative to the largest |ref| (for a scalar: the relative error)."""
-    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float(np.max(np.abs(x - ref)) / max(float(np.max(np.abs(ref))), 1e-300))
 
 
 def load_fixture(golden_dir, name):
@@ -169,10 +164,3 @@ def replay_draws(seed, B, I):
     torch.manual_seed(int(seed))
     mask = F.dropout(torch.ones(B, I), 0.5) != 0
     return mask.numpy(), torch.randn(B, LATENT).numpy()
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d

@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 import torch
+from accept import rel_dev, user_item_dict  # noqa: F401
 from vae_ops_host import vae_key, vae_uniform      # the counter RNG of csrc/draws.h in uint64 numpy
 
 D = 64
@@ -28,19 +29,6 @@ def with_grad(n_layers):
         if mod == "MLP" or k >= 4 or (k <= min(n_layers, 3) and not mod.startswith("linear_layer")):
             out.append(n)
     return tuple(out)
-
-
-def rel_dev(a, b):
-    """max |a - b| relative to the largest |b|."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
-
-
-def user_item_dict(edges):
-    d = {}
-    for u, i in np.asarray(edges).tolist():
-        d.setdefault(u, []).append(i)
-    return d
 
 
 def load_fixture(golden_dir, name="mvgae_small.npz"):

@@ -2,7 +2,7 @@
 tests/golden/cfdiff_small.npz, the vectorised loss history against the reference's loop, the shape checks, the keep-bit keying
 restated, and the backward identities of csrc/cfdiff.hip in float64 against autograd.
 
-Tolerance: bound = 4 * max(own, ULP) relative to the largest magnitude of the float64 array, `own` the deviation of an fp32
+Tolerance (accept.within): bound = 4 x max(own, ULP) relative to the largest magnitude of the float64 array, `own` the deviation of an fp32
 computation that is not the code under test (the reference's stored fp32 output; for the small random model the fp32 run of the
 restatement) from the float64 restatement.  Every check prints deviation, own, bound and ratio."""
 import functools
@@ -14,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import cfdiff_host as ch  # noqa: E402
 from conftest import GOLDEN, tie_aware_rank_equal  # noqa: E402
 
@@ -22,10 +23,7 @@ from chaorec_amd.Model import CF_Diff  # noqa: E402
 
 
 def within(what, got, ref, own, scale=None):
-    dev, bound = ch.rel_dev(got, ref, scale), 4 * max(float(own), ch.ULP)
-    print(f"{what}: deviation {dev:.3e} own {float(own):.3e} bound {bound:.3e} ratio {dev / bound:.3f}")
-    assert dev <= bound, f"{what}: {dev:.3e} > {bound:.3e}"
-    return dev / bound
+    return accept.within(what, got, ref, own, ch.ULP, scale=scale, zero_ref=ch.ZERO_REF)
 
 
 @functools.lru_cache(maxsize=None)
@@ -251,7 +249,7 @@ def test_p_sample_and_the_ranking():
     ref_idx = g["rank"].astype(np.int64)
     ref_val = np.take_along_axis(ch.masked(g["sample32"], edges), ref_idx - ch.U, 1)
     val = np.take_along_axis(ch.masked(x.numpy(), edges), rank.numpy() - ch.U, 1)
-    ok, why = tie_aware_rank_equal(rank.numpy(), val, ref_idx, ref_val, atol=4 * max(float(g["own_sample"]), ch.ULP) * np.abs(g["sample64"]).max())
+    ok, why = tie_aware_rank_equal(rank.numpy(), val, ref_idx, ref_val, atol=accept.bound_of(g["own_sample"], ch.ULP) * np.abs(g["sample64"]).max())
     assert ok, why
     assert np.isfinite(val).all()                                                        # no history item is listed
     assert m.full_sort_predict.__func__ is m.gene_ranklist.__func__

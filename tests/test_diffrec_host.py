@@ -2,7 +2,7 @@
 reference's own run left in tests/golden/diffrec_small.npz, the collapse of the sampling chain against the literal chain, the
 loss history against the reference's loop, and the wiring.  No kernel runs here.
 
-Tolerance: bound = 4 * max(own, ULP) relative to the largest magnitude of the float64 array, `own` the stored deviation of the
+Tolerance (accept.within): bound = 4 x max(own, ULP) relative to the largest magnitude of the float64 array, `own` the stored deviation of the
 reference's fp32 run from the float64 restatement.  Every check prints deviation, own, bound and ratio."""
 import functools
 import os
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import diffrec_host as dh  # noqa: E402
 import kernel_meta  # noqa: E402
 from conftest import GOLDEN, tie_aware_rank_equal  # noqa: E402
@@ -22,9 +23,7 @@ from chaorec_amd.Model.DiffRec import DiffRec  # noqa: E402
 
 
 def within(what, got, ref, own, scale=None):
-    dev, bound = dh.rel_dev(got, ref, scale), 4 * max(float(own), dh.ULP)
-    print(f"{what}: deviation {dev:.3e} own {float(own):.3e} bound {bound:.3e} ratio {dev / bound:.3f}")
-    assert dev <= bound, f"{what}: {dev:.3e} > {bound:.3e}"
+    accept.within(what, got, ref, own, dh.ULP, scale=scale, zero_ref=dh.ZERO_REF)
 
 
 @functools.lru_cache(maxsize=None)
@@ -156,7 +155,7 @@ def test_p_sample_and_the_ranking(collapsed):
     assert rank.shape == (dh.U, dh.TOPK) and rank.dtype == torch.int64 and int(rank.min()) >= dh.U and m.training is False
     i64, v64 = dh.top_lists(dh.masked(g["sample64"], edges))
     val = np.take_along_axis(dh.masked(x.numpy(), edges), rank.numpy() - dh.U, 1)
-    atol = 4 * max(float(g["own_sample"]), dh.ULP) * np.abs(g["sample64"]).max()
+    atol = accept.bound_of(g["own_sample"], dh.ULP) * np.abs(g["sample64"]).max()
     ok, why = tie_aware_rank_equal(rank.numpy() - dh.U, val, i64, v64, atol=atol)
     assert ok, why
     ref_idx = g["rank"].astype(np.int64)

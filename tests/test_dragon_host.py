@@ -111,11 +111,11 @@ def test_sample_law_matches_the_reference_draw(small):
             assert e_idx[u, j] in e_idx[u, :j]
         cs = np.array([count_of[u][int(i)] for i in e_idx[u]], dtype=np.float64)
         sm = np.exp(cs - cs.max())
-        assert np.abs(e_w[u] - sm / sm.sum()).max() <= 4 * 2.0 ** -24
+        assert np.abs(e_w[u] - sm / sm.sum()).max() <= 4 * dh.EPS32
     # the restated sample on the same structure: same first slots, same law, its own draws
     m_idx, m_w, src, r = dh.sample(idx, cnt, length, k, 7, 0)
     full = length >= k
-    assert np.array_equal(m_idx[full], e_idx[full]) and np.abs(m_w[full] - e_w[full]).max() <= 4 * 2.0 ** -24
+    assert np.array_equal(m_idx[full], e_idx[full]) and np.abs(m_w[full] - e_w[full]).max() <= 4 * dh.EPS32
     for u in np.nonzero(~full & (length > 0))[0]:
         for j in range(int(length[u]), k):
             assert 0 <= r[u, j] < j and m_idx[u, j] == m_idx[u, r[u, j]]

@@ -92,10 +92,10 @@ def test_sample_law_matches_the_reference_draw(small):
             assert e_idx[u, j] in e_idx[u, :j]
         cs = np.array([count_of[u][int(i)] for i in e_idx[u]], dtype=np.float64)
         sm = np.exp(cs - cs.max())
-        assert np.abs(e_w[u] - sm / sm.sum()).max() <= 4 * 2.0 ** -24
+        assert np.abs(e_w[u] - sm / sm.sum()).max() <= 4 * dh.EPS32
     m_idx, m_w, src, r = dh.sample(idx, cnt, length, k, 7, 0)
     full = length >= k
-    assert np.array_equal(m_idx[full], e_idx[full]) and np.abs(m_w[full] - e_w[full]).max() <= 4 * 2.0 ** -24
+    assert np.array_equal(m_idx[full], e_idx[full]) and np.abs(m_w[full] - e_w[full]).max() <= 4 * dh.EPS32
 
 
 @pytest.mark.parametrize("U,I,k", [(5, 0, 1), (9, 4, 3)])

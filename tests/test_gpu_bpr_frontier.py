@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import lightgcn_small_graph as small
+from accept import same_bits_t
 
 B, D, L = 8, 64, 3
 W = 1.0 / (L + 1)
@@ -81,13 +82,9 @@ def worlds(dev):
     return out
 
 
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 def _assert_same(ref, new):
     for a, b in zip(ref, new):
-        assert _same_bits(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
+        assert same_bits_t(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
 
 
 def _launch_pair(dev, wd, batch=None, poison=True, **draw):

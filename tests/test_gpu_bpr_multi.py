@@ -27,6 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bpr_multi_host as H  # noqa: E402
+from accept import lib as _lib, ptr as _ptr, ptrs as _ptrs, stream as _stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,23 +42,6 @@ def dev():
     from chaorec_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _lib():
-    from chaorec_amd import _lib as L
-    return L.load()
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
 _bits = H.bits

@@ -1,7 +1,7 @@
 """BSPM on the MI355X: the three launches of csrc/bspm.hip per operand, and the whole model against the golden the reference's
 own run left (tests/golden/bspm_small.npz).
 
-Tolerance, measured not chosen (the rule of tests/test_gpu_diffmm.py): for each compared array bound = 4 * max(own, ULP), `own`
+Tolerance, measured not chosen (accept.within): for each compared array bound = 4 x max(own, ULP), `own`
 the stored fp32 reference's deviation from the float64 restatement and ULP fp32 epsilon, both relative to the largest magnitude
 of the float64 array.  Every check prints deviation, own, bound and ratio; the per-operand checks compare against float64
 evaluated on the operands the kernel was given (the reference's fp32 Rn and P), so their deviation is the kernel's arithmetic
@@ -23,6 +23,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import bspm_host as bh  # noqa: E402
 from conftest import GOLDEN, tie_aware_rank_equal  # noqa: E402
 
@@ -60,10 +61,7 @@ def tiles(width):
 
 
 def within(what, got, ref, own, scale=None):
-    dev, bound = bh.rel_dev(got, ref, scale), 4 * max(float(own), bh.ULP)
-    print(f"{what}: deviation {dev:.3e} own {float(own):.3e} bound {bound:.3e} ratio {dev / bound:.3f}")
-    assert dev <= bound, f"{what}: {dev:.3e} > {bound:.3e}"
-    return dev / bound
+    return accept.within(what, got, ref, own, bh.ULP, scale=scale)
 
 
 def host_idl(c, u0, u1, B):
@@ -167,7 +165,7 @@ def test_model_against_the_golden(c):
     within(f"case {c} plain against float64", plain.cpu().numpy(), host64, own)
     within(f"case {c} fused against plain", fused.cpu().numpy(), plain.cpu().numpy().astype(np.float64), own, np.abs(host64).max())
     # the ranking: every row, ties aware, at the scores' bound
-    bound = 4 * max(own, bh.ULP) * np.abs(host64).max()
+    bound = accept.bound_of(own, bh.ULP) * np.abs(host64).max()
     ref_idx = g[f"rank_{c}"].astype(np.int64)
     ref_val = np.take_along_axis(bh.masked(g[f"ref32_{c}"], edges), ref_idx - bh.U, 1)
     for mdl in (model(c), model(c, fused=False)):

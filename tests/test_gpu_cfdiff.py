@@ -1,8 +1,8 @@
 """CF_Diff on the MI355X: the launches of csrc/cfdiff.hip per operand, on given and on device-drawn flags, and the whole model
 against the golden the reference's own run left (tests/golden/cfdiff_small.npz).
 
-Tolerance, measured not chosen (the rule of tests/test_gpu_bspm.py and tests/test_gpu_diffmm.py): for each compared array
-bound = 4 * max(own, ULP) relative to the largest magnitude of the float64 array; `own` is the deviation of an fp32 computation
+Tolerance, measured not chosen (accept.within, the floor ULP = 2^-23 as in tests/test_gpu_bspm.py): for each compared array
+bound = 4 x max(own, ULP) relative to the largest magnitude of the float64 array; `own` is the deviation of an fp32 computation
 that is not the code under test from the float64 restatement on the same operands -- `ops.cfdiff_attention_plain` in fp32 on the
 CPU for the per-operand checks, the reference's stored fp32 output for the golden, the fp32 run of the restatement for the
 one-step gradients.  Every check prints deviation, own, bound and ratio.
@@ -25,6 +25,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import cfdiff_host as ch  # noqa: E402
 from conftest import GOLDEN, tie_aware_rank_equal  # noqa: E402
 
@@ -38,12 +39,7 @@ SEED = 20241012
 
 
 def within(what, got, ref, own, scale=None):
-    got = got.detach().cpu().numpy() if torch.is_tensor(got) else got
-    ref = ref.detach().cpu().numpy() if torch.is_tensor(ref) else ref
-    dev, bound = ch.rel_dev(got, ref, scale), 4 * max(float(own), ch.ULP)
-    print(f"{what}: deviation {dev:.3e} own {float(own):.3e} bound {bound:.3e} ratio {dev / bound:.3f}")
-    assert dev <= bound, f"{what}: {dev:.3e} > {bound:.3e}"
-    return dev / bound
+    return accept.within(what, got, ref, own, ch.ULP, scale=scale, zero_ref=ch.ZERO_REF)      # (takes tensors as they are)
 
 
 @functools.lru_cache(maxsize=None)
@@ -308,7 +304,7 @@ def test_p_sample_and_the_ranking():
     g, edges = case()
     users = torch.arange(ch.U, device=DEV)
     scale = np.abs(g["sample64"]).max()
-    bound = 4 * max(float(g["own_sample"]), ch.ULP) * scale
+    bound = accept.bound_of(g["own_sample"], ch.ULP) * scale
     ref_idx = g["rank"].astype(np.int64)
     ref_val = np.take_along_axis(ch.masked(g["sample32"], edges), ref_idx - ch.U, 1)
     rows = {}

@@ -22,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dragon_host as dh  # noqa: E402
 import cohesion_host as ch  # noqa: E402
+from accept import same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -40,10 +41,6 @@ def _structure(dev, U, idx=None, w=None):
     if idx is not None:
         s.set_epoch(torch.as_tensor(idx).to(dev), torch.as_tensor(w).to(dev))
     return s
-
-
-def _bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
 
 
 # ---- the node ------------------------------------------------------------------------------------------------------------------
@@ -112,8 +109,8 @@ def test_fuse(dev, U, I, k, with_h):
     runs = [_run_node(dev, s, U, idr, v, t, h, g, chunk, fill) for fill in (float("nan"), 1e30)]
     names = ("result", "dv", "dt", "dh_v", "dh_t")
     for name, a, b, ref in zip(names, runs[0], runs[1], want):
-        assert _bits(a, b), f"{name}: two runs differ in their bits"
-        assert _bits(a, ref), f"{name}: differs from the float32 restatement in {int((a != ref).sum())} elements"
+        assert same_bits(a, b), f"{name}: two runs differ in their bits"
+        assert same_bits(a, ref), f"{name}: differs from the float32 restatement in {int((a != ref).sum())} elements"
     # ... and against float64 within the bound of any fixed order
     out64, b_out, n = ch.fuse_fwd64(idr, v, t, h, idx, w, U)
     (dv64, dt64), (b_dv, b_dt), n_b = ch.fuse_bwd64(g, idx, w, U)
@@ -149,7 +146,7 @@ def test_chunk_edges(dev, chunk):
         s = _structure(dev, U, idx, w)
         got = _run_node(dev, s, U, idr, v, t, None, g, chunk, float("nan"))
         for name, a, ref in zip(("result", "dv", "dt"), got, [ch.fuse_fwd32(idr, v, t, None, idx, w, U)] + list(ch.fuse_bwd32(g, idx, w, U, chunk, False))):
-            assert _bits(a, ref), f"chunk {chunk}, m {m}: {name} differs from the float32 restatement"
+            assert same_bits(a, ref), f"chunk {chunk}, m {m}: {name} differs from the float32 restatement"
         # the chunk index the wrapper built with tensor ops = the host's
         rev_ptr, _, row_chunk, rows, first, _ = ch.rev_chunks(idx, U, chunk)
         c = s.rev_chunks[chunk]
@@ -172,7 +169,7 @@ def test_chunk_sizes_against_each_other(dev):
     s = _structure(dev, U, idx, w)
     by_chunk = {c: _run_node(dev, s, U, idr, v, t, h, g, c, 1e30) for c in (0, 4, 64)}
     for a, ref in zip(by_chunk[0][1:], ch.fuse_bwd32(g, idx, w, U, 0)):
-        assert _bits(a, ref), "chunk = 0 differs from the single-walk restatement"
+        assert same_bits(a, ref), "chunk = 0 differs from the single-walk restatement"
     assert set(s.rev_chunks) == {0, 4, 64} and s.rev_chunks[0].n_chunks == int((np.diff(dh.reverse(idx, U)[0]) > 0).sum())
     (dv64, dt64), (b_dv, b_dt), n = ch.fuse_bwd64(g, idx, w, U)
     assert n == 3 * 64 + 8
@@ -180,9 +177,9 @@ def test_chunk_sizes_against_each_other(dev):
         a, b = by_chunk[4][j].astype(np.float64), by_chunk[64][j].astype(np.float64)
         assert not np.array_equal(a[7], b[7])                    # user 7's 199 entries are summed in another order ...
         assert (np.abs(a - ref) <= bound).all() and (np.abs(b - ref) <= bound).all() and (np.abs(a - b) <= 2 * bound).all()
-        assert _bits(by_chunk[4][j][U:], by_chunk[64][j][U:])    # ... the item rows are copies
+        assert same_bits(by_chunk[4][j][U:], by_chunk[64][j][U:])    # ... the item rows are copies
     for j in (0, 3, 4):                                          # the forward and the h gradients do not depend on chunk
-        assert _bits(by_chunk[4][j], by_chunk[64][j]) and _bits(by_chunk[0][j], by_chunk[64][j])
+        assert same_bits(by_chunk[4][j], by_chunk[64][j]) and same_bits(by_chunk[0][j], by_chunk[64][j])
 
 
 def test_nan_in_the_id_columns_of_g_stays_out(dev):
@@ -193,7 +190,7 @@ def test_nan_in_the_id_columns_of_g_stays_out(dev):
     g2 = g.copy()
     g2[:, :D] = np.nan
     for a, b in zip(_run_node(dev, s, U, idr, v, t, h, g2, 4, 1e30)[1:], clean[1:]):
-        assert np.isfinite(a).all() and _bits(a, b)
+        assert np.isfinite(a).all() and same_bits(a, b)
 
 
 def test_fuse_rejects(dev):

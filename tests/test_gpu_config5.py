@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from accept import ULP24
+
 pytestmark = pytest.mark.gpu
 
 D, L = 128, 3
@@ -63,7 +65,7 @@ def test_spmm_rows_vs_oracle_and_fp64(shard, oracle):
         s, e = sub_rp[k], sub_rp[k + 1]
         terms = val[take[s:e]].astype(np.float64)[:, None] * xh[col[take[s:e]]].astype(np.float64)
         ref[k], mass[k] = terms.sum(0), np.abs(terms).sum(0)
-    bound = (deg[rows][:, None] + 1) * 2.0 ** -24 * mass
+    bound = (deg[rows][:, None] + 1) * ULP24 * mass
     assert np.all(np.abs(got - ref) <= bound + 1e-30)
     light = deg[rows] <= 64
     assert np.abs(got - ref)[light].max() <= 2e-6 * np.abs(ref)[light].max()

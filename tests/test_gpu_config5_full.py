@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from accept import ULP24
+
 pytestmark = pytest.mark.gpu
 
 D, L = 128, 3
@@ -89,7 +91,7 @@ def test_spmm_rows_vs_oracle_and_fp64(full, oracle):
         s, e = sub_rp[k], sub_rp[k + 1]
         terms = val[s:e].astype(np.float64)[:, None] * xs[inv[s:e]].astype(np.float64)
         ref[k], mass[k] = terms.sum(0), np.abs(terms).sum(0)
-    bound = (sdeg[:, None] + 1) * 2.0 ** -24 * mass
+    bound = (sdeg[:, None] + 1) * ULP24 * mass
     assert np.all(np.abs(got - ref) <= bound + 1e-30)
     light = sdeg <= 64
     assert np.abs(got - ref)[light].max() <= 2e-6 * np.abs(ref)[light].max()

@@ -34,6 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dgcf_ops_host as H  # noqa: E402
+from accept import lib as _lib, ptr as _ptr, stream as _stream, up as _up  # noqa: E402
 from test_dgcf_host import dgcf_forward as dgcf_forward64  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -49,23 +50,6 @@ def dev():
     from chaorec_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _lib():
-    from chaorec_amd import _lib as L
-    return L.load()
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _up(dev, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _is_sentinel(a):

@@ -8,7 +8,7 @@ Device draws: keyed (seed, step, salt, user, item) only; over 10^6 kept elements
 |var - 1| <= 5 sqrt(2 / N), |keep rate - 1/2| <= 5 / (2 sqrt(N)) (five standard errors of the three estimators).
 One-pass node: tolerance measured and not chosen -- the reference's own lines in torch fp32 on the CPU on the same inputs
 (diffmm_host.node_all), their deviation from float64 relative to the tensor's largest magnitude, asserted below 1e-4; the
-kernels are allowed 4 x max(that, 2^-24).  Every case runs twice over allocator memory dirtied with NaN, then 1e30: the two
+kernels are allowed 4 x max(that, 2^-24) (accept.within_measured).  Every case runs twice over allocator memory dirtied with NaN, then 1e30: the two
 runs agree in their bits.  An incoming gradient of 0.37 is held to the same rule against 0.37 x the float64 gradients.
 Every row of the node's x0 holds an interaction, as every user of a dataset does: the rule measures against a tensor's largest
 magnitude, and at I = 1 a tensor is one number per row -- err = out - x0 with x0 = 1 is then a sum led by an exact term,
@@ -27,10 +27,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import diffmm_host as mh  # noqa: E402
+from accept import ULP24, bound_of, same_bits, within, within_measured  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-ULP = 2.0 ** -24
 MODS = ("image", "text")
 
 
@@ -45,11 +45,6 @@ def _tiles():
     return ops_extra.diffmm_tiles()
 
 
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
 def _dirty(dev, B, I, H, fill):
     """Junk where the allocator will hand out the rows, the bit table, d_out, the partials and the gradients."""
     for shape in ((3 * B, I + 8), (2 * B, H), (2 * I, H), (B, 64), (B, I // 32 + 2), (I + 8,), (B + 8,), (1,)):
@@ -57,20 +52,6 @@ def _dirty(dev, B, I, H, fill):
     torch.full((B + 8,), fill, dtype=torch.float64, device=dev)
     torch.full((B, I // 32 + 2), -1, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
-
-
-def _check(name, got, ref32, ref64, failures, ratios):
-    """got within 4 x max(the fp32 reference's own deviation, 2^-24) of the float64 restatement, relative to its largest
-    magnitude; the reference's deviation itself below 1e-4."""
-    scale = max(float(np.abs(np.asarray(ref64)).max()), 1e-300)
-    own = float(np.abs(np.asarray(ref32, dtype=np.float64) - ref64).max()) / scale
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max()) / scale
-    assert np.isfinite(np.asarray(ref32)).all() and own < 1e-4, f"{name}: the fp32 reference itself deviates by {own:.3e}"
-    bound = 4 * max(own, ULP)
-    ratios.append(err / bound)
-    print(f"{name}: deviation {err:.3e}, the fp32 reference's own {own:.3e}, bound {bound:.3e}, ratio {err / bound:.3f}")
-    if not (np.isfinite(np.asarray(got)).all() and err <= bound):
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
 
 
 # ---- (a) the rows launch -------------------------------------------------------------------------------------------------------
@@ -119,10 +100,10 @@ def test_rows_given_draws_bit_for_bit(dev, Bk, I):
         for got, ref, name in ((x, want, "noised"), (xp, x0, "plain")):
             assert tuple(got.shape) == (B, I) and got.stride() == (ld, 1)
             full = got.as_strided((B, ld), (ld, 1)).cpu().numpy()
-            assert _bits(full[:, :I], ref), f"{name}: x_in differs from the float32 restatement"
-            assert _bits(full[:, I:], np.zeros((B, ld - I), dtype=np.float32)), f"{name}: pad columns"
+            assert same_bits(full[:, :I], ref), f"{name}: x_in differs from the float32 restatement"
+            assert same_bits(full[:, I:], np.zeros((B, ld - I), dtype=np.float32)), f"{name}: pad columns"
         for b in (bits, bits_p):
-            assert _bits(b.cpu().numpy().view(np.uint32), mh.bit_table(x0)), "bit table"
+            assert same_bits(b.cpu().numpy().view(np.uint32), mh.bit_table(x0)), "bit table"
     if B >= 3:
         assert not x0[1].any() and np.array_equal(x0[0], x0[2])          # the empty row, the repeated user
 
@@ -138,10 +119,10 @@ def test_device_draws_keyed_by_user_and_item(dev):
     order = np.random.default_rng(0).permutation(19)
     y, _ = ops_extra.diffmm_rows(d(users[order]), d(rowptr), d(col), I, a, s, seed=9, step=4, salt=1)
     z, _ = ops_extra.diffmm_rows(d(users[order][:7]), d(rowptr), d(col), I, a[:7], s[:7], seed=9, step=4, salt=1)
-    assert _bits(x.cpu().numpy()[order], y.cpu().numpy()) and _bits(y.cpu().numpy()[:7], z.cpu().numpy())
+    assert same_bits(x.cpu().numpy()[order], y.cpu().numpy()) and same_bits(y.cpu().numpy()[:7], z.cpu().numpy())
     for other in (dict(seed=10, step=4, salt=1), dict(seed=9, step=5, salt=1), dict(seed=9, step=4, salt=0)):
         o, _ = ops_extra.diffmm_rows(d(users), d(rowptr), d(col), I, a, s, **other)
-        assert not _bits(x.cpu().numpy(), o.cpu().numpy())
+        assert not same_bits(x.cpu().numpy(), o.cpu().numpy())
 
 
 def test_device_draws_statistics(dev):
@@ -238,12 +219,12 @@ def test_one_pass_node(dev, Bk, Ik, Hk):
     case, e_loss = node_case(B, I, Hd, 10000 * B + 10 * I + Hk), 0.01
     runs = [run_node(dev, case, e_loss, 1.0, fill) for fill in (float("nan"), 1e30)]
     for k in runs[0]:
-        assert _bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
+        assert same_bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
     failures, ratios = [], []
     for g, got in ((1.0, runs[0]), (0.37, run_node(dev, case, e_loss, 0.37, 1e30))):
         r64, r32 = mh.node_all(*case, e_loss, torch.float64, g=g), mh.node_all(*case, e_loss, torch.float32, g=g)
         for k in ("loss", "diff_rows", "gc_rows", "d_out", "dW_out", "db_out", "dh"):
-            _check(f"node B={B} I={I} H={Hd} g={g} {k}", got[k], r32[k], r64[k], failures, ratios)
+            within_measured(f"node B={B} I={I} H={Hd} g={g} {k}", got[k], r32[k], r64[k], ULP24, failures=failures, ratios=ratios)
     print(f"node B={B} I={I} H={Hd}: largest ratio {max(ratios):.3f}")
     assert not failures, failures
 
@@ -272,18 +253,6 @@ def fx(dev):
     return dict(g=g, c=c, model=model, w=w, steps=steps, hist=(rowptr, col))
 
 
-def _check_dev(name, got, ref64, dev_ref, failures, ratios):
-    """within 4 x max(the reference's stored deviation, 2^-24) of the float64 restatement, relative to its largest magnitude"""
-    scale = max(float(np.abs(np.asarray(ref64)).max()), 1e-300)
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max()) / scale
-    assert float(dev_ref) < 1e-4
-    bound = 4 * max(float(dev_ref), ULP)
-    ratios.append(err / bound)
-    print(f"{name}: deviation {err:.3e}, the reference's own {float(dev_ref):.3e}, bound {bound:.3e}, ratio {err / bound:.3f}")
-    if not (np.isfinite(np.asarray(got)).all() and err <= bound):
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
-
-
 @pytest.mark.parametrize("fused", [True, False])
 def test_model_diffusion_step(fx, dev, fused):
     g, c, model = fx["g"], fx["c"], fx["model"]
@@ -299,11 +268,11 @@ def test_model_diffusion_step(fx, dev, fused):
     failures, ratios = [], []
     for m, (mod, loss) in enumerate(zip(MODS, (li, lt))):
         h = fx["steps"][m]
-        _check_dev(f"{mod} loss", float(loss), h["loss"], g[f"dev_step_{mod}_loss"], failures, ratios)
-        _check_dev(f"{mod} diff_loss", model.last[mod]["diff_loss"].cpu().numpy(), h["diff_loss"], g[f"dev_step_{mod}_diff"], failures, ratios)
-        _check_dev(f"{mod} gc_loss", model.last[mod]["gc_loss"].cpu().numpy(), h["gc_loss"], g[f"dev_step_{mod}_gc"], failures, ratios)
+        within(f"{mod} loss", float(loss), h["loss"], g[f"dev_step_{mod}_loss"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
+        within(f"{mod} diff_loss", model.last[mod]["diff_loss"].cpu().numpy(), h["diff_loss"], g[f"dev_step_{mod}_diff"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
+        within(f"{mod} gc_loss", model.last[mod]["gc_loss"].cpu().numpy(), h["gc_loss"], g[f"dev_step_{mod}_gc"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
         for n, ref in h["grads"].items():
-            _check_dev(n, params[n].grad.cpu().numpy(), ref, g["dev_grad_" + n], failures, ratios)
+            within(n, params[n].grad.cpu().numpy(), ref, g["dev_grad_" + n], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     assert all(params[n].grad is None for n in mh.NAMES if not n.startswith("denoise_model_"))
     print(f"model step fused={fused}: largest ratio {max(ratios):.3f}")
     model.fused_denoise = True
@@ -325,7 +294,7 @@ def test_model_rebuild(fx, dev, fused):
             idx, x_t = model.denoised_topk(dn, torch.arange(U, device=dev))
             assert np.array_equal(idx.cpu().numpy(), g[f"top_{mod}"]), f"{mod}: top-1"
             # against the reference's own fp32 iterate: our 4 x max(its deviation, 2^-24) from float64 plus its deviation from it
-            assert mh.rel_dev(x_t.cpu().numpy(), g[f"iter_{mod}"][-1]) <= 4 * max(float(g[f"dev_iter_{mod}"]), ULP) + float(g[f"dev_iter_{mod}"])
+            assert mh.rel_dev(x_t.cpu().numpy(), g[f"iter_{mod}"][-1]) <= bound_of(g[f"dev_iter_{mod}"], ULP24) + float(g[f"dev_iter_{mod}"])
     adjs = model.rebuild_graphs(loader, rand=rand, as_csr=False)
     csrs = model.rebuild_graphs(loader, rand=rand)
     model.fused_denoise = True
@@ -355,12 +324,12 @@ def test_model_loss_gradients_and_ranking(fx, dev):
     loss.backward()
     torch.cuda.synchronize()
     failures, ratios = [], []
-    _check_dev("loss", float(loss), h["loss"], g["dev_loss"], failures, ratios)
-    _check_dev("usr", model.restore_usrEmbeds.detach().cpu().numpy(), h["usr"], g["dev_usr"], failures, ratios)
-    _check_dev("itm", model.restore_itmEmbeds.detach().cpu().numpy(), h["itm"], g["dev_itm"], failures, ratios)
+    within("loss", float(loss), h["loss"], g["dev_loss"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
+    within("usr", model.restore_usrEmbeds.detach().cpu().numpy(), h["usr"], g["dev_usr"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
+    within("itm", model.restore_itmEmbeds.detach().cpu().numpy(), h["itm"], g["dev_itm"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     params = dict(model.named_parameters())
     for n, ref in h["grads"].items():
-        _check_dev("grad " + n, params[n].grad.cpu().numpy(), ref, g["dev_grad_" + n], failures, ratios)
+        within("grad " + n, params[n].grad.cpu().numpy(), ref, g["dev_grad_" + n], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     print(f"model loss: largest ratio {max(ratios):.3f}")
     assert not failures, failures
     K = g["rank"].shape[1]

@@ -7,7 +7,7 @@ float4, one k-tile, a partial k-tile, a segment edge, one past it, the default w
 product, 120 cases per kernel.
 Tolerance, measured and not chosen: the reference's own lines in torch fp32 on the CPU on the same inputs, their deviation from
 float64 relative to the tensor's largest magnitude, asserted below 1e-4; the kernels are allowed 4 x max(that, 2^-24)
-(test_gpu_diffmm's rule).  Every case runs twice over allocator memory dirtied with NaN, then 1e30: the two runs agree in their
+(accept.within_measured).  Every case runs twice over allocator memory dirtied with NaN, then 1e30: the two runs agree in their
 bits.  pt is not all ones; an incoming gradient of 0.37 is held to the same rule against 0.37 x the float64 gradients.
 Every row of the loss node's x0 holds an interaction, for the reason test_gpu_diffmm gives: the rule measures against a
 tensor's largest magnitude, and at B = I = 1 a tensor is one number, err = out - 1.  That number is led by the exact term only
@@ -34,10 +34,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import diffrec_host as dh  # noqa: E402
+from accept import ULP24, bound_of, same_bits, within, within_measured  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-ULP = 2.0 ** -24
 BS, NS, KS = (1, 127, 128, 129), (1, 127, 128, 129, 259), (4, 16, 20, 64, 68, 1000)
 
 
@@ -50,43 +50,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
 def _dirty(dev, B, N, K, fill):
     """Junk where the allocator will hand out d_out, the partials, the chain's outputs and the gradients."""
     for shape in ((3 * B, N + 8), (2 * B, K), (2 * N, K), (B, N // 128 + 2), (N + 8,), (B + 8,), (1,)):
         torch.full(shape, fill, device=dev)
     torch.full((B + 8,), fill, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
-
-
-def _check(name, got, ref32, ref64, failures, ratios):
-    """got within 4 x max(the fp32 reference's own deviation, 2^-24) of the float64 restatement, relative to its largest
-    magnitude; the reference's deviation itself below 1e-4."""
-    scale = max(float(np.abs(np.asarray(ref64)).max()), 1e-300)
-    own = float(np.abs(np.asarray(ref32, dtype=np.float64) - ref64).max()) / scale
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max()) / scale
-    assert np.isfinite(np.asarray(ref32)).all() and own < 1e-4, f"{name}: the fp32 reference itself deviates by {own:.3e}"
-    bound = 4 * max(own, ULP)
-    ratios.append(err / bound)
-    print(f"{name}: deviation {err:.3e}, the fp32 reference's own {own:.3e}, bound {bound:.3e}, ratio {err / bound:.3f}")
-    if not (np.isfinite(np.asarray(got)).all() and err <= bound):
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
-
-
-def _check_dev(name, got, ref64, dev_ref, failures, ratios):
-    """within 4 x max(the reference's stored deviation, 2^-24) of the float64 restatement, relative to its largest magnitude"""
-    scale = max(float(np.abs(np.asarray(ref64)).max()), 1e-300)
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max()) / scale
-    assert float(dev_ref) < 1e-4
-    bound = 4 * max(float(dev_ref), ULP)
-    ratios.append(err / bound)
-    print(f"{name}: deviation {err:.3e}, the reference's own {float(dev_ref):.3e}, bound {bound:.3e}, ratio {err / bound:.3f}")
-    if not (np.isfinite(np.asarray(got)).all() and err <= bound):
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
 
 
 # ---- (a) the loss node ----------------------------------------------------------------------------------------------------------
@@ -130,12 +99,12 @@ def test_loss_node(dev, B, I, Hd):
     case = loss_case(B, I, Hd, 10000 * B + 10 * I + Hd)
     runs = [run_loss(dev, case, 1.0, fill) for fill in (float("nan"), 1e30)]
     for k in runs[0]:
-        assert _bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
+        assert same_bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
     failures, ratios = [], []
     for g, got in ((1.0, runs[0]), (0.37, run_loss(dev, case, 0.37, 1e30))):
         r64, r32 = dh.loss_node(*case, torch.float64, g=g), dh.loss_node(*case, torch.float32, g=g)
         for k in ("loss", "reloss_rows", "d_out", "dW_out", "db_out", "dh"):
-            _check(f"loss node B={B} I={I} H={Hd} g={g} {k}", got[k], r32[k], r64[k], failures, ratios)
+            within_measured(f"loss node B={B} I={I} H={Hd} g={g} {k}", got[k], r32[k], r64[k], ULP24, failures=failures, ratios=ratios)
     print(f"loss node B={B} I={I} H={Hd}: largest ratio {max(ratios):.3f}")
     assert not failures, failures
 
@@ -168,8 +137,8 @@ def test_chain_step(dev, B, N, K):
     r64, r32 = dh.chain_step(*case, torch.float64), dh.chain_step(*case, torch.float32)
     failures, ratios = [], []
     for k in ("p_next", "z_next"):
-        assert _bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
-        _check(f"chain B={B} N={N} K={K} {k}", runs[0][k], r32[k], r64[k], failures, ratios)
+        assert same_bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
+        within_measured(f"chain B={B} N={N} K={K} {k}", runs[0][k], r32[k], r64[k], ULP24, failures=failures, ratios=ratios)
     sat = np.abs(r64["z_next"])
     assert B * N < 64 or ((sat > 0.9).any() and (sat < 0.3).any())
     print(f"chain B={B} N={N} K={K}: largest ratio {max(ratios):.3f}")
@@ -189,7 +158,7 @@ def test_strided_operands_travel_in_place_or_are_copied(dev):
         got = ops.diffrec_out_loss_raw(wide_h[:, :20], wide_W[:, :20], torch.from_numpy(b).to(dev), bits, torch.from_numpy(wt).to(dev),
                                        torch.from_numpy(pt).to(dev))
         for a, c in zip(ref, got):
-            assert _bits(a.cpu().numpy(), c.cpu().numpy())
+            assert same_bits(a.cpu().numpy(), c.cpu().numpy())
 
 
 def test_refused_shapes_raise_without_a_launch(dev):
@@ -236,11 +205,11 @@ def test_model_diffusion_step(fx, dev, fused):
     torch.cuda.synchronize()
     model.fused = True
     failures, ratios = [], []
-    _check_dev("loss", float(loss.detach()), g["loss64"], g["own_loss"], failures, ratios)
+    within("loss", float(loss.detach()), g["loss64"], g["own_loss"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     assert model.last["reloss"].dtype == torch.float64
-    _check_dev("reloss", model.last["reloss"].cpu().numpy(), g["reloss64"], g["own_reloss"], failures, ratios)
+    within("reloss", model.last["reloss"].cpu().numpy(), g["reloss64"], g["own_reloss"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     for n, p in model.named_parameters():
-        _check_dev("grad " + n, p.grad.cpu().numpy(), g["grad64_" + n], g["own_grad_" + n], failures, ratios)
+        within("grad " + n, p.grad.cpu().numpy(), g["grad64_" + n], g["own_grad_" + n], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     assert np.array_equal(model.Lt_count.cpu().numpy(), np.bincount(g["ts"], minlength=dh.STEPS))
     print(f"model step fused={fused}: largest ratio {max(ratios):.3f}")
     assert not failures, failures
@@ -293,10 +262,10 @@ def test_fused_against_plain_on_the_same_device_draws(fx, dev):
     r64, r32 = dh.training_step(dh.weights_of(g), *args), dh.training_step(dh.weights_of(g, torch.float32), *args)
     failures, ratios = [], []
     for name, got in (("fused", fused), ("plain", plain)):
-        _check(f"{name} loss", got["loss"], r32["loss"], r64["loss"], failures, ratios)
-        _check(f"{name} reloss", got["reloss"], r32["reloss"], r64["reloss"], failures, ratios)
+        within_measured(f"{name} loss", got["loss"], r32["loss"], r64["loss"], ULP24, failures=failures, ratios=ratios)
+        within_measured(f"{name} reloss", got["reloss"], r32["reloss"], r64["reloss"], ULP24, failures=failures, ratios=ratios)
         for n in dh.NAMES:
-            _check(f"{name} grad {n}", got[n], r32["grads"][n], r64["grads"][n], failures, ratios)
+            within_measured(f"{name} grad {n}", got[n], r32["grads"][n], r64["grads"][n], ULP24, failures=failures, ratios=ratios)
     print(f"fused and plain on device draws: largest ratio {max(ratios):.3f}")
     model.Lt_history.zero_()
     model.Lt_count.zero_()
@@ -314,12 +283,12 @@ def test_p_sample_routes_and_the_ranking(fx, dev):
     with torch.no_grad():
         col = model.p_sample(x0)
         lit = model.p_sample_literal(x0)
-    _check_dev("p_sample collapsed", col.cpu().numpy(), g["sample64"], g["own_sample"], failures, ratios)
-    _check_dev("p_sample literal", lit.cpu().numpy(), g["sample64"], g["own_sample"], failures, ratios)
+    within("p_sample collapsed", col.cpu().numpy(), g["sample64"], g["own_sample"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
+    within("p_sample literal", lit.cpu().numpy(), g["sample64"], g["own_sample"], ULP24, own_cap=1e-4, failures=failures, ratios=ratios)
     print(f"p_sample: largest ratio {max(ratios):.3f}")
     assert not failures, failures
     i64, v64 = dh.top_lists(dh.masked(g["sample64"], edges))
-    atol = 4 * max(float(g["own_sample"]), ULP) * np.abs(g["sample64"]).max()
+    atol = bound_of(g["own_sample"], ULP24) * np.abs(g["sample64"]).max()
     for collapsed, scores in ((True, col), (False, lit)):
         model.collapsed = collapsed
         rank = model.gene_ranklist(dh.TOPK, batch_size=5).numpy()              # three user ranges, the last of two users

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from accept import same_bits_t
 from lightgcn_small_graph import EMPTY_ROW, LONG_ROW, MID_ROW, N, ONE_ROW, small_edges
 
 WIDE_USER, WIDE_ITEM = 1000, 601
@@ -63,10 +64,6 @@ def _operands(dev, gr, D):
     return x, torch.where(keep, z, torch.zeros_like(z)), torch.where(keep, z, torch.full_like(z, float("nan")))
 
 
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 @pytest.mark.gpu
 def test_plain_launch_reads_z_through_its_bitmap(dev, small):
     from chaorec_amd import ops
@@ -76,7 +73,7 @@ def test_plain_launch_reads_z_through_its_bitmap(dev, small):
     y = torch.full_like(ref, float("nan"))
     ops.spmm_rowsparse_raw(csr, x, y, alpha=0.25, z=znan, beta=0.75, z_bits=small["bits"])
     torch.cuda.synchronize()
-    assert _same_bits(y, ref)
+    assert same_bits_t(y, ref)
 
 
 @pytest.mark.gpu
@@ -108,9 +105,9 @@ def test_adam_launch_reads_z_through_its_bitmap_and_clears_it_last(dev, small, w
                           clear_bits=(bits_new,), z_bits=bits_new, ticket=ticket)
         torch.cuda.synchronize()
         for a, b in zip(ref + [g_ref], new + [g_new]):
-            assert _same_bits(a, b), launch
+            assert same_bits_t(a, b), launch
         assert not bool(z_ref.any())
-        assert _same_bits(z_new, torch.where(keep, torch.zeros_like(znan), znan)), launch
+        assert same_bits_t(z_new, torch.where(keep, torch.zeros_like(znan), znan)), launch
         assert not bool(bits_new.any()) and not bool(bits_ref.any()) and not bool(ticket.any()), launch
 
 

@@ -16,19 +16,18 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import grade_host as gh  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
+ULP = accept.ULP24
 D_EMPTY = float(np.float32(1.0) / np.sqrt(np.float32(1e-7)))          # (1e-7f)^-1/2
 
 
 def within(x, ref, dev, what):
-    got, bound = gh.rel_dev(x, ref), 4 * max(float(dev), ULP)
-    print(f"{what}: deviation {got:.3e}, reference's own {float(dev):.3e}, bound {bound:.3e}, ratio {got / bound:.3f}")
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    accept.within(what, x, ref, dev, ULP)
 
 
 def dev():
@@ -36,7 +35,7 @@ def dev():
 
 
 def t(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x), dtype=dtype).to(dev())
+    return accept.to_dev(x, dtype, dev())
 
 
 @functools.lru_cache(maxsize=None)

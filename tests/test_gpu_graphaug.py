@@ -17,21 +17,19 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import graphaug_host as gh  # noqa: E402
 import vae_ops_host as vo  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
 LSE_SHAPES = ((33, 97), (1, 5), (64, 32 * 64 + 1))       # a partial row tile, a table below one tile, a last split of one row
 INV_TEMP = 20.0
 
 
 def within(x, ref, dev, what):
-    got, bound = gh.rel_dev(x, ref), 4 * max(float(dev), ULP)
-    print(f"{what}: deviation {got:.3e}, reference's own {float(dev):.3e}, bound {bound:.3e}")
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    accept.within(what, x, ref, dev, accept.ULP24)
 
 
 def dev():
@@ -39,7 +37,7 @@ def dev():
 
 
 def t(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x), dtype=dtype).to(dev())
+    return accept.to_dev(x, dtype, dev())
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,6 +7,7 @@ import ctypes
 import pytest
 import torch
 
+from accept import same_bits_t
 from lightgcn_small_graph import N, N_ITEM, N_USER, small_edges
 
 B, D, L = 8, 64, 3
@@ -37,10 +38,6 @@ def layers(dev):
     return xs, final
 
 
-def _same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 def _bpr_pair(dev, layers, batch):
     """-> (reference, new): workspace, coef, ids, G, bitmap of the launch over `final` and of the one over the layer tables."""
     from chaorec_amd import ops
@@ -61,7 +58,7 @@ def _bpr_pair(dev, layers, batch):
                         num_item=N_ITEM, row_bits=bits, **src)
         torch.cuda.synchronize()
         out.append([ws, coef, G, bits, *ids])
-    assert _same_bits(rows, final[rows_read.view(3, B).t().reshape(-1)])       # triple b's rows at 3 b, 3 b + 1, 3 b + 2
+    assert same_bits_t(rows, final[rows_read.view(3, B).t().reshape(-1)])       # triple b's rows at 3 b, 3 b + 1, 3 b + 2
     return out
 
 
@@ -73,7 +70,7 @@ def test_bpr_over_layer_tables_ordered_mode_repeated_rows(dev, layers):
     ref, new = _bpr_pair(dev, layers, REPEATS)
     assert bool(ref[2].any())
     for a, b in zip(ref, new):
-        assert _same_bits(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
+        assert same_bits_t(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
 
 
 @pytest.mark.gpu
@@ -83,7 +80,7 @@ def test_bpr_over_layer_tables_atomic_mode(dev, layers, monkeypatch):
     ref, new = _bpr_pair(dev, layers, DISTINCT)
     assert bool(ref[2].any())
     for a, b in zip(ref, new):
-        assert _same_bits(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
+        assert same_bits_t(a, b) if a.dtype == torch.float32 else torch.equal(a, b)
 
 
 def test_layer_table_argument_checks():
@@ -150,4 +147,4 @@ def test_step_with_the_switches_equals_step_without(dev, capture, sparse, light,
         for s0, s1 in zip(out["0", "0"], out[mode]):
             assert len(s0) == len(s1)
             for a, b in zip(s0, s1):
-                assert _same_bits(a, b) if a.dtype == torch.float32 else torch.equal(a, b), mode
+                assert same_bits_t(a, b) if a.dtype == torch.float32 else torch.equal(a, b), mode

@@ -36,7 +36,7 @@ def _model(dev, U, I, edges, D, L, seed=0):
     return m, FusedAdam(m.parameters(), lr=LR)
 
 
-def _check(route, step, opt, U, I, csr, L, reg, table, result, batch=None, light=False):
+def _check_step(route, step, opt, U, I, csr, L, reg, table, result, batch=None, light=False):
     """run ONE step of `step` and hold it to the fp64 reference; table() / result() read the joined table / the layer mean"""
     W0, m0, v0 = table().clone(), step.m.clone(), step.v.clone()
     t = int(opt._step_dev) + 1
@@ -69,8 +69,8 @@ def _check(route, step, opt, U, I, csr, L, reg, table, result, batch=None, light
     return r
 
 
-def _fused_check(route, step, model, opt, batch=None, light=False):
-    return _check(route, step, opt, model.num_user, model.num_item, model.graph, model.n_layers, model.reg_weight,
+def _fused_check_step(route, step, model, opt, batch=None, light=False):
+    return _check_step(route, step, opt, model.num_user, model.num_item, model.graph, model.n_layers, model.reg_weight,
                   lambda: model._flat, lambda: step.final if light else model.result, batch, light)
 
 
@@ -91,10 +91,10 @@ def test_bench_step_sports(dev, ordered, monkeypatch):
     step = FusedLightGCNStep(model, opt, batch_size=1024, edges=_drawn(dev, d["train"]), seed=3, step_dev=cnt)
     assert step.graph is not None and not step.light
     for _ in range(3):
-        _fused_check(f"bench sports captured, ordered={ordered}", step, model, opt)
+        _fused_check_step(f"bench sports captured, ordered={ordered}", step, model, opt)
     step.run(27)
     for _ in range(2):
-        _fused_check(f"bench sports captured, ordered={ordered}", step, model, opt)
+        _fused_check_step(f"bench sports captured, ordered={ordered}", step, model, opt)
     assert int(opt._step_dev) == 32
 
 
@@ -112,9 +112,9 @@ def test_baby_widths_and_depths(dev, D, L, capture, ordered, monkeypatch):
     step = FusedLightGCNStep(model, opt, batch_size=1024, edges=_drawn(dev, d["train"]), seed=5, step_dev=cnt,
                              capture=capture)
     route = f"baby D={D} L={L} {'captured' if capture else 'eager'}, ordered={ordered}"
-    _fused_check(route, step, model, opt)
+    _fused_check_step(route, step, model, opt)
     step.run(3)
-    _fused_check(route, step, model, opt)
+    _fused_check_step(route, step, model, opt)
 
 
 # ---- batch edges ------------------------------------------------------------------------------------------------------
@@ -142,7 +142,7 @@ def test_given_batch_repeats_and_isolated_rows(dev, case, monkeypatch):
         sel = rng.integers(0, len(edges), B)
         negs = rng.choice(isolated, B) if case != "repeats_atomic" else rng.integers(U, U + I, B)
         batch = [torch.from_numpy(a.astype(np.int64)).to(dev) for a in (edges[sel, 0], edges[sel, 1], negs)]
-        _fused_check(f"given batch, {case}", step, model, opt, batch)
+        _fused_check_step(f"given batch, {case}", step, model, opt, batch)
 
 
 @pytest.mark.parametrize("B,ordered", [(1, "1"), (3, "2"), (1023, "1"), (5462, "2")])
@@ -156,7 +156,7 @@ def test_batch_sizes(dev, B, ordered, monkeypatch):
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
     step = FusedLightGCNStep(model, opt, batch_size=B, edges=_drawn(dev, d["train"]), seed=9, step_dev=cnt)
     for _ in range(2):
-        _fused_check(f"baby B={B}, ordered={ordered}", step, model, opt)
+        _fused_check_step(f"baby B={B}, ordered={ordered}", step, model, opt)
 
 
 def test_wide_rows_are_refused(dev, monkeypatch):
@@ -194,7 +194,7 @@ def test_light_and_row_sparse_routes(dev, D, L, light, capture, monkeypatch):
     assert step.sparse_bwd and step.light == light
     route = f"{'light' if light else 'row-sparse'} D={D} L={L} {'captured' if capture else 'eager'}"
     for _ in range(2):
-        _fused_check(route, step, model, opt, light=light)
+        _fused_check_step(route, step, model, opt, light=light)
 
 
 # ---- the one-rank sharded step ----------------------------------------------------------------------------------------
@@ -215,6 +215,6 @@ def test_one_rank_sharded_step(dev, L, capture):
     for _ in range(3):
         sel = rng.choice(E, B, replace=False)
         batch = [torch.from_numpy(a.astype(np.int64)).to(dev) for a in (edges[sel, 0], edges[sel, 1], rng.integers(U, U + I, B))]
-        _check(f"one-rank sharded L={L} {'captured' if capture else 'eager'}", step, opt, U, I, csr, L, m.reg_weight,
+        _check_step(f"one-rank sharded L={L} {'captured' if capture else 'eager'}", step, opt, U, I, csr, L, m.reg_weight,
                lambda: torch.cat((m.user_embedding.weight, m.item_embedding.weight)).detach(),
                lambda: torch.cat((m.result_u, m.result_i)), batch)

@@ -16,18 +16,16 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import mhrec_host as mh  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
 
 
 def within(x, ref, dev, what, scale=None):
-    got, bound = mh.rel_dev(x, ref, scale), 4 * max(float(dev), ULP)
-    print(f"{what}: deviation {got:.3e}, reference's own {float(dev):.3e}, bound {bound:.3e}, ratio {got / bound:.3f}")
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    accept.within(what, x, ref, dev, accept.ULP24, scale=scale)
 
 
 def dev():
@@ -35,7 +33,7 @@ def dev():
 
 
 def t(x, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(x), dtype=dtype).to(dev())
+    return accept.to_dev(x, dtype, dev())
 
 
 @functools.lru_cache(maxsize=None)

@@ -3,8 +3,8 @@ the float64 restatements of tests/mvgae_host.py and the reference fixture of tes
 
 Tolerance of the nodes, measured and not chosen: the reference's own lines run in torch fp32 on the CPU on the same inputs
 (mvgae_host.conv_tail_torch / tail_torch), their deviation from the float64 restatement is taken relative to the tensor's
-largest magnitude, asserted below 1e-4, and the kernels are allowed 4 x max(that, 2^-24) (the project's rule: another
-summation order, the device's exp / log).  The four BPR parts are one tensor, the four KL parts another.
+largest magnitude, asserted below 1e-4, and the kernels are allowed 4 x max(that, 2^-24) (the project's rule,
+accept.within_measured: another summation order, the device's exp / log).  The four BPR parts are one tensor, the four KL parts another.
 The bound is per case and per tensor (each of the six gradient tables its own).  A sample's BPR coefficient follows its
 score difference 1 : 1, so the kernel evaluates the z rows, scores and coefficients of the 3B batch rows in double.  The
 batches are what a sampler hands out: a sample's negative is never its own positive (where there are two items), so no
@@ -21,11 +21,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mvgae_host as mh  # noqa: E402
+from accept import ULP24, same_bits, within, within_measured  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 D = mh.D
-ULP = 2.0 ** -24
 RW, RB = 4, 16
 NS = (1, RW, RW + 1, RB - 1, RB, RB + 1, 4 * RB + 3)
 
@@ -38,11 +38,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
 def _dirty(dev, N, B, fill):
     """Junk where the allocator will hand out the outputs, the z rows, the partials and the gradients."""
     for shape in ((8 * N, D), (12 * B, D), (8 * B,), (N + 16,), (9,)):
@@ -53,19 +48,6 @@ def _dirty(dev, N, B, fill):
 
 def _state(dev, step=0):
     return torch.tensor([step, step], dtype=torch.int64, device=dev)
-
-
-def _check(name, got, ref32, ref64, failures):
-    """got within 4 x max(the fp32 reference's own deviation, 2^-24) of the float64 restatement, relative to its largest
-    magnitude; the reference's deviation itself below 1e-4."""
-    scale = max(float(np.abs(np.asarray(ref64)).max()), 1e-300)
-    own = float(np.abs(np.asarray(ref32, dtype=np.float64) - ref64).max()) / scale
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max()) / scale
-    assert np.isfinite(np.asarray(ref32)).all() and own < 1e-4, f"{name}: the fp32 reference itself deviates by {own:.3e}"
-    bound = 4 * max(own, ULP)
-    print(f"{name}: deviation {err:.3e}, the fp32 reference's own {own:.3e}, bound {bound:.3e}")
-    if not (np.isfinite(np.asarray(got)).all() and err <= bound):
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
 
 
 # ---- (a) the conv epilogue -------------------------------------------------------------------------------------------------
@@ -100,14 +82,14 @@ def test_conv_epilogue(dev, N, training):
     assert not keep[N // 2].any() and ((s[N - 1] + bias) < 0).all()
     runs = [run_conv(dev, s, bias, gy, keep, training, fill) for fill in (float("nan"), 1e30)]
     for name, a, b in zip(("y", "gs", "gbias"), *runs):
-        assert _bits(a, b), f"{name}: two runs differ in their bits"
+        assert same_bits(a, b), f"{name}: two runs differ in their bits"
     y64 = mh.conv_tail(s, bias, keep, training)
     gs64, gb64 = mh.conv_tail_bwd(gy, s, bias, keep, training)
     y32, backward = mh.conv_tail_torch(s, bias, keep, training, torch.float32)
     gs32, gb32 = backward(gy)
     failures = []
     for name, got, r32, r64 in zip(("y", "gs", "gbias"), runs[0], (y32, gs32, gb32), (y64, gs64, gb64)):
-        _check(f"conv N={N} training={training} {name}", got, r32, r64, failures)
+        within_measured(f"conv N={N} training={training} {name}", got, r32, r64, ULP24, failures=failures)
     if training:
         assert not runs[0][0][N // 2].any() and not runs[0][1][N // 2].any()           # the fully dropped row
     assert (runs[0][0][N - 1][keep[N - 1] | (not training)] < 0).all()               # the negative-only row
@@ -177,21 +159,21 @@ def test_tail(dev, N, B, U, kind, training):
     assert (np.concatenate(tabs[1::2]) == 10.0).sum() >= 1 and (N < RW or max(t.max() for t in tabs[1::2]) > 10.0)
     runs = [run_tail(dev, tabs, users, pos, neg, eps, training, fill) for fill in (float("nan"), 1e30)]
     for k in ("total", "parts", "Pm"):
-        assert _bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
+        assert same_bits(runs[0][k], runs[1][k]), f"{k}: two runs differ in their bits"
     for k, (a, b) in enumerate(zip(runs[0]["grads"], runs[1]["grads"])):
-        assert _bits(a, b), f"gradient {k}: two runs differ in their bits"
+        assert same_bits(a, b), f"gradient {k}: two runs differ in their bits"
     f = mh.tail(tabs, users, pos, neg, 0.1, eps, training)
     g64 = mh.tail_bwd(tabs, users, pos, neg, 0.1, eps, training)
     total32, parts32, pm32, g32 = mh.tail_torch(tabs, users, pos, neg, 0.1, eps, training, torch.float32)
     failures = []
     tag = f"tail N={N} B={B} U={U} {kind} training={training}"
     got = runs[0]
-    _check(f"{tag} total", got["total"][0], total32, f["total"], failures)
-    _check(f"{tag} BPR parts", got["parts"][:4], parts32[:4], f["parts"][:4], failures)
-    _check(f"{tag} KL parts", got["parts"][4:], parts32[4:], f["parts"][4:], failures)
-    _check(f"{tag} Pm", got["Pm"], pm32, f["Pm"], failures)
+    within_measured(f"{tag} total", got["total"][0], total32, f["total"], ULP24, failures=failures)
+    within_measured(f"{tag} BPR parts", got["parts"][:4], parts32[:4], f["parts"][:4], ULP24, failures=failures)
+    within_measured(f"{tag} KL parts", got["parts"][4:], parts32[4:], f["parts"][4:], ULP24, failures=failures)
+    within_measured(f"{tag} Pm", got["Pm"], pm32, f["Pm"], ULP24, failures=failures)
     for name, a, r32, r64 in zip(GRADS, got["grads"], g32, g64):
-        _check(f"{tag} {name}", a, r32, r64, failures)
+        within_measured(f"{tag} {name}", a, r32, r64, ULP24, failures=failures)
     assert not failures, failures
 
 
@@ -200,7 +182,7 @@ def test_tail_scales_with_the_incoming_gradient(dev):
     a = run_tail(dev, tabs, users, pos, neg, eps, True, 0.0)
     b = run_tail(dev, tabs, users, pos, neg, eps, True, 0.0, gscale=-2.0)
     for x, y in zip(a["grads"], b["grads"]):
-        assert _bits(-2.0 * x, y)                # (a power of two: exact)
+        assert same_bits(-2.0 * x, y)                # (a power of two: exact)
 
 
 # ---- the device-drawn path -------------------------------------------------------------------------------------------------
@@ -211,21 +193,21 @@ def test_device_draws_are_a_function_of_seed_and_step(dev):
     b = run_tail(dev, tabs, users, pos, neg, None, True, float("nan"), state=_state(dev, 5), seed=99, return_eps=True)
     c = run_tail(dev, tabs, users, pos, neg, None, True, 0.0, state=_state(dev, 6), seed=99, return_eps=True)
     for k in ("total", "parts", "Pm", "eps"):
-        assert _bits(a[k], b[k]), k
-    assert all(_bits(x, y) for x, y in zip(a["grads"], b["grads"]))
-    assert not _bits(a["eps"], c["eps"]) and not _bits(a["total"], c["total"]) and _bits(a["Pm"], c["Pm"])
+        assert same_bits(a[k], b[k]), k
+    assert all(same_bits(x, y) for x, y in zip(a["grads"], b["grads"]))
+    assert not same_bits(a["eps"], c["eps"]) and not same_bits(a["total"], c["total"]) and same_bits(a["Pm"], c["Pm"])
     e = a["eps"]                                          # [4, 3, B, 64]
-    assert e.shape == (4, 3, 65, D) and _bits(e[:, 0, 0], e[:, 0, 1])
+    assert e.shape == (4, 3, 65, D) and same_bits(e[:, 0, 0], e[:, 0, 1])
     for q in np.nonzero(pos == pos[0])[0]:
-        assert _bits(e[:, 1, 0], e[:, 1, q])
+        assert same_bits(e[:, 1, 0], e[:, 1, q])
     # fed back as GIVEN tables, the returned rows reproduce loss and gradients bit for bit: the backward redrew the forward's
     given = np.zeros((4, 67, D), dtype=np.float32)
     for k, ids in enumerate((users, pos, neg)):
         given[:, ids] = e[:, k]
     d = run_tail(dev, tabs, users, pos, neg, given, True, 0.0, state=_state(dev, 1), seed=3)
     for k in ("total", "parts", "Pm"):
-        assert _bits(a[k], d[k]), k
-    assert all(_bits(x, y) for x, y in zip(a["grads"], d["grads"]))
+        assert same_bits(a[k], d[k]), k
+    assert all(same_bits(x, y) for x, y in zip(a["grads"], d["grads"]))
     # mean and variance of the noise over the distinct rows drawn, within five standard errors of 0 and 1
     rows = np.concatenate([e[:, k][:, np.unique(ids, return_index=True)[1]] for k, ids in enumerate((users, pos, neg))], axis=1)
     n = rows.size
@@ -239,11 +221,11 @@ def test_device_dropout_redrawn_by_the_backward(dev):
     b = run_conv(dev, s, bias, gy, None, True, float("nan"), state=_state(dev, 5), seed=99, salt=7)
     c = run_conv(dev, s, bias, gy, None, True, 0.0, state=_state(dev, 6), seed=99, salt=7)
     e = run_conv(dev, s, bias, gy, None, True, 0.0, state=_state(dev, 5), seed=99, salt=8)
-    assert all(_bits(x, y) for x, y in zip(a, b)) and not _bits(a[0], c[0]) and not _bits(a[0], e[0])
+    assert all(same_bits(x, y) for x, y in zip(a, b)) and not same_bits(a[0], c[0]) and not same_bits(a[0], e[0])
     implied = a[0] != 0                                                         # (no element of s + bias is 0)
     assert np.array_equal(implied, mh.keep_mask(99, 5, 7, N)), "the device's flags are not the restated counter RNG's"
     d = run_conv(dev, s, bias, gy, implied, True, 0.0, state=_state(dev, 1), seed=3, salt=0)
-    assert all(_bits(x, y) for x, y in zip(a, d))                               # given flags reproduce the drawn run
+    assert all(same_bits(x, y) for x, y in zip(a, d))                               # given flags reproduce the drawn run
     big = 4099
     s2, bias2, gy2, _ = conv_case(big, 6)
     frac = float((run_conv(dev, s2, bias2, gy2, None, True, 0.0, state=_state(dev, 2), seed=1234, salt=3)[0] != 0).mean())
@@ -260,13 +242,6 @@ def make_model(c, dev, n_layers=mh.N_LAYERS, fused=True):
     return m
 
 
-def _within(name, got, ref64, dev_stored, failures):
-    err, bound = mh.rel_dev(got, ref64), 4 * max(float(dev_stored), ULP)
-    print(f"{name}: deviation {err:.3e}, the reference's own {float(dev_stored):.3e}, bound {bound:.3e}")
-    if not err <= bound:
-        failures.append(f"{name}: {err:.3e} > {bound:.3e}")
-
-
 @pytest.mark.parametrize("fused", [True, False])
 def test_model_meets_the_reference_fixture(dev, fused):
     g, c = mh.load_fixture(GOLDEN), mh.small_case()
@@ -281,24 +256,24 @@ def test_model_meets_the_reference_fixture(dev, fused):
     loss.backward()
     torch.cuda.synchronize()
     failures = []
-    _within("loss", float(loss), out["loss"], g["dev_loss"], failures)
-    _within("result_embed", m.result_embed.cpu().numpy(), out["result"], g["dev_result"], failures)
+    within("loss", float(loss), out["loss"], g["dev_loss"], ULP24, failures=failures)
+    within("result_embed", m.result_embed.cpu().numpy(), out["result"], g["dev_result"], ULP24, failures=failures)
     parts = m.last["parts"].cpu().numpy()
     for k in range(8):
-        _within(f"part {k}", parts[k], out["parts"][k], g["dev_parts"][k], failures)
+        within(f"part {k}", parts[k], out["parts"][k], g["dev_parts"][k], ULP24, failures=failures)
     names = mh.with_grad(mh.N_LAYERS)
     params = dict(m.named_parameters())
     assert tuple(n for n in mh.NAMES if params[n].grad is not None) == names
     for k, n in enumerate(names):
-        _within(f"grad {n}", params[n].grad.cpu().numpy(), out["grads"][n], g["dev_grads"][k], failures)
+        within(f"grad {n}", params[n].grad.cpu().numpy(), out["grads"][n], g["dev_grads"][k], ULP24, failures=failures)
     # evaluation mode: the means are ranked, result_embed stays the last TRAINING forward's
     kept = m.result_embed.clone()
     m.eval()
     with torch.no_grad():
         ev = m.loss(*ids)
     ev64 = mh.step(weights, plain, c, c["users"], c["pos"], c["neg"], mh.KL_WEIGHT, mh.N_LAYERS, None, None, False)
-    _within("eval loss", float(ev), ev64["loss"], g["dev_eval_loss"], failures)
-    _within("eval result", m.last["pd_mu"].cpu().numpy(), ev64["result"], g["dev_eval_result"], failures)
+    within("eval loss", float(ev), ev64["loss"], g["dev_eval_loss"], ULP24, failures=failures)
+    within("eval result", m.last["pd_mu"].cpu().numpy(), ev64["result"], g["dev_eval_result"], ULP24, failures=failures)
     assert torch.equal(kept, m.result_embed)
     assert not failures, failures
 
@@ -317,17 +292,17 @@ def test_model_one_layer(dev, fused):
     loss.backward()
     torch.cuda.synchronize()
     failures = []
-    _within("loss", float(loss), out["loss"], g["dev_loss"], failures)
-    _within("result_embed", m.result_embed.cpu().numpy(), out["result"], g["dev_result"], failures)
+    within("loss", float(loss), out["loss"], g["dev_loss"], ULP24, failures=failures)
+    within("result_embed", m.result_embed.cpu().numpy(), out["result"], g["dev_result"], ULP24, failures=failures)
     parts = m.last["parts"].cpu().numpy()
     for k in range(8):
-        _within(f"part {k}", parts[k], out["parts"][k], g["dev_parts"][k], failures)
+        within(f"part {k}", parts[k], out["parts"][k], g["dev_parts"][k], ULP24, failures=failures)
     params = dict(m.named_parameters())
     names = mh.with_grad(1)
     assert tuple(n for n in mh.NAMES if params[n].grad is not None) == names
     worst = float(g["dev_grads"].max())
     for n in names:
-        _within(f"grad {n}", params[n].grad.cpu().numpy(), out["grads"][n], worst, failures)
+        within(f"grad {n}", params[n].grad.cpu().numpy(), out["grads"][n], worst, ULP24, failures=failures)
     assert not failures, failures
 
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from accept import lib as _lib, ptr as _ptr, same_bits, stream as _stream, up as _up  # noqa: E402
 from bpr_multi_host import Guarded, U24, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -26,23 +27,6 @@ def dev():
     from chaorec_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def _lib():
-    from chaorec_amd import _lib as L
-    return L.load()
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _up(dev, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _salted(rng, *shape):
@@ -61,9 +45,11 @@ def _leaky(x, g, slope):
 
 
 def _same_bits(got, want):
-    assert got.shape == want.shape
-    diff = bits(got) != bits(want)
-    assert not diff.any(), (int(diff.sum()), got[diff][:4], want[diff][:4])
+    """accept.same_bits on the float32 values of both, reporting the first elements that differ"""
+    if not same_bits(np.asarray(got, np.float32), np.asarray(want, np.float32)):
+        assert got.shape == want.shape
+        diff = bits(got) != bits(want)
+        raise AssertionError((int(diff.sum()), got[diff][:4], want[diff][:4]))
 
 
 CAT_CASES = [(1, 4, 4, True), (7, 4, 64, True), (5, 128, 4, True), (33, 64, 64, False), (32771, 192, 64, True)]

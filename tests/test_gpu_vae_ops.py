@@ -44,6 +44,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import vae_ops_host as vo  # noqa: E402
+from accept import ULP24, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -162,7 +163,7 @@ class Table:
         """A plain fp32 sum over the first axis of `addends` (fp32 inputs, so the fp64 sum's addends are exact): the forward
         error bound n 2^-24 sum |addends| per element."""
         a = np.abs(np.asarray(addends, dtype=np.float64))
-        err, bound = np.abs(np.asarray(got, dtype=np.float64) - ref64), a.shape[0] * 2.0 ** -24 * a.sum(0)
+        err, bound = np.abs(np.asarray(got, dtype=np.float64) - ref64), a.shape[0] * ULP24 * a.sum(0)
         ratio = float((err / bound).max())
         print(f"{self.op} {what}: largest |error| {err.max():.3e}, forward bound there {bound[np.argmax(err / bound)]:.3e}, ratio {ratio:.3f}")
         if not ratio <= self.worst[0]:
@@ -184,10 +185,6 @@ def backward(pairs):
     """sum <output, upstream gradient> . backward()"""
     sum((o * g).sum() for o, g in pairs).backward()
     torch.cuda.synchronize()
-
-
-def bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
 def with_junk(x, dev, rows=200):
@@ -237,13 +234,13 @@ def test_multvae_ops(dev, B, I):
     backward(((z, cu(gz, dev)), (kl, float(gkl)), (sq, float(gsq))))
     o64, g64, o32, g32 = both(vo.multvae_encode_fwd, dict(Wq_t=Wq_t, bq=bq, x=x, mask=mask, eps=eps), ("Wq_t", "bq"),
                               {"z": gz, "kl": gkl, "sumsq": gsq}, keep_prob=0.5, training=True)
-    assert bits_equal(host(eps_out), eps)
+    assert same_bits(host(eps_out), eps)
     for k, got in (("h", h), ("z", z), ("kl", kl[0]), ("sumsq", sq[0])):
         t.check(host(got), o64[k], o32[k], f"encode {k}")
     t.check(host(Wt.grad), g64["Wq_t"], g32["Wq_t"], "encode dWq_t")
     t.check(host(bt.grad), g64["bq"], g32["bq"], "encode dbq")
     want = np.float32(2.0) * (gsq * Wq_t[st["dead"]])                      # nobody holds it: 2 gsq w, bit for bit
-    assert bits_equal(host(Wt.grad)[st["dead"]], want), "the untouched item's encoder-gradient row is not exactly 2 gsq w"
+    assert same_bits(host(Wt.grad)[st["dead"]], want), "the untouched item's encoder-gradient row is not exactly 2 gsq w"
 
     # decode
     zin, Wp, bp = signed(rng, B, 64, decades=1.0), signed(rng, I, 64, scale=0.5), signed(rng, I, scale=0.5)
@@ -259,16 +256,16 @@ def test_multvae_ops(dev, B, I):
     # junk rows behind I change no bit
     junk = multvae_decode_run(ox, dev, st, zin, Wp, bp, gnll, gsq, junk=True)
     for k in out:
-        assert bits_equal(out[k], junk[k]), f"decode {k} moved with junk rows behind I"
+        assert same_bits(out[k], junk[k]), f"decode {k} moved with junk rows behind I"
     # a permuted batch: per-sample outputs move with it
     if B > 1:
         p = rng.permutation(B)
         perm = multvae_decode_run(ox, dev, st, zin[p], Wp, bp, gnll, gsq, users=users[p])
-        assert bits_equal(perm["lse"], out["lse"][p]) and bits_equal(perm["z"], out["z"][p]), "decode lse / dz do not move with the batch"
+        assert same_bits(perm["lse"], out["lse"][p]) and same_bits(perm["z"], out["z"][p]), "decode lse / dz do not move with the batch"
         s2, batch2 = on_device(st, dev, users[p])
         z2 = ox.multvae_encode(cu(Wq_t, dev), cu(bq, dev), s2, batch2, state, SEED, False, 0.5, None, None, cu(eps[p], dev))[0]
         z1 = ox.multvae_encode(cu(Wq_t, dev), cu(bq, dev), s, batch, state, SEED, False, 0.5, None, None, cu(eps, dev))[0]
-        assert bits_equal(host(z2), host(z1)[p]), "encode z does not move with the batch"
+        assert same_bits(host(z2), host(z1)[p]), "encode z does not move with the batch"
     t.done()
 
 
@@ -335,11 +332,11 @@ def test_macrid_ops(dev, B, I):
         t.check(out[k], g64[k], g32[k], f"mix d{k}")
     junk = macrid_mix_run(ox, dev, st, zh, items, cates, gce, junk=True)
     for k in out:
-        assert bits_equal(out[k], junk[k]), f"mix {k} moved with junk rows behind I"
+        assert same_bits(out[k], junk[k]), f"mix {k} moved with junk rows behind I"
     if B > 1:
         p = rng.permutation(B)
         perm = macrid_mix_run(ox, dev, st, zh[p], items, cates, gce, users=users[p])
-        assert bits_equal(perm["lse"], out["lse"][p]) and bits_equal(perm["zh"], out["zh"][p]), "mix lse / dzh do not move with the batch"
+        assert same_bits(perm["lse"], out["lse"][p]) and same_bits(perm["zh"], out["zh"][p]), "mix lse / dzh do not move with the batch"
     t.done()
 
 
@@ -394,12 +391,12 @@ def test_dualvae_ops(dev, B, N):
         t.check(out[k], g64[k], g32[k], f"dense d{k}")
     junk = dualvae_dense_run(ox, dev, st, z, zh, th, w, table, g1, g2, gN, junk=True)
     for k in out:
-        assert bits_equal(out[k], junk[k]), f"dense {k} moved with junk rows behind N"
+        assert same_bits(out[k], junk[k]), f"dense {k} moved with junk rows behind N"
     if B > 1:
         p = rng.permutation(B)
         perm = dualvae_dense_run(ox, dev, st, z[p], zh[p], th, w, table, g1[p], g2[p], gN[p], ids=ids[p])
         for k in ("sum_p", "xlog", "nei", "z", "zh"):
-            assert bits_equal(perm[k], out[k][p]), f"dense {k} does not move with the batch"
+            assert same_bits(perm[k], out[k][p]), f"dense {k} does not move with the batch"
     t.done()
 
 

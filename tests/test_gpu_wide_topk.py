@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from accept import to_dev
 from chaorec_amd import ops, ranking, utils
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ DEV = torch.device("cuda:0")
 
 
 def t(x, dtype=None):
-    return torch.as_tensor(np.asarray(x), dtype=dtype).to(DEV)
+    return to_dev(x, dtype, DEV)
 
 
 def bits(a):

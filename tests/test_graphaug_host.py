@@ -9,17 +9,16 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import graphaug_host as gh  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
 
 
 def within(x, ref, dev, what):
-    got, bound = gh.rel_dev(ref, x), 4 * max(float(dev), ULP)
-    print(f"{what}: deviation {got:.3e}, stored {float(dev):.3e}, bound {bound:.3e}")
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    """x is the float64 restatement, `ref` the reference's stored fp32 tensor: the stored tensor is held to the restatement."""
+    accept.within(what, ref, x, dev, accept.ULP24)
 
 
 @functools.lru_cache(maxsize=None)

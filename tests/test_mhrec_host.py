@@ -10,11 +10,12 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import mhrec_host as mh  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
+ULP = accept.ULP24
 
 
 @functools.lru_cache(maxsize=None)
@@ -25,8 +26,7 @@ def case():
 
 
 def close(x, ref, dev, what, scale=None):
-    got, bound = mh.rel_dev(x, ref, scale), 4 * max(float(dev), ULP)
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    accept.within(what, x, ref, dev, ULP, scale=scale)
 
 
 # ---- the restatement against the golden ----------------------------------------------------------------------------------------

@@ -13,18 +13,16 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accept  # noqa: E402
 import kernel_meta  # noqa: E402
 import mvgae_host as mh  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ULP = 2.0 ** -24
 
 
 def within(x, ref, dev, what):
-    got, bound = mh.rel_dev(x, ref), 4 * max(float(dev), ULP)
-    print(f"{what}: deviation {got:.3e}, reference's own {float(dev):.3e}, bound {bound:.3e}")
-    assert got <= bound, f"{what}: {got:.3e} > {bound:.3e}"
+    accept.within(what, x, ref, dev, accept.ULP24)
 
 
 def make_model(c, device="cpu", n_layers=mh.N_LAYERS):

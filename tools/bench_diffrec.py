@@ -25,7 +25,8 @@ import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from accept import ULP24, bound_of  # noqa: E402  (the tests' acceptance rule; numpy alone)
 from chaorec_amd import dataload, ops  # noqa: E402
 from chaorec_amd.Model.DiffRec import DiffRec  # noqa: E402
 from tools.bench_mvgae import compare  # noqa: E402
@@ -124,7 +125,7 @@ def main():
     scale = float(ref.abs().max())
     out["dev_collapsed"], out["dev_literal"] = float((col - ref).abs().max()) / scale, float((lit - ref).abs().max()) / scale
     out["dev_plain_fp32_cpu"] = float((own - ref).abs().max()) / scale
-    out["dev_bound"] = 4 * max(out["dev_plain_fp32_cpu"], 2.0 ** -24)
+    out["dev_bound"] = bound_of(out["dev_plain_fp32_cpu"], ULP24)
 
     for k, fast, slow in (("step", "step_fused", "step_plain_torch"), ("node", "node_fused", "node_plain_torch"),
                           ("node_vs_diffmm", "node_fused", "node_diffmm_e0"), ("eval", "eval_collapsed", "eval_literal")):
