@@ -305,8 +305,6 @@ static __global__ __launch_bounds__(256) void cf_keep_kernel(int64_t total, int 
   for (int jj = 0; jj < 64 && 64 * w + jj < n; ++jj) keep[(bh * n + i) * n + 64 * w + jj] = (uint8_t)((r >> jj) & 1ull);
 }
 
-static bool cf_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace chaorec
 
 using namespace chaorec;
@@ -332,7 +330,7 @@ extern "C" int chaorec_cfdiff_attn_fwd_f32(const float *q, const float *k, const
                                            float *out, float *lse, void *stream) {
   if (int rc = chaorec_cfdiff_check_shape(B, L)) return rc;
   if (!q || !k || !v || !out || !lse) return fail(CHAOREC_E_INVALID, "cfdiff_attn_fwd: NULL argument");
-  if (!cf_aligned16(q) || !cf_aligned16(k) || !cf_aligned16(v) || !cf_aligned16(out))
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out))
     return fail(CHAOREC_E_INVALID, "cfdiff_attn_fwd: q, k, v, out must be 16-byte aligned");
   if (int rc = cf_check_draws("cfdiff_attn_fwd", B, training, keep, state, b0)) return rc;
   const dim3 grid((unsigned)(4 * B)), block(CF_THREADS);
@@ -351,8 +349,8 @@ extern "C" int chaorec_cfdiff_attn_bwd_f32(const float *q, const float *k, const
                                            float *dv, float *rnorm, void *stream) {
   if (int rc = chaorec_cfdiff_check_shape(B, L)) return rc;
   if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !rnorm) return fail(CHAOREC_E_INVALID, "cfdiff_attn_bwd: NULL argument");
-  if (!cf_aligned16(q) || !cf_aligned16(k) || !cf_aligned16(v) || !cf_aligned16(out) || !cf_aligned16(dout) || !cf_aligned16(dq) ||
-      !cf_aligned16(dk) || !cf_aligned16(dv))
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) ||
+      !aligned16(dk) || !aligned16(dv))
     return fail(CHAOREC_E_INVALID, "cfdiff_attn_bwd: the [B, L, 16] operands must be 16-byte aligned");
   if (int rc = cf_check_draws("cfdiff_attn_bwd", B, training, keep, state, b0)) return rc;
   const dim3 grid((unsigned)(4 * B)), block(CF_THREADS);

@@ -30,6 +30,9 @@ inline int check_launch(const char *what) {
 
 constexpr int kWave = 64;  // CDNA wavefront width
 
+// is p 16-byte aligned (a base that float4 loads and stores walk from)?
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // Separately rounded fp32 product and sum: the compiler must not contract these into an FMA,
 // the reference's message()/scatter_add_ pair rounds twice (Model/LightGCN.py:40-43).
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }

@@ -5,15 +5,15 @@
 // (a) dm_rows_kernel      users -> x_in [B, ld] and the bit table of x0 (uint32 [B, ceil(I / 32)]), one wave per row
 // (b) dm_out_loss_kernel  d_out = c_b (h W_out^T + b_out - x0) + k (r F^T) on the f32 MFMA pipe, per-row partials of err^2
 // (c) dm_reduce_kernel    the row partials in item-tile order -> diff_rows, gc_rows, loss (double, one fixed order)
-#include "vae_common.h"
+//
+// The tile of (b) -- its placement, its K loop and the x0-error epilogue -- is out_tile.h's, shared with diffrec.hip.
+#include "out_tile.h"
 
 namespace chaorec {
 
 constexpr int DM_ROWS = 4;        // rows per workgroup of (a): one wave each
 constexpr int DM_CH = 2048;       // items per pass of a wave over its row: 64 words of the bit table, one per lane
-constexpr int DM_BM = 128, DM_BN = 128, DM_BK = 16, DM_PAD = 4;   // (b)'s tile: waves 2 x 2 of 64 x 64, as gemm.hip's <128, 128>
 constexpr int DM_D = 64;          // the embedding width of r and F
-constexpr int DM_SEG = 64;        // k per segment of the out-layer's chain (a multiple of DM_BK)
 constexpr int DM_BITS = 24;       // random bits of a uniform
 
 // (a) Row b of the batch is user u = users[b] (history empty for an id outside [0, U)).  Per pass of DM_CH items the wave
@@ -78,36 +78,19 @@ static __global__ __launch_bounds__(64 * DM_ROWS) void dm_rows_kernel(
   }
 }
 
-// (b) One 128 x 128 tile of out = h W_out^T per workgroup.  The K = H loop is gemm.hip's: operand tiles staged k-major in
-// LDS, double-buffered, the k-ascending fmaf chain of v_mfma_f32_32x32x2_f32 per element -- in segments of DM_SEG = 64 k: after
-// every fourth tile the chain's value is added to a running sum and the chain restarts from zero (segments in ascending order,
-// the same bits every run).  One chain over K = 1000 rounds a thousand times at the magnitude of its growing partial sum and
-// deviated 4 to 5 times as much as torch's blocked fp32 sum (measured against float64 at H = 1000: 1.0 to 1.3e-6 of the
-// largest |d_out|, torch 2.5 to 3e-7); the running sum lives in the accumulators the second chain needs anyway.
-// Epilogue, in registers:
-//   err = (acc + b_out[i]) - x0[b, i]      (x0 from the bit table: the 32 columns of a lane group are one word)
-//   the tile's share of sum_i err^2 per row: columns in a fixed butterfly order, then the two column halves in order
-//   acc = c_b err, then 64 more k-steps over (r, F) into a SECOND set of accumulators, acc2 = r_b . F_i from zero,
-// and c_b err + k acc2 is stored once.  (Continuing the chain on c_b err instead would save 64 registers and round 64 times at
-// the magnitude of c_b err, which at small B I is a thousand times that of the chain's terms: measured, 8 ulp of d_out.)
-// Workgroups are dealt to the 8 XCDs round-robin: block id -> (id % 8, id / 8), and the workgroups of one XCD walk the row
-// tiles of one column tile before the next, so a slice of W_out is read into one L2 and h, 4 MB, stays in all of them.
+// (b) One tile of out = h W_out^T per workgroup: out_tile.h's placement, its segmented K = H loop and its x0-error epilogue,
+// which leaves acc = c_b err and the row partials.  Then 64 more k-steps over (r, F) into a second set of accumulators,
+// acc2 = r_b . F_i from zero and unsegmented (out_tile.h gives the measured reason), and c_b err + k acc2 is stored once.
 template <class = void>
 static __global__ __launch_bounds__(256) void dm_out_loss_kernel(
     const float *__restrict__ h, int64_t ldh, const float *__restrict__ W, int64_t ldw, const float *__restrict__ bias,
     const uint32_t *__restrict__ bits, int64_t nwords, const float *__restrict__ r, const float *__restrict__ F,
     const float *__restrict__ c_row, float kf, int64_t B, int64_t I, int64_t H, int64_t MT, int64_t NT,
     float *__restrict__ d_out, int64_t ldd, float *__restrict__ part) {
-  __shared__ float As[2][DM_BK][DM_BM + DM_PAD];
-  __shared__ float Bs[2][DM_BK][DM_BN + DM_PAD];
-  __shared__ float Ps[2][DM_BM];
-  const int64_t slot = (int64_t)blockIdx.x >> 3;
-  const int64_t nt = (slot / MT) * 8 + ((int64_t)blockIdx.x & 7), mt = slot % MT;
-  if (nt >= NT) return;           // the whole workgroup: no barrier has been reached
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int rr = lane & 31, hh = lane >> 5;
-  const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 64;
-  const int64_t m0 = mt * DM_BM, n0 = nt * DM_BN;
+  __shared__ OtStage As, Bs;
+  __shared__ float Ps[2][OT_BM];
+  const OutTile tp = out_tile_place(MT, NT);
+  if (!tp.live) return;           // the whole workgroup: no barrier has been reached
 
   f32x16 acc[2][2], acc2[2][2];
 #pragma unroll
@@ -115,126 +98,14 @@ static __global__ __launch_bounds__(256) void dm_out_loss_kernel(
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = acc2[i][j] = vae_zero();
 
-  // acc += A[m0 .., 0 .. K) . Bm[n0 .., 0 .. K)^T; both operands [rows][k], K a multiple of 4, rows 16-byte aligned
-  // sum != nullptr: every DM_SEG k, sum += acc and acc = 0 (the caller adds the last, partial segment)
-  auto run = [&](f32x16 (&acc)[2][2], f32x16 (*sum)[2], const float *__restrict__ A, int64_t lda, const float *__restrict__ Bm, int64_t ldb,
-                 int64_t K) {
-    float4 ra[2], rb[2];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int v = t + p * 256, row = v >> 2, k4 = (v & 3) * 4;
-        const int64_t gk = k0 + k4;
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-        if (m0 + row < B && gk < K) x = *reinterpret_cast<const float4 *>(A + (m0 + row) * lda + gk);
-        if (n0 + row < I && gk < K) y = *reinterpret_cast<const float4 *>(Bm + (n0 + row) * ldb + gk);
-        ra[p] = x;
-        rb[p] = y;
-      }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int v = t + p * 256, row = v >> 2, k4 = (v & 3) * 4;
-        As[buf][k4 + 0][row] = ra[p].x;
-        As[buf][k4 + 1][row] = ra[p].y;
-        As[buf][k4 + 2][row] = ra[p].z;
-        As[buf][k4 + 3][row] = ra[p].w;
-        Bs[buf][k4 + 0][row] = rb[p].x;
-        Bs[buf][k4 + 1][row] = rb[p].y;
-        Bs[buf][k4 + 2][row] = rb[p].z;
-        Bs[buf][k4 + 3][row] = rb[p].w;
-      }
-    };
-    int buf = 0;
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    for (int64_t k0 = 0; k0 < K; k0 += DM_BK) {
-      const bool more = k0 + DM_BK < K;
-      if (more) fetch(k0 + DM_BK);
-      float af[DM_BK / 2][2], bf[DM_BK / 2][2];
-#pragma unroll
-      for (int s = 0; s < DM_BK / 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          af[s][i] = As[buf][2 * s + hh][wrow + 32 * i + rr];
-          bf[s][i] = Bs[buf][2 * s + hh][wcol + 32 * i + rr];
-        }
-#pragma unroll
-      for (int s = 0; s < DM_BK / 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s][i], bf[s][j], acc[i][j], 0, 0, 0);
-      if (sum && ((k0 + DM_BK) % DM_SEG) == 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            sum[i][j] = sum[i][j] + acc[i][j];
-            acc[i][j] = vae_zero();
-          }
-      }
-      if (more) stash(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
-  };
-
-  run(acc, acc2, h, ldh, W, ldw, H);
+  out_tile_run<true>(acc, tp, As, Bs, h, ldh, W, ldw, B, I, H);
+  out_tile_x0_err(acc, tp, Ps, bias, bits, nwords, c_row, B, I, NT, part);
+  out_tile_run<false>(acc2, tp, As, Bs, r, DM_D, F, DM_D, B, I, DM_D);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = acc2[i][j] + acc[i][j];
-
-  // err, its squares per row, c_b err
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int row = wrow + 32 * i + vae_row(reg, hh);
-      const int64_t gm = m0 + row;
-      const float cb = gm < B ? c_row[gm] : 0.f;
-      float sq = 0.f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t g0 = n0 + wcol + 32 * j, gn = g0 + rr;
-        float err = 0.f;
-        if (gm < B && gn < I) {
-          const uint32_t word = bits[gm * nwords + (g0 >> 5)];
-          const float x0 = ((word >> rr) & 1u) ? 1.f : 0.f;
-          err = (acc[i][j][reg] + bias[gn]) - x0;
-        }
-        sq = sq + err * err;
-        acc[i][j][reg] = cb * err;
-      }
-#pragma unroll
-      for (int off = 1; off < 32; off <<= 1) sq = sq + __shfl_xor(sq, off, 64);   // within the 32 lanes that hold the row
-      if (rr == 0) Ps[wave & 1][row] = sq;
-    }
-  }
-  __syncthreads();
-  if (t < DM_BM && m0 + t < B) part[(m0 + t) * NT + nt] = Ps[0][t] + Ps[1][t];
-
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc2[i][j] = vae_zero();
-  run(acc2, nullptr, r, DM_D, F, DM_D, DM_D);
-
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t gn = n0 + wcol + 32 * j + rr;
-      if (gn >= ldd) continue;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int64_t gm = m0 + wrow + 32 * i + vae_row(reg, hh);
-        if (gm < B) d_out[gm * ldd + gn] = gn < I ? acc[i][j][reg] + kf * acc2[i][j][reg] : 0.f;
-      }
-    }
+    for (int j = 0; j < 2; ++j) acc[i][j] = acc[i][j] + kf * acc2[i][j];
+  out_tile_store_padded(acc, tp, B, I, d_out, ldd);
 }
 
 // (c) diff_rows[b] = w_b / I sum_tiles part[b, .] (tiles ascending, in double), gc_rows[b] = mean_d r[b, d]^2, loss =
@@ -270,7 +141,20 @@ static __global__ __launch_bounds__(256) void dm_reduce_kernel(const float *__re
   if (threadIdx.x == 0) loss[0] = (float)(red[0][0] / (double)B + (double)e_loss * (red[1][0] / (double)B));
 }
 
-static bool dm_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// Both rows exports: the checks and the launch of (a).  plain as the kernel takes it (2: chaorec_diffmm_rows_noised_f32).
+static int dm_rows_launch(const char *name, const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col, int64_t I,
+                          int64_t ld, const float *a_row, const float *s_row, const float *noise, const uint8_t *keep, uint64_t seed,
+                          uint64_t step, uint32_t salt, int plain, float *x, uint32_t *bits, void *stream) {
+  if (!users || !rowptr || !col || !x || !bits) return fail(CHAOREC_E_INVALID, "%s: NULL argument", name);
+  if (plain != 1 && (!a_row || !s_row)) return fail(CHAOREC_E_INVALID, "%s: a_row / s_row missing", name);
+  if (B < 0 || U < 0 || I <= 0 || I > ((int64_t)1 << 31) - 256) return fail(CHAOREC_E_INVALID, "%s: B=%lld I=%lld", name, (long long)B, (long long)I);
+  if (ld != (I + 3) / 4 * 4 || !aligned16(x))
+    return fail(CHAOREC_E_INVALID, "%s: ld=%lld must be I rounded up to 4, the rows 16-byte aligned", name, (long long)ld);
+  if (B == 0) return CHAOREC_OK;
+  hipLaunchKernelGGL(dm_rows_kernel<>, dim3((unsigned)((B + DM_ROWS - 1) / DM_ROWS)), dim3(64 * DM_ROWS), 0, (hipStream_t)stream, users,
+                     B, U, rowptr, col, I, ld, a_row, s_row, noise, keep, seed, step, (uint64_t)salt, plain, x, bits, (I + 31) / 32);
+  return check_launch("dm_rows_kernel");
+}
 
 }  // namespace chaorec
 
@@ -286,9 +170,9 @@ extern "C" int chaorec_diffmm_check_shape(int64_t B, int64_t I, int64_t H, int32
 
 extern "C" int chaorec_diffmm_tiles(int32_t *bm, int32_t *bn, int32_t *bk) {
   if (!bm || !bn || !bk) return fail(CHAOREC_E_INVALID, "diffmm_tiles: NULL argument");
-  *bm = DM_BM;
-  *bn = DM_BN;
-  *bk = DM_BK;
+  *bm = OT_BM;
+  *bn = OT_BN;
+  *bk = OT_BK;
   return CHAOREC_OK;
 }
 
@@ -298,26 +182,13 @@ extern "C" int chaorec_diffmm_rows_f32(const int64_t *users, int64_t B, int64_t 
                                        int64_t I, int64_t ld, const float *a_row, const float *s_row, const float *noise,
                                        const uint8_t *keep, uint64_t seed, uint64_t step, uint32_t salt, int32_t plain,
                                        float *x_in, uint32_t *bits, void *stream) {
-  if (!users || !rowptr || !col || !x_in || !bits) return fail(CHAOREC_E_INVALID, "diffmm_rows: NULL argument");
-  if (!plain && (!a_row || !s_row)) return fail(CHAOREC_E_INVALID, "diffmm_rows: a_row / s_row missing");
-  if (B < 0 || U < 0 || I <= 0 || I > ((int64_t)1 << 31) - 256) return fail(CHAOREC_E_INVALID, "diffmm_rows: B=%lld I=%lld", (long long)B, (long long)I);
-  if (ld != (I + 3) / 4 * 4 || !dm_aligned16(x_in)) return fail(CHAOREC_E_INVALID, "diffmm_rows: ld=%lld must be I rounded up to 4, x_in 16-byte aligned", (long long)ld);
-  if (B == 0) return CHAOREC_OK;
-  hipLaunchKernelGGL(dm_rows_kernel<>, dim3((unsigned)((B + DM_ROWS - 1) / DM_ROWS)), dim3(64 * DM_ROWS), 0, (hipStream_t)stream, users,
-                     B, U, rowptr, col, I, ld, a_row, s_row, noise, keep, seed, step, (uint64_t)salt, plain ? 1 : 0, x_in, bits, (I + 31) / 32);
-  return check_launch("dm_rows_kernel");
+  return dm_rows_launch("diffmm_rows", users, B, U, rowptr, col, I, ld, a_row, s_row, noise, keep, seed, step, salt, plain ? 1 : 0, x_in, bits, stream);
 }
 
 extern "C" int chaorec_diffmm_rows_noised_f32(const int64_t *users, int64_t B, int64_t U, const int64_t *rowptr, const int32_t *col,
                                               int64_t I, int64_t ld, const float *a_row, const float *s_row, const float *noise,
                                               uint64_t seed, uint64_t step, uint32_t salt, float *x_t, uint32_t *bits, void *stream) {
-  if (!users || !rowptr || !col || !x_t || !bits || !a_row || !s_row) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: NULL argument");
-  if (B < 0 || U < 0 || I <= 0 || I > ((int64_t)1 << 31) - 256) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: B=%lld I=%lld", (long long)B, (long long)I);
-  if (ld != (I + 3) / 4 * 4 || !dm_aligned16(x_t)) return fail(CHAOREC_E_INVALID, "diffmm_rows_noised: ld=%lld must be I rounded up to 4, x_t 16-byte aligned", (long long)ld);
-  if (B == 0) return CHAOREC_OK;
-  hipLaunchKernelGGL(dm_rows_kernel<>, dim3((unsigned)((B + DM_ROWS - 1) / DM_ROWS)), dim3(64 * DM_ROWS), 0, (hipStream_t)stream, users,
-                     B, U, rowptr, col, I, ld, a_row, s_row, noise, (const uint8_t *)nullptr, seed, step, (uint64_t)salt, 2, x_t, bits, (I + 31) / 32);
-  return check_launch("dm_rows_kernel");
+  return dm_rows_launch("diffmm_rows_noised", users, B, U, rowptr, col, I, ld, a_row, s_row, noise, nullptr, seed, step, salt, 2, x_t, bits, stream);
 }
 
 extern "C" int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const float *W_out, int64_t ldw, const float *b_out,
@@ -328,16 +199,15 @@ extern "C" int chaorec_diffmm_out_loss_f32(const float *h, int64_t ldh, const fl
   if (!h || !W_out || !b_out || !bits || !r || !F || !w || !c_row || !d_out || !part || !diff_rows || !gc_rows || !loss)
     return fail(CHAOREC_E_INVALID, "diffmm_out_loss: NULL argument");
   if (int rc = chaorec_diffmm_check_shape(B, I, H, DM_D)) return rc;
-  if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3) || ldd < I || !dm_aligned16(h) || !dm_aligned16(W_out) || !dm_aligned16(r) || !dm_aligned16(F))
+  if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3) || ldd < I || !aligned16(h) || !aligned16(W_out) || !aligned16(r) || !aligned16(F))
     return fail(CHAOREC_E_INVALID, "diffmm_out_loss: h, W_out, r, F must be 16-byte aligned with row strides that are multiples of 4");
-  const int64_t MT = (B + DM_BM - 1) / DM_BM, NT = (I + DM_BN - 1) / DM_BN;
-  if (ldd > NT * DM_BN) return fail(CHAOREC_E_INVALID, "diffmm_out_loss: ldd=%lld past the last item tile", (long long)ldd);
-  const int64_t blocks = (NT + 7) / 8 * MT * 8;
-  if (blocks > 0x7fffffff) return fail(CHAOREC_E_INVALID, "diffmm_out_loss: %lld workgroups", (long long)blocks);
+  const OutGrid g = out_tile_grid(B, I);
+  if (ldd > g.NT * OT_BN) return fail(CHAOREC_E_INVALID, "diffmm_out_loss: ldd=%lld past the last item tile", (long long)ldd);
+  if (!g.blocks) return fail(CHAOREC_E_INVALID, "diffmm_out_loss: too many workgroups at B=%lld I=%lld", (long long)B, (long long)I);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(dm_out_loss_kernel<>, dim3((unsigned)blocks), dim3(256), 0, st, h, ldh, W_out, ldw, b_out, bits, (I + 31) / 32, r, F,
-                     c_row, kf, B, I, H, MT, NT, d_out, ldd, part);
+  hipLaunchKernelGGL(dm_out_loss_kernel<>, dim3((unsigned)g.blocks), dim3(256), 0, st, h, ldh, W_out, ldw, b_out, bits, (I + 31) / 32, r, F,
+                     c_row, kf, B, I, H, g.MT, g.NT, d_out, ldd, part);
   if (int rc = check_launch("dm_out_loss_kernel")) return rc;
-  hipLaunchKernelGGL(dm_reduce_kernel<>, dim3(1), dim3(256), 0, st, part, NT, r, w, B, I, e_loss, diff_rows, gc_rows, loss);
+  hipLaunchKernelGGL(dm_reduce_kernel<>, dim3(1), dim3(256), 0, st, part, g.NT, r, w, B, I, e_loss, diff_rows, gc_rows, loss);
   return check_launch("dm_reduce_kernel");
 }

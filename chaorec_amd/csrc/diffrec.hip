@@ -6,16 +6,12 @@
 // (b) dr_reduce_kernel          the row partials in item-tile order -> reloss_rows (double), loss = mean_b reloss_b / pt_b
 // (c) dr_tile_kernel<DR_CHAIN>  p_next = c1 (z G^T + g0) + c2 p,  z_next = tanh(p_next + e_next)
 //
-// One tile loop serves both: acc = A[m0 .., 0 .. K) . Bm[n0 .., 0 .. K)^T on v_mfma_f32_32x32x2_f32, both operands
-// [rows][k], staged k-major in LDS and double-buffered, 128 x 128 x 16 per workgroup (waves 2 x 2 of 64 x 64).  The k chain
-// of an element is cut into segments of DR_SEG = 64 whose values are added in ascending order, as csrc/diffmm.hip's output
-// layer does and for its measured reason (one chain over K = 1000 deviated 4 to 5 times as much as a blocked sum).
-#include "vae_common.h"
+// One tile serves both: out_tile.h's placement of the workgroups and its K loop, the chain of an element cut into segments
+// of 64 k; (a)'s epilogue and padded store are out_tile.h's as well, shared with diffmm.hip's output layer.
+#include "out_tile.h"
 
 namespace chaorec {
 
-constexpr int DR_BM = 128, DR_BN = 128, DR_BK = 16, DR_PAD = 4;
-constexpr int DR_SEG = 64;        // k per segment of a chain (a multiple of DR_BK)
 constexpr int DR_LOSS = 0, DR_CHAIN = 1;
 
 // What the two epilogues read and write beside the product.  LOSS: bias = b_out [N], bits, c_row [M], out0 = d_out [M, ldo]
@@ -35,137 +31,25 @@ struct DrEpilogue {
   int64_t ldo;
 };
 
-// Workgroups are dealt to the 8 XCDs round-robin: block id -> (id % 8, id / 8), and the workgroups of one XCD walk the row
-// tiles of one column tile before the next, so a slice of Bm is read into one L2 and A stays in all of them.
 template <int EPI>
 static __global__ __launch_bounds__(256) void dr_tile_kernel(const float *__restrict__ A, int64_t lda, const float *__restrict__ Bm,
                                                              int64_t ldb, int64_t M, int64_t N, int64_t K, int64_t MT, int64_t NT,
                                                              DrEpilogue ep) {
-  __shared__ float As[2][DR_BK][DR_BM + DR_PAD];
-  __shared__ float Bs[2][DR_BK][DR_BN + DR_PAD];
-  __shared__ float Ps[2][DR_BM];
-  const int64_t slot = (int64_t)blockIdx.x >> 3;
-  const int64_t nt = (slot / MT) * 8 + ((int64_t)blockIdx.x & 7), mt = slot % MT;
-  if (nt >= NT) return;           // the whole workgroup: no barrier has been reached
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int rr = lane & 31, hh = lane >> 5;
-  const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 64;
-  const int64_t m0 = mt * DR_BM, n0 = nt * DR_BN;
+  __shared__ OtStage As, Bs;
+  const OutTile tp = out_tile_place(MT, NT);
+  if (!tp.live) return;           // the whole workgroup: no barrier has been reached
 
-  f32x16 acc[2][2], sum[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = sum[i][j] = vae_zero();
-
-  float4 ra[2], rb[2];
-  auto fetch = [&](int64_t k0) {      // K is a multiple of 4 and rows are 16-byte aligned: a float4 is inside or outside
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int v = t + p * 256, row = v >> 2, k4 = (v & 3) * 4;
-      const int64_t gk = k0 + k4;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-      if (m0 + row < M && gk < K) x = *reinterpret_cast<const float4 *>(A + (m0 + row) * lda + gk);
-      if (n0 + row < N && gk < K) y = *reinterpret_cast<const float4 *>(Bm + (n0 + row) * ldb + gk);
-      ra[p] = x;
-      rb[p] = y;
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int v = t + p * 256, row = v >> 2, k4 = (v & 3) * 4;
-      As[buf][k4 + 0][row] = ra[p].x;
-      As[buf][k4 + 1][row] = ra[p].y;
-      As[buf][k4 + 2][row] = ra[p].z;
-      As[buf][k4 + 3][row] = ra[p].w;
-      Bs[buf][k4 + 0][row] = rb[p].x;
-      Bs[buf][k4 + 1][row] = rb[p].y;
-      Bs[buf][k4 + 2][row] = rb[p].z;
-      Bs[buf][k4 + 3][row] = rb[p].w;
-    }
-  };
-  int buf = 0;
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int64_t k0 = 0; k0 < K; k0 += DR_BK) {
-    const bool more = k0 + DR_BK < K;
-    if (more) fetch(k0 + DR_BK);
-    float af[DR_BK / 2][2], bf[DR_BK / 2][2];
-#pragma unroll
-    for (int s = 0; s < DR_BK / 2; ++s)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        af[s][i] = As[buf][2 * s + hh][wrow + 32 * i + rr];
-        bf[s][i] = Bs[buf][2 * s + hh][wcol + 32 * i + rr];
-      }
-#pragma unroll
-    for (int s = 0; s < DR_BK / 2; ++s)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s][i], bf[s][j], acc[i][j], 0, 0, 0);
-    if (((k0 + DR_BK) % DR_SEG) == 0) {     // a segment is complete: into the running sum, the chain restarts from zero
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          sum[i][j] = sum[i][j] + acc[i][j];
-          acc[i][j] = vae_zero();
-        }
-    }
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = sum[i][j] + acc[i][j];      // the last, partial segment (zero when K % 64 == 0)
+    for (int j = 0; j < 2; ++j) acc[i][j] = vae_zero();
+  out_tile_run<true>(acc, tp, As, Bs, A, lda, Bm, ldb, M, N, K);
 
   if constexpr (EPI == DR_LOSS) {
-    // err = (acc + b_out[i]) - x0[b, i] (x0 from the bit table: the 32 columns of a lane group are one word), the tile's share
-    // of sum_i err^2 per row: columns in a fixed butterfly order, then the two column halves in order; acc = c_b err
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = wrow + 32 * i + vae_row(reg, hh);
-        const int64_t gm = m0 + row;
-        const float cb = gm < M ? ep.c_row[gm] : 0.f;
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int64_t g0 = n0 + wcol + 32 * j, gn = g0 + rr;
-          float err = 0.f;
-          if (gm < M && gn < N) {
-            const uint32_t word = ep.bits[gm * ep.nwords + (g0 >> 5)];
-            const float x0 = ((word >> rr) & 1u) ? 1.f : 0.f;
-            err = (acc[i][j][reg] + ep.bias[gn]) - x0;
-          }
-          sq = sq + err * err;
-          acc[i][j][reg] = cb * err;
-        }
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) sq = sq + __shfl_xor(sq, off, 64);   // within the 32 lanes that hold the row
-        if (rr == 0) Ps[wave & 1][row] = sq;
-      }
-    }
-    __syncthreads();
-    if (t < DR_BM && m0 + t < M) ep.part[(m0 + t) * NT + nt] = Ps[0][t] + Ps[1][t];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t gn = n0 + wcol + 32 * j + rr;
-        if (gn >= ep.ldo) continue;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int64_t gm = m0 + wrow + 32 * i + vae_row(reg, hh);
-          if (gm < M) ep.out0[gm * ep.ldo + gn] = gn < N ? acc[i][j][reg] : 0.f;
-        }
-      }
+    __shared__ float Ps[2][OT_BM];      // the row partials: the chain kernel does not carry them
+    out_tile_x0_err(acc, tp, Ps, ep.bias, ep.bits, ep.nwords, ep.c_row, M, N, NT, ep.part);
+    out_tile_store_padded(acc, tp, M, N, ep.out0, ep.ldo);
   } else {
     // p_next = fl(fl(c1 fl(acc + g0)) + fl(c2 p)), z_next = fl(tanh(fl(p_next + e_next))), the tanh itself evaluated in double:
     // B N evaluations against the tile's 2 B N K flops.  Every element has one owner.
@@ -173,12 +57,12 @@ static __global__ __launch_bounds__(256) void dr_tile_kernel(const float *__rest
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int64_t gn = n0 + wcol + 32 * j + rr;
+        const int64_t gn = tp.n0 + tp.wcol + 32 * j + tp.rr;
         if (gn >= N) continue;
         const float g0 = ep.bias[gn], en = ep.e[gn];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          const int64_t gm = m0 + wrow + 32 * i + vae_row(reg, hh);
+          const int64_t gm = tp.m0 + tp.wrow + 32 * i + vae_row(reg, tp.hh);
           if (gm >= M) continue;
           const float pn = ep.c1 * (acc[i][j][reg] + g0) + ep.c2 * ep.prev[gm * ep.ldp + gn];
           ep.out0[gm * ep.ldo + gn] = pn;
@@ -212,16 +96,6 @@ static __global__ __launch_bounds__(256) void dr_reduce_kernel(const float *__re
   if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
 }
 
-static bool dr_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// the launch grid of a tile kernel over [M, N]; 0: too many workgroups
-static int64_t dr_blocks(int64_t M, int64_t N, int64_t *MT, int64_t *NT) {
-  *MT = (M + DR_BM - 1) / DR_BM;
-  *NT = (N + DR_BN - 1) / DR_BN;
-  const int64_t blocks = (*NT + 7) / 8 * *MT * 8;
-  return blocks > 0x7fffffff ? 0 : blocks;
-}
-
 }  // namespace chaorec
 
 using namespace chaorec;
@@ -235,9 +109,9 @@ extern "C" int chaorec_diffrec_check_shape(int64_t B, int64_t I, int64_t H) {
 
 extern "C" int chaorec_diffrec_tiles(int32_t *bm, int32_t *bn, int32_t *bk) {
   if (!bm || !bn || !bk) return fail(CHAOREC_E_INVALID, "diffrec_tiles: NULL argument");
-  *bm = DR_BM;
-  *bn = DR_BN;
-  *bk = DR_BK;
+  *bm = OT_BM;
+  *bn = OT_BN;
+  *bk = OT_BK;
   return CHAOREC_OK;
 }
 
@@ -248,12 +122,11 @@ extern "C" int chaorec_diffrec_out_loss_f32(const float *h, int64_t ldh, const f
   if (!h || !W_out || !b_out || !bits || !w || !pt || !c_row || !d_out || !part || !reloss_rows || !loss)
     return fail(CHAOREC_E_INVALID, "diffrec_out_loss: NULL argument");
   if (int rc = chaorec_diffrec_check_shape(B, I, H)) return rc;
-  if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3) || ldd < I || !dr_aligned16(h) || !dr_aligned16(W_out))
+  if (ldh < H || ldw < H || (ldh & 3) || (ldw & 3) || ldd < I || !aligned16(h) || !aligned16(W_out))
     return fail(CHAOREC_E_INVALID, "diffrec_out_loss: h, W_out must be 16-byte aligned with row strides that are multiples of 4, ldd >= I");
-  int64_t MT, NT;
-  const int64_t blocks = dr_blocks(B, I, &MT, &NT);
-  if (!blocks) return fail(CHAOREC_E_INVALID, "diffrec_out_loss: too many workgroups at B=%lld I=%lld", (long long)B, (long long)I);
-  if (ldd > NT * DR_BN) return fail(CHAOREC_E_INVALID, "diffrec_out_loss: ldd=%lld past the last item tile", (long long)ldd);
+  const OutGrid g = out_tile_grid(B, I);
+  if (!g.blocks) return fail(CHAOREC_E_INVALID, "diffrec_out_loss: too many workgroups at B=%lld I=%lld", (long long)B, (long long)I);
+  if (ldd > g.NT * OT_BN) return fail(CHAOREC_E_INVALID, "diffrec_out_loss: ldd=%lld past the last item tile", (long long)ldd);
   DrEpilogue ep = {};
   ep.bias = b_out;
   ep.bits = bits;
@@ -263,9 +136,9 @@ extern "C" int chaorec_diffrec_out_loss_f32(const float *h, int64_t ldh, const f
   ep.out0 = d_out;
   ep.ldo = ldd;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(dr_tile_kernel<DR_LOSS>, dim3((unsigned)blocks), dim3(256), 0, st, h, ldh, W_out, ldw, B, I, H, MT, NT, ep);
+  hipLaunchKernelGGL(dr_tile_kernel<DR_LOSS>, dim3((unsigned)g.blocks), dim3(256), 0, st, h, ldh, W_out, ldw, B, I, H, g.MT, g.NT, ep);
   if (int rc = check_launch("dr_tile_kernel<loss>")) return rc;
-  hipLaunchKernelGGL(dr_reduce_kernel<>, dim3(1), dim3(256), 0, st, part, NT, w, pt, B, I, reloss_rows, loss);
+  hipLaunchKernelGGL(dr_reduce_kernel<>, dim3(1), dim3(256), 0, st, part, g.NT, w, pt, B, I, reloss_rows, loss);
   return check_launch("dr_reduce_kernel");
 }
 
@@ -274,13 +147,12 @@ extern "C" int chaorec_diffrec_chain_f32(const float *z, int64_t ldz, const floa
                                          float *p_next, float *z_next, int64_t ldo, void *stream) {
   if (!z || !G || !g0 || !p || !e_next || !p_next || !z_next) return fail(CHAOREC_E_INVALID, "diffrec_chain: NULL argument");
   if (int rc = chaorec_diffrec_check_shape(B, N, K)) return rc;
-  if (ldz < K || ldg < K || (ldz & 3) || (ldg & 3) || ldp < N || ldo < N || !dr_aligned16(z) || !dr_aligned16(G))
+  if (ldz < K || ldg < K || (ldz & 3) || (ldg & 3) || ldp < N || ldo < N || !aligned16(z) || !aligned16(G))
     return fail(CHAOREC_E_INVALID, "diffrec_chain: z, G must be 16-byte aligned with row strides that are multiples of 4, ldp, ldo >= N");
   if (p_next == z_next || p_next == z || z_next == z || z_next == p)
     return fail(CHAOREC_E_INVALID, "diffrec_chain: the outputs must not alias each other or an operand another workgroup reads");
-  int64_t MT, NT;
-  const int64_t blocks = dr_blocks(B, N, &MT, &NT);
-  if (!blocks) return fail(CHAOREC_E_INVALID, "diffrec_chain: too many workgroups at B=%lld N=%lld", (long long)B, (long long)N);
+  const OutGrid g = out_tile_grid(B, N);
+  if (!g.blocks) return fail(CHAOREC_E_INVALID, "diffrec_chain: too many workgroups at B=%lld N=%lld", (long long)B, (long long)N);
   DrEpilogue ep = {};
   ep.bias = g0;
   ep.e = e_next;
@@ -291,6 +163,6 @@ extern "C" int chaorec_diffrec_chain_f32(const float *z, int64_t ldz, const floa
   ep.out0 = p_next;
   ep.out1 = z_next;
   ep.ldo = ldo;
-  hipLaunchKernelGGL(dr_tile_kernel<DR_CHAIN>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z, ldz, G, ldg, B, N, K, MT, NT, ep);
+  hipLaunchKernelGGL(dr_tile_kernel<DR_CHAIN>, dim3((unsigned)g.blocks), dim3(256), 0, (hipStream_t)stream, z, ldz, G, ldg, B, N, K, g.MT, g.NT, ep);
   return check_launch("dr_tile_kernel<chain>");
 }

@@ -7,9 +7,8 @@ import torch
 
 from . import _lib
 from . import ops as _ops
-from .ops import _f32, _f32c, _need_cuda, _ptr, _stream, col_sum
-from .ops_dense import gemm_nn_bf16x3, gemm_raw, gemm_tn_bf16x3
-from .ops_diffmm import _diffmm_big, diffmm_ld
+from .ops import _f32, _need_cuda, _ptr, _stream
+from .ops_diffmm import _out_layer_backward, _out_layer_buffers
 
 __all__ = [
     "diffrec_check_shape", "diffrec_tiles", "_diffrec_rows16", "diffrec_out_loss_raw", "_DiffRecX0Loss", "diffrec_x0_loss",
@@ -47,19 +46,12 @@ def diffrec_out_loss_raw(h, W_out, b_out, bits, w, pt):
     diffrec_check_shape(B, I, H)
     h, W_out = _diffrec_rows16(h), _diffrec_rows16(W_out)
     b_out = _f32("diffrec", b_out, "b_out", (I,))
-    if W_out.shape[1] != H or tuple(bits.shape) != (B, (I + 31) // 32) or bits.dtype != torch.int32 or not bits.is_contiguous():
-        raise ValueError("diffrec: W_out must be [I, H] and bits int32 [B, ceil(I / 32)]")
-    if w.dtype != torch.float64 or tuple(w.shape) != (B,):
-        raise ValueError("diffrec: the weight is float64 [B] (SNR works on float64 tables)")
+    w, ld, d_out, part = _out_layer_buffers("diffrec", h, W_out, bits, w, diffrec_tiles()[1])
     if tuple(pt.shape) != (B,):
         raise ValueError("diffrec: pt must be [B]")
     lib, dev = _lib.load(), h.device
-    w, pt = w.contiguous(), pt.to(torch.float64).contiguous()
+    pt = pt.to(torch.float64).contiguous()
     c_row = (w * (2.0 / (float(B) * float(I))) / pt).to(torch.float32)      # formed in double
-    bn = diffrec_tiles()[1]
-    ld, NT = diffmm_ld(I), (I + bn - 1) // bn
-    d_out = torch.empty((B, ld), dtype=torch.float32, device=dev)
-    part = torch.empty((B, NT), dtype=torch.float32, device=dev)
     reloss = torch.empty(B, dtype=torch.float64, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lib.chaorec_diffrec_out_loss_f32(_ptr(h), h.stride(0), _ptr(W_out), W_out.stride(0), _ptr(b_out), _ptr(bits), _ptr(w), _ptr(pt),
@@ -69,8 +61,7 @@ def diffrec_out_loss_raw(h, W_out, b_out, bits, w, pt):
 
 class _DiffRecX0Loss(torch.autograd.Function):
     """(h [B, H], W_out [I, H], b_out [I]) -> loss [1], reloss_rows [B] float64 (Model/DiffRec.py:86-89, :445-461).  Forward: the
-    one-pass launch, which leaves d loss / d out.  Backward, as DiffMM's node: dW_out = d_out^T (g h), dh = g (d_out W_out),
-    db_out = g colsum(d_out); g is folded into the [B, H] operands, d_out is not passed over again."""
+    one-pass launch, which leaves d loss / d out.  Backward: ops_diffmm._out_layer_backward, DiffMM's node's as well."""
 
     @staticmethod
     def forward(ctx, h, W_out, b_out, bits, w, pt):
@@ -81,20 +72,7 @@ class _DiffRecX0Loss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gr):
-        h, W_out, d_full = ctx.saved_tensors
-        B, I = h.shape[0], W_out.shape[0]
-        g = _f32c(g).reshape(1)
-        d_out = d_full[:, :I]
-        dW = dh = db = None
-        if ctx.needs_input_grad[1]:
-            gh = h * g
-            dW = gemm_tn_bf16x3(d_out, gh) if _diffmm_big(B) else gemm_raw(d_out.contiguous(), gh.contiguous(), transA=True)
-        if ctx.needs_input_grad[0]:
-            dh = gemm_nn_bf16x3(d_out, W_out) if _diffmm_big(B) else gemm_raw(d_out.contiguous(), W_out.contiguous())
-            dh = dh * g
-        if ctx.needs_input_grad[2]:
-            db = col_sum(d_full)[:I] * g
-        return dh, dW, db, None, None, None
+        return _out_layer_backward(ctx, g) + (None,) * 3
 
 
 def diffrec_x0_loss(h, W_out, b_out, bits, w, pt):

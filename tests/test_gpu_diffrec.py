@@ -109,6 +109,30 @@ def test_loss_node(dev, B, I, Hd):
     assert not failures, failures
 
 
+@pytest.mark.parametrize("Hd", [4, 68, 132])
+@pytest.mark.parametrize("I", [1, 129, 259])
+@pytest.mark.parametrize("B", [1, 129])
+def test_loss_launch_is_the_diffmm_launch_without_its_second_term(dev, B, I, Hd):
+    """The two loss launches run one tile loop and one x0-error epilogue (csrc/out_tile.h).  With pt = 1 both c_row are the
+    same float; with x0E = 0, F = 0 and e_loss = 0 DiffMM's r and acc2 are exactly 0 and kf = 0: the rows and the loss agree
+    in their bits, d_out by value over all ld columns (acc + 0 acc2 turns a -0 into +0, so not by bits).  I = 259 is three
+    column tiles, five of the eight dealt workgroups return early; H = 68 and 132 end in a partial segment after one and
+    after two full ones; H = 4 is a single short tile."""
+    from chaorec_amd import ops
+    h, W, b, x0, wt, _ = loss_case(B, I, Hd, 10000 * B + 10 * I + Hd)
+    th, tW, tb, tw = (torch.from_numpy(a).to(dev) for a in (h, W, b, wt))
+    bits = torch.from_numpy(dh.bit_table(x0).view(np.int32)).to(dev)
+    x0E, F = torch.zeros(B, ops.DIFFMM_D, device=dev), torch.zeros(I, ops.DIFFMM_D, device=dev)
+    m_loss, m_rows, _, m_d, m_r = ops.diffmm_out_loss_raw(th, tW, tb, bits, x0E, F, tw, 0.0)
+    r_loss, r_rows, r_d = ops.diffrec_out_loss_raw(th, tW, tb, bits, tw, torch.ones(B, dtype=torch.float64, device=dev))
+    torch.cuda.synchronize()
+    assert not m_r.cpu().numpy().any()
+    assert same_bits(m_rows.cpu().numpy(), r_rows.cpu().numpy()), "diff_rows against reloss_rows"
+    assert same_bits(m_loss.cpu().numpy(), r_loss.cpu().numpy()), "loss"
+    assert m_d.shape == r_d.shape == (B, ops.diffmm_ld(I))
+    assert np.array_equal(m_d.cpu().numpy(), r_d.cpu().numpy()), "d_out over all ld columns"
+
+
 # ---- (b) the chain step ---------------------------------------------------------------------------------------------------------
 def chain_case(B, N, K, seed):
     rng = np.random.default_rng(seed)
