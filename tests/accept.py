@@ -73,6 +73,23 @@ def same_bits_t(a, b):
     return torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
+# ---- the exact row selection: what rows_topk and rows_topk_wide are compared with ----------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.uint32)
+
+
+def order_key(x):
+    """mc_order_key / f32_to_ord: ascending with the float order, by bit pattern (-0 < +0, a NaN by sign and payload)."""
+    b = bits(x)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
+
+
+def numpy_topk(x, K):
+    comb = (order_key(x).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.arange(x.shape[1], dtype=np.uint64))[None, :]
+    idx = np.argsort(comb, axis=1)[:, ::-1][:, :K]          # key descending, then index ascending: the entries are distinct
+    return idx.astype(np.int64), np.take_along_axis(x, idx, 1)
+
+
 def user_item_dict(edges):
     d = {}
     for u, i in np.asarray(edges).tolist():

@@ -219,6 +219,26 @@ def test_ranklist_meets_the_cap(dev, name):
         assert torch.equal(torch.softmax((m.mu_beta * m.item_topics).sum(-1), 1), m.aspect_probability)
 
 
+def test_several_user_ranges_equal_one_range(dev, monkeypatch):
+    """A staging cap of 7 rows: 42 ranges of 7 users (user_begin = 7, 14, ...) and a short last one of 6, against the one
+    range the small fixture otherwise fits -- the same list for ALL users."""
+    from chaorec_amd import ops_vae
+    g, _, _ = case("small", dev)
+    m = make_model(g, dev)
+    U, I, topk = g["U"], g["I"], g["topk"]
+    gen = torch.Generator().manual_seed(78)
+    m.mu_theta = torch.randn(U, dh.A, dh.K, generator=gen).to(dev)
+    m.mu_beta = torch.randn(I, dh.A, dh.K, generator=gen).to(dev)
+    assert ops_vae.dualvae_range_users(I) >= U
+    one = m.gene_ranklist(topk)
+    monkeypatch.setattr(ops_vae, "DUALVAE_STAGING_BYTES", 7 * 4 * I)
+    assert ops_vae.dualvae_range_users(I) == 7 and U % 7 == 6
+    many = m.gene_ranklist(topk)
+    assert many.dtype == torch.int64 and tuple(many.shape) == (U, topk)
+    differ = (many != one).any(1).nonzero().flatten().tolist()
+    assert not differ, f"users {differ[:10]} ... rank differently in ranges of 7"
+
+
 def test_no_batch_by_table_buffer(dev):
     """U = I = 131 072, B = 2 048: one [B, I] fp32 matrix is 1 GiB.  Parameters, Adam state and gradients exist BEFORE the
     measured step."""

@@ -238,6 +238,23 @@ def test_ranklist_meets_the_cap(dev, name):
     assert again.is_cuda and torch.equal(again.cpu(), ranks)
 
 
+def test_several_user_ranges_equal_one_range(dev, monkeypatch):
+    """A staging cap of 7 rows: 42 ranges of 7 users (user_begin = 7, 14, ...) and a short last one of 6, against the one
+    range the small fixture otherwise fits -- the same list for ALL users."""
+    from chaorec_amd import ops_vae
+    g = mh.load_fixture(GOLDEN, "small")
+    m = make_model(g, dev)
+    U, I, topk = g["U"], g["I"], int(g["topk"])
+    assert ops_vae.macrid_range_users(I) >= U
+    one = m.gene_ranklist(topk)
+    monkeypatch.setattr(ops_vae, "MACRID_STAGING_BYTES", 7 * 4 * I)
+    assert ops_vae.macrid_range_users(I) == 7 and U % 7 == 6
+    many = m.gene_ranklist(topk)
+    assert many.dtype == torch.int64 and tuple(many.shape) == (U, topk)
+    differ = (many != one).any(1).nonzero().flatten().tolist()
+    assert not differ, f"users {differ[:10]} ... rank differently in ranges of 7"
+
+
 def test_topk_kernel_is_exact_with_ties_to_the_lowest_index(dev):
     from chaorec_amd import ops
     gen = torch.Generator().manual_seed(3)

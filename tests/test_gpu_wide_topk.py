@@ -1,6 +1,7 @@
 """Rank lists past 64 columns on the MI355X (csrc/topk_wide.hip, the wave-per-row kernel of csrc/metrics.hip): staged exact
 scores + wide row selection against the oracle bit for bit, the first 64 columns against the narrow route, the range loop,
-ops.rows_topk alone against a numpy sort by the same bit-pattern key, the metrics up to k = 1024 against the python loops, four
+ops.score_rows alone against the oracle's whole rows (both store paths, the pad columns left alone), ops.rows_topk alone
+against a numpy sort by the same bit-pattern key (accept.numpy_topk), the metrics up to k = 1024 against the python loops, four
 models' gene_ranklist(topk=100) and the training loop's --topk 20 100.
 
 Shapes: the smallest at which each path is taken -- I = K and K + 1 (a row that is all winners / one loser), item counts that
@@ -11,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from accept import to_dev
+from accept import bits, numpy_topk, to_dev
 from chaorec_amd import ops, ranking, utils
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,6 @@ DEV = torch.device("cuda:0")
 
 def t(x, dtype=None):
     return to_dev(x, dtype, DEV)
-
-
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.uint32)
 
 
 def history(rng, U, I, per_user=12):
@@ -110,6 +107,37 @@ def test_user_ranges_equal_one_range():
     assert np.array_equal(host.numpy(), one[0])
 
 
+SENTINEL = -12345.0
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("U,I,D", [(33, 66, 64), (100, 1001, 8), (33, 1300, 192)])
+def test_score_rows_alone_equals_the_oracle_over_the_whole_block(oracle, U, I, D, offset):
+    """ops.score_rows without the selection behind it: every staged score, not only the ones a top-K list shows.  The oracle
+    sorts whole rows, so K = I returns all of them; scattered back by index they are the block.  offset 1: `out` starts one
+    float off a 16-byte boundary, the scalar store path of score_rows_kernel."""
+    ue, ie, hist = case(U, I, D, "a", seed=U + I + D)
+    idx, val = oracle.score_topk(ue, ie, hist, 1e-6, I, 0)
+    assert np.array_equal(np.sort(idx, axis=1), np.broadcast_to(np.arange(I), (U, I)))
+    ref = np.empty((U, I), np.float32)
+    np.put_along_axis(ref, idx, val, 1)
+    in_hist = np.zeros((U, I), bool)
+    for u in range(U):
+        in_hist[u, hist[1][hist[0][u]:hist[0][u + 1]]] = True
+    assert in_hist.any() and np.array_equal(bits(ref[in_hist]), bits(np.full(in_hist.sum(), 1e-6, np.float32)))
+    ld = (I + 3) // 4 * 4                                   # 68, 1004 and 1300: two cases have pad columns
+    buf = torch.full((U * ld + 4,), SENTINEL, dtype=torch.float32, device=DEV)
+    out = buf[offset:offset + U * ld]
+    assert (out.data_ptr() % 16 == 0) == (offset == 0)
+    sc = ops.score_rows(t(ue), t(ie), (t(hist[0]), t(hist[1])), 1e-6, 0, U, out=out, ld=ld)
+    assert sc.data_ptr() == out.data_ptr() and tuple(sc.shape) == (U, ld)
+    got, whole = sc.cpu().numpy(), buf.cpu().numpy()
+    assert np.array_equal(bits(got[:, :I]), bits(ref))
+    assert np.array_equal(bits(got[in_hist.nonzero()]), bits(ref[in_hist]))              # (the masked entries, said out loud)
+    assert (got[:, I:] == SENTINEL).all(), "a pad column was written"
+    assert (whole[:offset] == SENTINEL).all() and (whole[offset + U * ld:] == SENTINEL).all()
+
+
 def test_wide_call_leaves_hints_and_counters_alone():
     U, I, D, K = 33, 1300, 64, 100
     ue, ie, hist = case(U, I, D, "a", seed=2)
@@ -124,18 +152,6 @@ def test_wide_call_leaves_hints_and_counters_alone():
 
 
 # ---------------------------------------------------------------------------------------------- ops.rows_topk alone
-def order_key(x):
-    """mc_order_key / f32_to_ord: ascending with the float order, by bit pattern (-0 < +0, a NaN by sign and payload)."""
-    b = bits(x)
-    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
-
-
-def numpy_topk(x, K):
-    comb = (order_key(x).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.arange(x.shape[1], dtype=np.uint64))[None, :]
-    idx = np.argsort(comb, axis=1)[:, ::-1][:, :K]          # key descending, then index ascending: the entries are distinct
-    return idx.astype(np.int64), np.take_along_axis(x, idx, 1)
-
-
 @pytest.mark.parametrize("n,I,K,pad", [(129, 257, 100, 2), (1, 128, 128, 3), (129, 201, 200, 2), (1, 8449, 1024, 2),
                                        (129, 8449, 1000, 4), (129, 1025, 1024, 0), (1, 257, 65, 0)])
 def test_rows_topk_wide_against_numpy(n, I, K, pad):

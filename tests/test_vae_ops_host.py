@@ -1,7 +1,8 @@
 """The per-op restatements of tests/vae_ops_host.py, checked on the CPU: chained into one training step of each model on
 the `small` fixtures they must reproduce multvae_host.step, macridvae_host.step and dualvae_host.step -- restatements that
-tests/test_*vae_host.py tie to the reference's goldens -- in values and gradients to float64 rounding; and the numpy
-restatement of the counter RNG is in range, deterministic and BITS-dependent.  No GPU."""
+tests/test_*vae_host.py tie to the reference's goldens -- in values and gradients to float64 rounding; the ranking ops
+(macrid_scores, dualvae_scores) fed those restatements' own latents give their eval-mode scores, and masked() is checked
+by hand; and the numpy restatement of the counter RNG is in range, deterministic and BITS-dependent.  No GPU."""
 import os
 import sys
 
@@ -142,6 +143,54 @@ def test_dualvae_ops_chain_into_the_step():
             same(s[k].detach().numpy(), ref[name][k], f"{name} {k}")
     for n, got, want in zip(dh.NAMES, grads, ref["grads"]):
         same(got.numpy(), want, f"grad {n}")
+
+
+def test_macrid_scores_equal_the_model_restatements():
+    """The ranking op fed the model restatement's own eval-mode zh, items, cates gives macridvae_host.eval_scores."""
+    g = ch.load_fixture(GOLDEN, "small")
+    w = _macrid_weights(g)
+    W1, b1, W2, b2, E, Kemb = (t64(x) for x in w)
+    users = np.arange(g["U"])
+    x = t64(vo.dense_rows(g["rowptr"], g["col"], users, g["I"]))
+    xs = x / torch.clamp(x.sum(1).sqrt(), min=1e-12)[:, None]
+    items, cates = ch.concept_weights(E, Kemb)
+    zh, _ = ch.latents(W1, b1, W2, b2, cates, xs, None)
+    got = vo.macrid_scores(zh, items, cates, ch.TAU)
+    assert got.dtype == torch.float64 and got.shape == (g["U"], g["I"])
+    same(got.numpy(), ch.eval_scores(w, g["rowptr"], g["col"], users).numpy(), "macrid scores")
+    assert vo.macrid_scores(zh.float(), items.float(), cates.float(), ch.TAU).dtype == torch.float32
+
+
+def test_dualvae_scores_equal_the_model_restatements():
+    """Likewise dualvae_host.scores: z = mu_theta, table = mu_beta, the decoders' tanh rows, the RAW aspect weight."""
+    g = dh.load_fixture(GOLDEN, "small")
+    weights, _ = _dual_weights_and_tables(g)
+    p = {n: t64(w) for n, w in zip(dh.NAMES, weights)}
+    gen = torch.Generator().manual_seed(77)
+    mt = torch.randn(g["U"], dh.A, dh.K, generator=gen, dtype=torch.float64)
+    mb = torch.randn(g["I"], dh.A, dh.K, generator=gen, dtype=torch.float64)
+    zh = torch.tanh(mt @ p["user_decoder.fc_out0.weight"].t() + p["user_decoder.fc_out0.bias"])
+    th = torch.tanh(mb @ p["item_decoder.fc_out0.weight"].t() + p["item_decoder.fc_out0.bias"])
+    w = (mb * p["item_topics"]).sum(-1)
+    got = vo.dualvae_scores(mt, zh, mb, th, w)
+    assert got.dtype == torch.float64 and got.shape == (g["U"], g["I"])
+    same(got.numpy(), dh.scores(weights, mt.numpy(), mb.numpy()), "dualvae scores")
+    users = np.array([5, 0, g["U"] - 1])
+    same(vo.dualvae_scores(mt[users], zh[users], mb, th, w).numpy(), dh.scores(weights, mt.numpy(), mb.numpy(), users),
+         "dualvae scores of three users")
+
+
+def test_masked_sets_the_history_of_user_begin_plus_row():
+    rowptr = np.array([0, 2, 2, 6, 7], dtype=np.int64)
+    col = np.array([0, 4, -1, 1, 3, 5, 2], dtype=np.int64)             # user 2 holds the stray columns -1 and I = 5
+    sc = np.arange(10, dtype=np.float32).reshape(2, 5) + 1
+    got = vo.masked(sc, rowptr, col, 2, 1e-6)
+    want = sc.copy()
+    want[0, [1, 3]], want[1, 2] = 1e-6, 1e-6
+    assert got.dtype == np.float32 and np.array_equal(got, want) and sc[0, 1] == 2           # a copy
+    want = sc.copy()
+    want[0, [0, 4]] = 7.0                                               # user 0's row, user 1 holds nothing
+    assert np.array_equal(vo.masked(sc, rowptr, col, 0, 7.0), want)
 
 
 def test_counter_rng_restatement():

@@ -4,6 +4,7 @@ plus THE numpy uint64 restatement of the counter RNG (mix64 of csrc/common.h; dr
 here under the names vae_key, vae_uniform): mvgae_host, dragon_host and the graph models' GPU tests import it.
 A helper module, not a conftest: imported by tests/test_vae_ops_host.py, which chains the ops into one step of each model against multvae_host / macridvae_host / dualvae_host (themselves tied to the reference's goldens).
 It is the oracle for comparing the kernels op by op: each op alone, any upstream gradient, any mask.
+The ranking half (macrid_scores, dualvae_scores, masked) restates what gene_ranklist stages: tests/test_gpu_vae_rank_ops.py.
 
 Every `*_fwd` function is plain torch on tensors of one dtype: run in float64 it is the oracle, run in float32 on the same
 inputs it is "the reference arithmetic's own rounding" a bound is taken from.  `run()` is the numpy front: inputs in,
@@ -212,6 +213,37 @@ def dualvae_contrast(x, x_):
     acl = torch.exp(torch.einsum("bak,bck->bac", x_, x) / 0.2).sum(-1)
     ncl = torch.exp(torch.einsum("bak,cak->bac", x_, x) / 0.2).sum(-1)
     return -torch.log(pos / (acl + ncl)).sum(-1).mean()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the ranking half: the scores gene_ranklist stages, and the mask over them
+# ---------------------------------------------------------------------------------------------------------------
+def macrid_scores(zh, items, cates, tau):
+    """zh [n, K, D], items [I, D], cates [I, K] -> [n, I]: log sum_k cates[i, k] exp(<zh[u, k], items[i]> / tau)."""
+    p = 0.0
+    for k in range(cates.shape[1]):
+        p = p + cates[:, k] * torch.exp(zh[:, k] @ items.t() / tau)
+    return torch.log(p)
+
+
+def dualvae_scores(z, zh, table, th, w):
+    """z [n, 5, 25], zh [n, 5, 20], table [I, 5, 25], th [I, 5, 20], w [I, 5] (as given: no softmax) -> [n, I]:
+    sum_a w[i, a] sigmoid(z_ua . table_ia + tanh(zh_ua . th_ia))."""
+    s = 0.0
+    for a in range(w.shape[1]):
+        s = s + w[:, a] * torch.sigmoid(z[:, a] @ table[:, a].t() + torch.tanh(zh[:, a] @ th[:, a].t()))
+    return s
+
+
+def masked(scores, rowptr, col, user_begin, mask_value):
+    """A copy of the numpy block scores [n, I] with row r's entries at the history columns of user user_begin + r set to
+    mask_value; a column outside [0, I) is ignored."""
+    out = np.array(scores)
+    I = out.shape[1]
+    for r in range(out.shape[0]):
+        c = np.asarray(col[rowptr[user_begin + r]:rowptr[user_begin + r + 1]], dtype=np.int64)
+        out[r, c[(c >= 0) & (c < I)]] = mask_value
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
