@@ -18,7 +18,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libchaorec_hip.so")
 SOURCES = ["spmm.hip", "spmm_fewsrc.hip", "bpr.hip", "bpr_frontier.hip", "score_topk.hip", "topk_wide.hip", "gemm.hip", "gemm_bf16x3.hip", "metrics.hip", "graph_dropout.hip",
            "rowops.hip", "feature_adam.hip", "exchange.hip", "dgcf.hip", "multvae.hip", "macridvae.hip",
-           "dualvae.hip", "usergraph.hip", "mvgae.hip", "diffmm.hip", "graphaug.hip", "mhrec.hip", "grade.hip", "cfdiff.hip", "diffrec.hip", "bspm.hip", "adagcl.hip"]
+           "dualvae.hip", "usergraph.hip", "mvgae.hip", "diffmm.hip", "graphaug.hip", "mhrec.hip", "grade.hip", "cfdiff.hip", "diffrec.hip", "lightgode.hip", "bspm.hip", "adagcl.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-mllvm", "-amdgpu-mfma-vgpr-form"]   # MFMA results in VGPRs: no v_accvgpr_read per compared score
 

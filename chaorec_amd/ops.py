@@ -1104,7 +1104,7 @@ def mean_all(x):
 # ---- public name of theirs is still reachable as chaorec_amd.ops.<name>: resolved on first use (PEP 562) against the modules'
 # ---- own __all__ lists, then kept in this module's globals.
 _FAMILY_MODULES = ("ops_dense", "ops_adam", "ops_sparse_family", "ops_dgcf", "ops_vae", "ops_usergraph", "ops_mvgae",
-                   "ops_diffmm", "ops_edges", "ops_mhrec", "ops_bspm", "ops_cfdiff", "ops_wide", "ops_diffrec")
+                   "ops_diffmm", "ops_edges", "ops_mhrec", "ops_bspm", "ops_cfdiff", "ops_wide", "ops_diffrec", "ops_lightgode")
 
 
 def _family(module):

@@ -1,5 +1,5 @@
 """Compatibility module for the tests and tools that say `ops_extra.<name>`: it re-exports the family modules (one per
-kernel file: ops_adam, ops_sparse_family, ops_dgcf, ops_vae, ops_usergraph, ops_mvgae, ops_diffmm, ops_edges, ops_mhrec, ops_bspm, ops_cfdiff, ops_wide, ops_diffrec) and
+kernel file: ops_adam, ops_sparse_family, ops_dgcf, ops_vae, ops_usergraph, ops_mvgae, ops_diffmm, ops_edges, ops_mhrec, ops_bspm, ops_cfdiff, ops_wide, ops_diffrec, ops_lightgode) and
 the shared helpers that once stood here, under their old names.  It defines nothing of its own -- no function, no class; new
 code imports the family module or uses `chaorec_amd.ops.<name>`."""
 from functools import partial
@@ -18,5 +18,6 @@ from .ops_bspm import *  # noqa: F401,F403
 from .ops_cfdiff import *  # noqa: F401,F403
 from .ops_wide import *  # noqa: F401,F403
 from .ops_diffrec import *  # noqa: F401,F403
+from .ops_lightgode import *  # noqa: F401,F403
 
 _ug_i32 = partial(_i32, "usergraph")

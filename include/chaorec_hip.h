@@ -1390,6 +1390,33 @@ int chaorec_diffrec_chain_f32(const float *z, int64_t ldz, const float *G, int64
                               float *p_next, float *z_next, int64_t ldo, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * LightGODE (Model/LightGODE.py:97-146) -- csrc/lightgode.hip.  Additive to ABI 16: new names only.  fp32, D = 64, no float
+ * atomics, no scratch, the same bits every run.  The alignment + uniformity loss of a batch of B (user, item) pairs with the
+ * pair terms on the f32 MFMA pipe (v_mfma_f32_32x32x2_f32); no [B, B] and no [B (B - 1) / 2] buffer.
+ * chaorec_lightgode_check_shape: CHAOREC_E_INVALID for D != 64, B < 2 (the reference's mean over zero pairs) or B > 8192 (the
+ * backward keeps the batch's ids in LDS); nothing launched.  chaorec_lightgode_workspace: the floats of `workspace` for B.
+ * --------------------------------------------------------------------------------------------------------------- */
+int chaorec_lightgode_check_shape(int64_t B, int32_t D);
+int chaorec_lightgode_workspace(int64_t B, int32_t D, int64_t *n_floats);
+/* x_b = normalize(tab_u[users[b]]), y_b = normalize(tab_i[items[b]]) (F.normalize: / max(|e|, 1e-12)); tab_u [U, 64], tab_i
+ * [I, 64] (one joined table: tab_i = tab_u + item_offset * 64), ids int64 [B], LOCAL item ids.  Per side, with
+ * e_ij = exp(-2 max(n_i + n_j - 2 <z_i, z_j>, 0)), r_i = sum_{j != i} e_ij and S = 1/2 sum_i r_i:
+ *   out[4] = (loss, align, unif_u, unif_i): align = mean_b |x_b - y_b|^2, unif = log(S / (B (B - 1) / 2)),
+ *            loss = align + gamma (unif_u + unif_i) / 2; loss[0] = out[0]
+ *   row_grad fp32 [2, B, 64] (may be NULL): d loss / d the UN-normalised gathered rows, users' then items',
+ *            (g - z <z, g>) / max(|e|, 1e-12) with g = (gamma / 2) (-4 / S) (r_i z_i - sum_{j != i} e_ij z_j) +- 2 (x_b - y_b) / B
+ * Four launches (rows, centre, pairs, finish): the pair terms are evaluated on rows shifted by a common vector (a mean of 64 of
+ * them), which distances do not see; the partial sums of the pair launch are added in split order, S in double. */
+int chaorec_lightgode_loss_f32(const float *tab_u, const float *tab_i, int64_t U, int64_t I, const int64_t *users,
+                               const int64_t *items, int64_t B, int32_t D, float gamma, float *workspace, int64_t ws_floats,
+                               float *out, float *loss, float *row_grad, void *stream);
+/* g_u[users[b]] += go row_grad[0, b], g_i[items[b]] += go row_grad[1, b]; go = *grad_out (device scalar) or 1 if NULL.  One
+ * owner wave per table row, repeated ids added in batch order into the row's ONE running float sum, which starts from what the
+ * buffer holds (zero-filled by the caller).  g_u and g_i may be the two parts of one joined buffer. */
+int chaorec_lightgode_bwd_f32(const float *row_grad, const int64_t *users, const int64_t *items, int64_t B, int32_t D,
+                              int64_t U, int64_t I, const float *grad_out, float *g_u, float *g_i, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * AdaGCL (Model/AdaGCL.py) -- csrc/adagcl.hip.  Additive to ABI 16: new names only.
  * The E-sized work of the two view generators over ONE symmetric-pattern CSR of N = U + I nodes: rowptr int64 [N + 1],
  * col int32 [E], entry_row int32 [E], tentry int32 [E] (the stored entry of the reversed pair).  D = 64 is what the keep
